@@ -3,11 +3,18 @@
 cross-attention decoder + DPT pointmap heads + adaptor, 512x512 pairs, bf16 MFMA operands (BASELINE.json configs[1]).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   (+ the last timed step's outputs as DIR/<name>.npy)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full   (+ roofline, reference-policy legs, other configurations, CPU baseline)
     python bench.py --gpus 8 --steps 10 --warmup 3         (no torchrun: bench.py starts its own ranks, one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One process per GPU; every rank runs `--pairs` independent image pairs per step (weak scaling, no data-path
 collective: pairs are independent in the forward).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the headline line.  Everything else the line can carry — the
+roofline passes, the reference-policy and precision legs, the 224x224 / batch-sweep / other-configuration / training-step legs, the
+CPU baseline, and at N > 1 the training step with its gradient exchange — runs only with `--full` (the `--no-*` options then drop
+single parts of it).
 """
 import argparse
 import json
@@ -26,6 +33,8 @@ PEAK_HBM_GBS = 8000.0      # HBM3E peak (same guide)
 PMC_TRAFFIC_FILE = "r6_pmc_traffic.json"
 FWD_PAIRS = 128            # pairs per GPU per forward step: 56 GB; 64 -> 96 -> 128 pairs measured +0.7 / +0.9 % (same box), 256: see DESIGN section 7
 TRAIN_PAIRS = 64           # pairs per GPU per training step: 216 GB of the 288 GB at 512x512 with DPT heads (32: 96-98 pairs/s, 64: 100-101, 80: 101.9 at 267 GB)
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: at most this many bytes of float32 in all (a seeded sample of rows beyond it)
+DUMP_SEED = 1234
 
 
 def gflop_enc_dec(img, patch=16, enc_dim=1024, enc_depth=24, dec_dim=768, dec_depth=12, n_extra=0):
@@ -57,14 +66,20 @@ def parse():
     ap.add_argument("--attention", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: e4m3 K=64 MFMA attention kernel (BASELINE configs[4]; forward only)")
     ap.add_argument("--graph", action="store_true", help="replay the forward from a captured hipGraph (latency mode, small --pairs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the roofline passes, the reference-policy legs, the extra legs and the CPU baseline "
+                         "(at N > 1: the training step with its gradient exchange); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32; a fixed, seeded sample of "
+                         f"rows when the outputs exceed {DUMP_BUDGET_BYTES >> 20} MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-reference-policy", action="store_true",
-                    help="skip the extra legs: fp32-class heads beside the bf16 transformer, everything fp32-class, linear-head (enc+dec) run")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="with --full: skip the extra legs: fp32-class heads beside the bf16 transformer, everything fp32-class, linear-head (enc+dec) run")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline passes")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the `fwd_224` (224x224 pairs), `batch_sweep` (1 / 2 / 4 / 8 pairs), `other_configs` (BASELINE configs[3], [4]) and `train_step` (BASELINE configs[2]) legs of the default line")
-    ap.add_argument("--train-pairs", type=int, default=TRAIN_PAIRS, help="pairs per GPU of the `train_step` leg inside the forward line")
-    ap.add_argument("--train-steps", type=int, default=3, help="timed steps of the `train_step` leg")
+                    help="with --full: skip the `fwd_224` (224x224 pairs), `batch_sweep` (1 / 2 / 4 / 8 pairs), `other_configs` (BASELINE configs[3], [4]) and `train_step` (BASELINE configs[2]) legs")
+    ap.add_argument("--train-pairs", type=int, default=TRAIN_PAIRS, help="pairs per GPU of the `train_step` leg inside the forward line (--full)")
+    ap.add_argument("--train-steps", type=int, default=3, help="timed steps of the `train_step` leg (--full)")
     ap.add_argument("--single-stream", action="store_true",
                     help="no two-stream execution of independent sub-graphs at large batch (engine.concurrent(False)): what the "
                          "roofline pass and the committed kernel profiles use — per-kernel durations are only defined without overlap")
@@ -73,7 +88,10 @@ def parse():
                     help="comma-separated batch sizes (pairs), e.g. 1,2,4,8,16,64: adds `batch_sweep` to the JSON line — the forward at each "
                          "size, timed like the reference's own harness (examples/models/dust3r/profile_dust3r.py:31-46: randn images, "
                          "no_grad, Timer.blocked_autorange().mean), eager and (up to 16 pairs) replayed from a hipGraph")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def make_views(B, H, W, rank, dev):
@@ -751,6 +769,38 @@ def batch_sweep(model, sizes, args, dev):
     return out
 
 
+def step_outputs(out, mode):
+    "name -> tensor: what a caller of the timed step receives (forward: both views' result dicts; training: the loss)."
+    if mode == "train":
+        return {"loss": out[0]["pts3d"]}
+    return {f"view{v + 1}_{k}": t for v, res in enumerate(out) for k, t in res.items()}
+
+
+def dump_outputs(arrays, out_dir):
+    """Write name -> tensor as out_dir/<name>.npy in float32.  Within DUMP_BUDGET_BYTES everything is written; beyond it every array
+    keeps the same share of its rows (all dims but the last, e.g. the pixels of a [B, H, W, C] map), drawn by a generator seeded
+    with DUMP_SEED and sorted: the same arguments give the same sample, so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values()) * 4
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    written = {}
+    for name, t in sorted(arrays.items()):
+        t = t.detach()
+        flat = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+        rows = flat.shape[0]
+        keep = rows if frac >= 1.0 else max(1, int(rows * frac))
+        if keep < rows:
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(DUMP_SEED))[:keep].sort().values
+            flat = flat[idx.to(flat.device)]
+            a = flat.float().cpu().numpy()
+        else:
+            a = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[name] = {"shape": list(t.shape), "rows_written": keep, "rows": rows}
+    return written
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -841,6 +891,9 @@ def main():
         from uniception_amd.distributed import max_over_ranks
         dt = max_over_ranks(dt, dev)
     assert torch.isfinite(out[0]["pts3d"]).all()
+    if args.dump_outputs and rank == 0:
+        written = dump_outputs(step_outputs(out, args.mode), args.dump_outputs)
+        print(f"[bench] outputs of the last timed step -> {args.dump_outputs}: {json.dumps(written)}", file=sys.stderr, flush=True)
 
     pairs_total = world * args.pairs * args.steps
     value = pairs_total / dt
@@ -878,12 +931,12 @@ def main():
     }
     if world > 1:
         # the multi-GPU line measures the multi-GPU design: forward pairs/s above is weak scaling with no data-path
-        # collective; the bucketed gradient all-reduce only exists in the training step, so at N > 1 EVERY rank also runs it
+        # collective; the bucketed gradient all-reduce only exists in the training step, so with --full at N > 1 EVERY rank also runs it
         line["rccl_ranks"] = dist.get_world_size()
         line["backend"] = dist.get_backend()
         if not fwd:
             line["exchange"] = exchange_summary(trainer.comm_stats(), dt / args.steps * 1e3)
-        elif not args.no_extra_legs and args.precision == "bf16" and not args.graph:
+        elif args.full and not args.no_extra_legs and args.precision == "bf16" and not args.graph:
             del out
             try:
                 leg = train_step_leg(args, dev, pairs=args.train_pairs, steps=args.train_steps, rank=rank, world=world)
@@ -892,7 +945,7 @@ def main():
             line["train_step"] = leg
     if share:
         line["config"]["shared_gpu_dry_run"] = "ranks share devices, gloo process group: control-flow check only, not a measurement"
-    if rank == 0 and world == 1 and not fwd and not args.no_roofline and args.precision == "bf16":
+    if rank == 0 and world == 1 and not fwd and args.full and not args.no_roofline and args.precision == "bf16":
         # training: the same kernel family carries the forward and the data-gradient GEMMs (the TN weight-gradient kernel is
         # a separate, smaller share): all dense bf16 uc_gemm launches of a step, forward and backward
         with engine.concurrent(False):
@@ -900,24 +953,24 @@ def main():
             torch.cuda.synchronize()
             line["roofline"], line["roofline_families"] = roofline_pass(step, v1, args.precision, min(args.steps, 2))
     if rank == 0 and world == 1 and fwd:
-        if not args.no_roofline and args.precision == "bf16":
+        if args.full and not args.no_roofline and args.precision == "bf16":
             with engine.concurrent(False):   # per-launch durations are only defined when kernels do not overlap
                 step()                       # (untimed: the allocator's blocks of the side streams are not reusable here — first step mallocs)
                 torch.cuda.synchronize()
                 line["roofline"], line["roofline_families"] = roofline_pass(step, v1, args.precision, min(args.steps, 3))
             line["roofline"]["schedule"] = ("single-stream pass (engine.concurrent(False), = bench.py --single-stream, the command of the "
                                             "committed profiles); the timed region runs two kernel streams")
-        if not args.no_reference_policy and args.precision == "bf16" and not args.graph:
+        if args.full and not args.no_reference_policy and args.precision == "bf16" and not args.graph:
             line["reference_policy"] = reference_policy_legs(model, v1, v2, args, dev)
-        if (not args.no_extra_legs and args.precision == "bf16" and not args.graph and args.encoder == "croco" and args.img == 512
-                and args.attention == "bf16"):
+        if (args.full and not args.no_extra_legs and args.precision == "bf16" and not args.graph and args.encoder == "croco"
+                and args.img == 512 and args.attention == "bf16"):
             line["fwd_224"] = fwd_224_leg(args, dev)
             line["batch_sweep"] = batch_sweep(model, [1, 2, 4, 8], args, dev)      # the reference harness's own sizes (profile_dust3r.py:12-46)
             line["other_configs"] = other_configs_leg(args, dev)
             line["train_step"] = train_step_leg(args, dev, pairs=args.train_pairs, steps=args.train_steps)
         if args.sweep and "batch_sweep" not in line:
             line["batch_sweep"] = batch_sweep(model, [int(x) for x in args.sweep.split(",")], args, dev)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(model, args.img, args.img, args.head, args.cpu_baseline_max_s)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -24,7 +24,7 @@ def _bench(args, extra_env=None):
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["fwd", "train"])
 def test_bench_two_ranks_from_plain_python(gpu, mode):
-    line = _bench(["--gpus", "2", "--mode", mode, "--pairs", "1", "--img", "224", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+    line = _bench(["--gpus", "2", "--mode", mode, "--pairs", "1", "--img", "224", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
                    "--no-reference-policy", "--no-roofline", "--train-pairs", "1", "--train-steps", "1"], {"UNICEPTION_AMD_BENCH_SHARE_GPU": "1"})
     assert line["n_gpus"] == 2 and line["config"]["global_pairs_per_step"] == 2 and line["scaling"] == "weak"
     assert line["value"] > 0 and "shared_gpu_dry_run" in line["config"]
@@ -42,3 +42,17 @@ def test_bench_batch_sweep_line(gpu):
     line = _bench(["--img", "224", "--sweep", "1,2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-reference-policy", "--no-roofline"])
     sw = line["batch_sweep"]
     assert [e["pairs"] for e in sw] == [1, 2] and all(e["ms_per_batch"] > 0 and e["pairs_per_s"] > 0 for e in sw)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(gpu, tmp_path):
+    """A plain run: set up, warm up, the --steps timed steps, the outputs of the last one, ONE line — none of the --full legs."""
+    import numpy as np
+    line = _bench(["--img", "224", "--pairs", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert abs(line["value"] - 2 / (line["ms_per_step"] / 1e3)) <= 0.01 * line["value"]
+    for k in ("roofline", "reference_policy", "fwd_224", "batch_sweep", "other_configs", "train_step", "cpu_baseline"):
+        assert k not in line, k
+    for name, c in (("view1_pts3d", 3), ("view1_conf", 1), ("view2_pts3d_in_other_view", 3), ("view2_conf", 1)):
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (2, 224, 224, c) and np.isfinite(a).all(), name

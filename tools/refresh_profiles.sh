@@ -12,7 +12,7 @@ out=gpurun_out/prof_$tag
 bash tools/profile_round.sh $tag pmc > /dev/null 2>&1
 cp $out/${tag}_pmc_traffic.json profiles/r6_pmc_traffic.json
 rm -rf $out/trace $out/pmc_*
-python bench.py --steps 20 --warmup 3 > $out/${tag}_bench_forward_pairs128.json 2> $out/bench_forward.err
+python bench.py --steps 20 --warmup 3 --full > $out/${tag}_bench_forward_pairs128.json 2> $out/bench_forward.err
 cat $out/${tag}_bench_forward_pairs128.json
 # (the trace runs single-stream: per-kernel durations are only defined without overlap; the bench line below is the default two-stream step)
 cmd="python $root/bench.py --mode train --steps 2 --warmup 2 --no-cpu-baseline --no-roofline --single-stream"
@@ -20,7 +20,7 @@ cmd="python $root/bench.py --mode train --steps 2 --warmup 2 --no-cpu-baseline -
 db=$(ls $out/train/*/*_results.db $out/train/*_results.db 2>/dev/null | head -1)
 python tools/rocpd_stats.py $db > $out/${tag}_train_step_kernel_stats_dpt_pairs64.md
 rm -rf $out/train
-python bench.py --mode train --steps 10 --warmup 3 > $out/${tag}_bench_train_dpt_pairs64.json 2> $out/bench_train.err
+python bench.py --mode train --steps 10 --warmup 3 --full > $out/${tag}_bench_train_dpt_pairs64.json 2> $out/bench_train.err
 cat $out/${tag}_bench_train_dpt_pairs64.json
 # SQ counters of the bf16 attention forward (VERDICT r3 next #9 asks for the evidence): tools/pmc_attn.sh, eight-wave workgroups
 bash tools/pmc_attn.sh "8" > $out/${tag}_probe_attention_sq_counters.txt 2>&1
