@@ -1,5 +1,5 @@
 """Per-kernel register / LDS / scratch usage of one csrc file (hipcc -Rpass-analysis=kernel-resource-usage), as a table.
-usage: python tools/kres.py gemm_glds.hip [name-filter]"""
+usage: python tools/kres.py gemm_glds_dense_bf16.hip [name-filter]"""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "uniception_amd", "csrc", sys.argv[1])

@@ -1,6 +1,6 @@
 """Where does a kernel spill?  Lists scratch loads/stores of one kernel of a csrc file by position, with landmark instructions
 (MFMA loop, sin/cos = RoPE epilogue, row_ror = LN statistics, v_exp = GELU, nt loads = fp32 residual epilogue).
-usage: python tools/spills.py gemm_glds.hip '<mangled substring>'"""
+usage: python tools/spills.py gemm_glds_dense_bf16.hip '<mangled substring>'"""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "uniception_amd", "csrc", sys.argv[1])

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 
 #include "../../include/uc_hip.h"
+#include "gemm_plan.h"   // (ceil_div64)
 
 // ---------------------------------------------------------------------------------------
 // error plumbing (thread-local text, negative status codes)
@@ -93,8 +94,6 @@ typedef float float4_t __attribute__((ext_vector_type(4)));
 typedef float float16_t __attribute__((ext_vector_type(16)));
 typedef short short8_t __attribute__((ext_vector_type(8)));
 typedef short short4_t __attribute__((ext_vector_type(4)));
-
-static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -438,9 +438,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
 // partial sums followed by 128 flag words.  UNCACHED device memory: the partners of a split tile may run on different XCDs (separate,
 // non-coherent L2s).  Round 3 kept a lazily grown, never-freed pool of such buffers in here, keyed by (device, stream, capture id):
 // allocation and a synchronous memset inside a launch path, state a C caller could neither size nor release — removed.
-static constexpr int64_t UC_FUSE_TILES = 128;
-static constexpr int64_t UC_FUSE_WS_FLOATS = UC_FUSE_TILES * 128 * 128;
 extern "C" int64_t uc_gemm_fuse_ws_bytes(void) { return UC_FUSE_WS_FLOATS * (int64_t)sizeof(float) + UC_FUSE_TILES * (int64_t)sizeof(unsigned); }
+
+static_assert(BM == UC_REG_TILE && BN == UC_REG_TILE && FBM == UC_F32_TILE && FBN == UC_F32_TILE, "gemm_plan.h's tiles of the gemm.hip kernels");
 
 extern "C" int uc_gemm(const uc_gemm_desc* d, uc_stream_t stream) {
     UC_REQUIRE(d, "uc_gemm: null descriptor");
@@ -504,11 +504,6 @@ extern "C" int uc_gemm(const uc_gemm_desc* d, uc_stream_t stream) {
             UC_REQUIRE(d->rope_cols <= d->vt_col0, "uc_gemm: rope columns overlap vt columns");
             UC_REQUIRE((uintptr_t)d->vt_out % 8 == 0, "uc_gemm: vt_out must be 8-byte aligned");
         }
-        // dense operands with K % 64 == 0 take the direct-to-LDS kernel (gemm_glds.hip)
-        // (initial value from UC_GEMM_VARIANT, switchable at run time through uc_tuning_set: tests and micro-benchmarks run every
-        // tile variant inside one process)
-        const UcKnobs& knobs = uc_knobs();
-        const int forced_variant = g_uc_gemm_variant.load(std::memory_order_relaxed);   // -3: automatic, -1: register-staged kernel, 0..3, 6: glds tile variants
         if (d->split_k > 1) {
             UC_REQUIRE(d->a_mode == UC_A_DENSE && d->K % 64 == 0 && !d->relu_a, "uc_gemm: split_k needs a dense operand with K %% 64 == 0");
             UC_REQUIRE(d->out_dtype == UC_F32 && !d->bias && d->act == UC_ACT_NONE && !d->residual && d->rope_cols <= 0 && d->vt_col0 < 0 && !d->preact_out,
@@ -523,10 +518,7 @@ extern "C" int uc_gemm(const uc_gemm_desc* d, uc_stream_t stream) {
                            ((d->a_mode == UC_A_DENSE && d->K % 64 == 0 && !d->relu_a) || (d->a_mode == UC_A_CONV3X3 && d->conv_Cin % 32 == 0)),
                        "uc_gemm: dact_u needs the bf16 direct-to-LDS kernels, bf16 output and a plain epilogue");
         }
-        // (fp16 operands have no register-staged fallback kernel: K % 32 == 0 — the DPT's 96-channel ConvTranspose GEMM — takes the
-        // 32-deep tile of the direct-to-LDS kernel instead)
-        const bool dense32 = f16 && d->a_mode == UC_A_DENSE && d->K % 64 != 0 && d->K % 32 == 0 && !d->relu_a;
-        const bool glds_dense = d->a_mode == UC_A_DENSE && (d->K % 64 == 0 || dense32) && !d->relu_a;
+        const bool glds_dense = glds_dense_ok(*d);
         if (d->ln_stats || d->ln_colsum) {
             UC_REQUIRE(d->ln_stats && d->ln_colsum, "uc_gemm: the folded LayerNorm needs both ln_stats and ln_colsum");
             UC_REQUIRE(d->ln_nblk == 0 || (d->ln_nblk > 0 && d->K == (int64_t)64 * d->ln_nblk && d->ln_eps > 0.f),
@@ -558,164 +550,6 @@ extern "C" int uc_gemm(const uc_gemm_desc* d, uc_stream_t stream) {
             UC_REQUIRE((uintptr_t)d->tail_out % 16 == 0 && (uintptr_t)d->tail_w % 4 == 0 && (!d->tail_b || (uintptr_t)d->tail_b % 4 == 0),
                        "uc_gemm: tail_out must be 16-byte aligned");
         }
-        // the conv DMA addresses a tile's input window (the images its 256 output rows touch) with 32-bit byte offsets
-        const int64_t conv_window_bytes = d->a_mode == UC_A_CONV3X3
-            ? (256 / std::max<int64_t>(1, (int64_t)d->conv_Ho * d->conv_Wo) + 2) * (int64_t)d->conv_H * d->conv_W * d->conv_Cin * 2 : 0;
-        // Cin % 64 == 0: any tile; Cin % 32 == 0 (the DPT's 96-channel reassemble stage): the 32-deep K-step tile only
-        const bool glds_conv = d->a_mode == UC_A_CONV3X3 && d->conv_Cin % 32 == 0 &&
-                               (int64_t)d->conv_B * d->conv_H * d->conv_W < (int64_t)1 << 30 && conv_window_bytes < (int64_t)1 << 31 &&
-                               (int64_t)256 * d->K * 2 < (int64_t)1 << 31;
-        if ((glds_dense || glds_conv) && forced_variant != -1) {
-            GldsParams g;
-            g.A = (const bf16_t*)d->A; g.lda = d->lda; g.W = (const bf16_t*)d->W; g.M = d->M; g.N = d->N; g.K = d->K;
-            g.bias = d->bias; g.act = d->act; g.residual = d->residual; g.residual2 = d->residual2; g.res_dtype = d->res_dtype;
-            g.ldr = d->ldr; g.rope_cols = d->rope_cols; g.rope_pos = d->rope_pos; g.rope_table = (const float2*)d->rope_table;
-            g.rope_npos = d->rope_npos;
-            g.rope_turn0 = d->rope_cols > 0 ? (float)((double)d->rope_f0 / 6.283185307179586476925) : 0.f;
-            g.rope_ratio = d->rope_cols > 0 ? (float)pow((double)d->rope_base, -1.0 / 16.0) : 1.f;
-            g.rope_l2ratio = d->rope_cols > 0 ? (float)(-log2((double)d->rope_base) / 16.0) : 0.f;
-            g.vt_col0 = d->vt_col0; g.vt_out = (bf16_t*)d->vt_out; g.vt_ntok = d->vt_ntok;
-            g.vt_npad = d->vt_npad; g.C = d->C; g.out_dtype = d->out_dtype; g.ldc = d->ldc; g.tiles_m = g.tiles_n = 0;
-            const bool c_ok = ((uintptr_t)d->C % 16 == 0) && (d->ldc % 8 == 0);
-            const bool b_ok = !d->bias || ((uintptr_t)d->bias % 16 == 0);
-            const bool r_ok = !d->residual || (((uintptr_t)d->residual % 16 == 0) && (d->ldr % 4 == 0) &&
-                                               (!d->residual2 || (uintptr_t)d->residual2 % 16 == 0));
-            const bool x_ok = (!d->preact_out || (uintptr_t)d->preact_out % 16 == 0) && (!d->dact_u || (uintptr_t)d->dact_u % 8 == 0);
-            g.vec_ok = (c_ok && b_ok && r_ok && x_ok) ? 1 : 0;
-            g.preact = d->preact_out; g.split_k = d->split_k > 1 ? d->split_k : 1;
-            g.ln_stats = d->ln_nblk > 0 ? nullptr : (const float2*)d->ln_stats; g.ln_colsum = d->ln_colsum;
-            g.ln_partial = d->ln_nblk > 0 ? (const float2*)d->ln_stats : nullptr; g.ln_nblk = d->ln_nblk; g.ln_eps = d->ln_eps;
-            g.twin = (bf16_t*)d->twin_out; g.ldt = d->ldt; g.stats_out = (float2*)d->stats_out;
-            g.tail_w = d->tail_w; g.tail_b = d->tail_b; g.tail_out = d->tail_out;
-            if (d->tail_out) g.vec_ok = 0;     // never one of the single-family kernels
-            g.dact_u = (const bf16_t*)d->dact_u; g.dact_act = d->dact_act;
-            g.group_m = knobs.gemm_group_m;
-#ifdef UC_DIAG
-            g.dbg = knobs.gemm_dbg;     // (diag build only; the release build has no code behind these bits)
-#else
-            g.dbg = 0;
-#endif
-            g.f16 = f16 ? 1 : 0;
-            g.sat_flag = f16 ? d->sat_flag : nullptr;
-            g.a_mode = d->a_mode; g.relu_a = d->relu_a; g.cH = d->conv_H; g.cW = d->conv_W; g.cCin = d->conv_Cin;
-            g.cStride = d->conv_stride; g.cHo = d->conv_Ho; g.cWo = d->conv_Wo;
-            if (d->a_mode == UC_A_CONV3X3) {
-                g.dWo = uc_make_fastdiv((unsigned)d->conv_Wo); g.dHo = uc_make_fastdiv((unsigned)d->conv_Ho);
-                g.dHWo = uc_make_fastdiv((unsigned)d->conv_Ho * (unsigned)d->conv_Wo); g.dCin = uc_make_fastdiv((unsigned)d->conv_Cin);
-            }
-            int variant = forced_variant;
-            if ((d->a_mode == UC_A_CONV3X3 && d->conv_Cin % 64 != 0) || dense32) variant = 3;
-            else if (variant < 0) {
-                // tile choice: the 256x256 tile (16 waves) has the best steady state (least LDS fill per flop) but needs
-                // enough tiles to cover the 256 CUs; smaller problems fall back to 256x128 / 128x128 tiles.
-                const int64_t t256 = ceil_div64(d->M, 256) * ceil_div64(d->N, 256);
-                const int64_t t256x128 = ceil_div64(d->M, 256) * ceil_div64(d->N, 128);
-                const int64_t sk = d->split_k > 1 ? d->split_k : 1;
-                variant = t256 * sk >= 192 ? 2 : (t256x128 * sk >= 160 ? 1 : 0);
-                if (d->a_mode == UC_A_DENSE) {
-                    // Dense launches of a few rounds of tiles (the batch sweep's 2 - 16 pairs): what matters is how many ROUNDS of
-                    // workgroups a tile size needs on the 256 CUs, times what a round of that tile costs — measured per round at
-                    // K = 768 / 1024 (tools/scratch/bench_midsize_variants.py): 128x128 ~13 / 19 us, 256x128 ~16 / 23 us, 256x256 ~22 / 29 us,
-                    // i.e. 1 : 1.25 : 1.7.  The thresholds above missed the quantisation: 144 tiles of 256x256 beat 288 of 256x128 by
-                    // 38 % (decoder qkv at 4 pairs), 144 of 256x128 beat 288 of 128x128 by 47 % (at 2 pairs).
-                    const int64_t cus = uc_num_cus();
-                    const int64_t t128 = ceil_div64(d->M, 128) * ceil_div64(d->N, 128);
-                    const double c0 = (double)ceil_div64(t128 * sk, cus), c1 = 1.25 * (double)ceil_div64(t256x128 * sk, cus),
-                                 c2 = 1.7 * (double)ceil_div64(t256 * sk, cus);
-                    variant = (c2 <= c1 && c2 <= c0) ? 2 : (c1 <= c0 ? 1 : 0);
-                }
-                // a 256-wide tile whose last column block is at most half full wastes a 128-column slab of MFMA work per row
-                // panel (N = 128: half of every tile): take the 256x128 tile there
-                const int64_t waste256 = ceil_div64(d->N, 256) * 256 - d->N, waste128 = ceil_div64(d->N, 128) * 128 - d->N;
-                if (variant == 2 && waste256 - waste128 >= 128 && t256x128 * sk >= 160) variant = 1;
-                // 256x128 tiles with enough workgroups for two per CU: the 32-deep K-step form (72 KiB of LDS, two co-resident
-                // 8-wave workgroups) keeps 16 waves on a CU where the 64-deep form (96 KiB) leaves 8
-                if (variant == 1 && t256x128 * sk >= 512 && knobs.gemm_coresident) variant = 3;
-            }
-            if (d->tail_out && (variant == 2 || variant == 6)) variant = 1;    // the tail needs a tile that spans all 128 columns with two wave columns
-            // Small-M path: a launch (dense or 3x3 conv) whose 128x128 tiles cover at most half the CUs is a chain of K / 64 dependent steps of
-            // ~0.7 us on each of them (neither a smaller tile nor a deeper ring shortens it: measured) — split K in two across twice
-            // the workgroups, hand-over inside the kernel (fuse_split2).  UC_GEMM_SMALLM / tuning knob small_m_split = smallest K it is taken for
-            // (0: never — the sum over K is then one chain whatever the batch size, and a pair's bits do not depend on its batch).
-            g.fuse_split2 = 0; g.fs_ws = nullptr; g.fs_flags = nullptr;
-            const int small_m_k = g_uc_small_m_split.load(std::memory_order_relaxed);
-            if (forced_variant < 0 && variant == 0 && d->split_k <= 1 && !d->tail_out && small_m_k > 0 &&
-                d->K >= small_m_k && d->K % 128 == 0 &&
-                2 * ceil_div64(d->M, 128) * ceil_div64(d->N, 128) <= uc_num_cus() &&
-                ceil_div64(d->M, 128) * ceil_div64(d->N, 128) <= UC_FUSE_TILES && d->fuse_ws) {
-                UC_REQUIRE((uintptr_t)d->fuse_ws % 256 == 0, "uc_gemm: fuse_ws must be 256-byte aligned");
-                g.fuse_split2 = 1; g.fs_ws = (float*)d->fuse_ws; g.fs_flags = (unsigned*)((float*)d->fuse_ws + UC_FUSE_WS_FLOATS);
-            }
-            { const int nt = knobs.gemm_nt;
-              const int64_t out_bytes = d->M * d->N * (d->out_dtype == UC_F32 ? 4 : 2);
-              g.nt_out = out_bytes > ((int64_t)128 << 20) ? (nt >= 0 ? nt : 7) : 0; }   // bit 0: fp32 residual stream, 1: bf16 outputs, 2: bf16 RoPE (q, k) tiles
-            g.stagger = g_uc_gemm_stagger.load(std::memory_order_relaxed);   // -1: the launcher's default policy
-            g.trace = nullptr;
-#ifdef UC_DIAG
-            const int trace_on = knobs.gemm_trace;
-            static unsigned long long* trace_buf = nullptr;
-            const size_t trace_cap = 1 << 16;
-            if (trace_on) {
-                if (!trace_buf) (void)hipMalloc((void**)&trace_buf, trace_cap * 6 * sizeof(unsigned long long));
-                g.trace = trace_buf;
-            }
-#endif
-            uc_launch_gemm_glds(g, variant, st, forced_variant < 0);
-            UC_CHECK_LAUNCH("uc_gemm(glds)");
-#ifdef UC_DIAG
-            if (trace_on) {   // diagnostics only (diag build): per-CU timeline statistics of this launch to stderr
-                (void)hipStreamSynchronize(st);
-                const int bm = variant >= 1 ? 256 : 128, bn = (variant == 2 || variant == 6) ? 256 : 128;
-                size_t nwg = (size_t)ceil_div64(d->M, bm) * ceil_div64(d->N, bn) * (size_t)g.split_k;
-                if (nwg > trace_cap) nwg = trace_cap;
-                unsigned long long* h = (unsigned long long*)malloc(nwg * 6 * sizeof(unsigned long long));
-                (void)hipMemcpy(h, trace_buf, nwg * 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-                double pro = 0, loop = 0, epi = 0; unsigned long long tmin = ~0ull, tmax = 0;
-                for (size_t i = 0; i < nwg; ++i) {
-                    pro += (double)(h[i*6+1] - h[i*6+0]); loop += (double)(h[i*6+2] - h[i*6+1]); epi += (double)(h[i*6+3] - h[i*6+2]);
-                    if (h[i*6+0] < tmin) tmin = h[i*6+0];
-                    if (h[i*6+3] > tmax) tmax = h[i*6+3];
-                }
-                // per-CU gaps: sort WGs by (xcc, hw id cu/se bits) then start time
-                struct Rec { unsigned long long key, s, e; };
-                Rec* r = (Rec*)malloc(nwg * sizeof(Rec));
-                for (size_t i = 0; i < nwg; ++i) {
-                    const unsigned hw = (unsigned)h[i*6+4];
-                    const unsigned cu = (hw >> 8) & 0xf, sh = (hw >> 12) & 1, se = (hw >> 13) & 7;
-                    r[i].key = ((h[i*6+5] & 0xf) << 12) | (se << 8) | (sh << 4) | cu; r[i].s = h[i*6+0]; r[i].e = h[i*6+3];
-                }
-                qsort(r, nwg, sizeof(Rec), [](const void* a, const void* b) -> int {
-                    const Rec* x = (const Rec*)a; const Rec* y = (const Rec*)b;
-                    if (x->key != y->key) return x->key < y->key ? -1 : 1;
-                    return x->s < y->s ? -1 : (x->s > y->s ? 1 : 0); });
-                double gap = 0; size_t ngap = 0, ncu = 0; double overlap = 0;
-                for (size_t i = 0; i < nwg; ++i) {
-                    if (i == 0 || r[i].key != r[i-1].key) { ++ncu; continue; }
-                    const double gp = (double)r[i].s - (double)r[i-1].e;
-                    if (gp >= 0) { gap += gp; ++ngap; } else overlap += 1;
-                }
-                fprintf(stderr, "[uc_gemm trace] M=%lld N=%lld K=%lld variant=%d wgs=%zu cus=%zu span=%.1f us | per WG: prologue %.2f us, loop %.2f us, epilogue %.2f us | same-CU gap %.2f us (n=%zu, overlapping pairs %.0f)\n",
-                        (long long)d->M, (long long)d->N, (long long)d->K, variant, nwg, ncu, (tmax - tmin) * 0.01,
-                        pro / nwg * 0.01, loop / nwg * 0.01, epi / nwg * 0.01, ngap ? gap / ngap * 0.01 : 0.0, ngap, overlap);
-                free(h); free(r);
-            }
-#endif
-            return UC_OK;
-        }
-        UC_REQUIRE(!d->ln_stats && !d->twin_out && !d->stats_out, "uc_gemm: the LayerNorm fusion options need the direct-to-LDS kernel (forced off?)");
-        UC_REQUIRE(!d->tail_out, "uc_gemm: the fused tail needs the direct-to-LDS kernel (dense K %% 64 == 0 / conv Cin %% 32 == 0)");
-        p.tiles_m = (int)ceil_div64(d->M, BM);
-        p.tiles_n = (int)ceil_div64(d->N, BN);
-        const unsigned grid = (unsigned)p.tiles_m * (unsigned)p.tiles_n;
-        const size_t smem = 4 * TILE_BYTES;
-        if (f16 && d->a_mode == UC_A_DENSE)
-            hipLaunchKernelGGL((gemm_bf16_kernel<UC_A_DENSE, true>), dim3(grid), dim3(GEMM_THREADS), smem, st, p);
-        else if (f16)
-            hipLaunchKernelGGL((gemm_bf16_kernel<UC_A_CONV3X3, true>), dim3(grid), dim3(GEMM_THREADS), smem, st, p);
-        else if (d->a_mode == UC_A_DENSE)
-            hipLaunchKernelGGL((gemm_bf16_kernel<UC_A_DENSE>), dim3(grid), dim3(GEMM_THREADS), smem, st, p);
-        else
-            hipLaunchKernelGGL((gemm_bf16_kernel<UC_A_CONV3X3>), dim3(grid), dim3(GEMM_THREADS), smem, st, p);
     } else if (d->compute_dtype == UC_F32) {
         UC_REQUIRE(!d->ln_stats && !d->twin_out && !d->stats_out && !d->tail_out, "uc_gemm(f32): the LayerNorm fusion options and the fused tail are bf16-path only");
         if (d->split_k > 1 || d->dact_u) {
@@ -731,17 +565,142 @@ extern "C" int uc_gemm(const uc_gemm_desc* d, uc_stream_t stream) {
             uc_set_error("uc_gemm(f32): fused RoPE epilogue is only implemented for the bf16 MFMA path; call uc_rope2d");
             return UC_ERR_UNSUPPORTED;
         }
-        p.tiles_m = (int)ceil_div64(d->M, FBM);
-        p.tiles_n = (int)ceil_div64(d->N, FBN);
-        const unsigned grid = (unsigned)p.tiles_m * (unsigned)p.tiles_n;
-        if (d->a_mode == UC_A_DENSE)
-            hipLaunchKernelGGL((gemm_f32_kernel<UC_A_DENSE>), dim3(grid), dim3(256), 0, st, p);
-        else
-            hipLaunchKernelGGL((gemm_f32_kernel<UC_A_CONV3X3>), dim3(grid), dim3(256), 0, st, p);
     } else {
         uc_set_error("uc_gemm: unsupported compute dtype %d", d->compute_dtype);
         return UC_ERR_BAD_ARG;
     }
-    UC_CHECK_LAUNCH("uc_gemm");
+
+    // every knob this launch depends on, read once (tuning knobs switched at run time take effect between launches)
+    const UcKnobs& knobs = uc_knobs();
+    GemmKnobs k;
+    k.gemm_variant = g_uc_gemm_variant.load(std::memory_order_relaxed);
+    k.small_m_split = g_uc_small_m_split.load(std::memory_order_relaxed);
+    k.gemm_stagger = g_uc_gemm_stagger.load(std::memory_order_relaxed);
+    k.conv_rows = g_uc_conv_rows.load(std::memory_order_relaxed);
+    k.conv_rows_flat = g_uc_conv_rows_flat.load(std::memory_order_relaxed);
+    k.gemm_group_m = knobs.gemm_group_m;
+    k.gemm_4wave = knobs.gemm_4wave;
+    k.cus = uc_num_cus();
+#ifdef UC_DIAG
+    k.dbg = knobs.gemm_dbg;     // (diag build only; the release build has no code behind these bits)
+#else
+    k.dbg = 0;
+#endif
+    const GemmPlan plan = uc_gemm_plan(*d, k);
+
+    if (plan.kernel == UC_GK_F32 || plan.kernel == UC_GK_REG) {
+        if (plan.kernel == UC_GK_REG) {
+            UC_REQUIRE(!d->ln_stats && !d->twin_out && !d->stats_out, "uc_gemm: the LayerNorm fusion options need the direct-to-LDS kernel (forced off?)");
+            UC_REQUIRE(!d->tail_out, "uc_gemm: the fused tail needs the direct-to-LDS kernel (dense K %% 64 == 0 / conv Cin %% 32 == 0)");
+        }
+        p.tiles_m = (int)plan.tiles_m;
+        p.tiles_n = (int)plan.tiles_n;
+        const unsigned grid = (unsigned)p.tiles_m * (unsigned)p.tiles_n;
+        const size_t smem = 4 * TILE_BYTES;
+        if (plan.kernel == UC_GK_F32) {
+            if (d->a_mode == UC_A_DENSE)
+                hipLaunchKernelGGL((gemm_f32_kernel<UC_A_DENSE>), dim3(grid), dim3(256), 0, st, p);
+            else
+                hipLaunchKernelGGL((gemm_f32_kernel<UC_A_CONV3X3>), dim3(grid), dim3(256), 0, st, p);
+        } else if (f16 && d->a_mode == UC_A_DENSE)
+            hipLaunchKernelGGL((gemm_bf16_kernel<UC_A_DENSE, true>), dim3(grid), dim3(GEMM_THREADS), smem, st, p);
+        else if (f16)
+            hipLaunchKernelGGL((gemm_bf16_kernel<UC_A_CONV3X3, true>), dim3(grid), dim3(GEMM_THREADS), smem, st, p);
+        else if (d->a_mode == UC_A_DENSE)
+            hipLaunchKernelGGL((gemm_bf16_kernel<UC_A_DENSE>), dim3(grid), dim3(GEMM_THREADS), smem, st, p);
+        else
+            hipLaunchKernelGGL((gemm_bf16_kernel<UC_A_CONV3X3>), dim3(grid), dim3(GEMM_THREADS), smem, st, p);
+        UC_CHECK_LAUNCH("uc_gemm");
+        return UC_OK;
+    }
+
+    // direct-to-LDS kernels
+    if (plan.fuse_split2) UC_REQUIRE((uintptr_t)d->fuse_ws % 256 == 0, "uc_gemm: fuse_ws must be 256-byte aligned");
+    GldsParams g;
+    g.A = (const bf16_t*)d->A; g.lda = d->lda; g.W = (const bf16_t*)d->W; g.M = d->M; g.N = d->N; g.K = d->K;
+    g.bias = d->bias; g.act = d->act; g.residual = d->residual; g.residual2 = d->residual2; g.res_dtype = d->res_dtype;
+    g.ldr = d->ldr; g.rope_cols = d->rope_cols; g.rope_pos = d->rope_pos; g.rope_table = (const float2*)d->rope_table;
+    g.rope_npos = d->rope_npos;
+    g.rope_turn0 = d->rope_cols > 0 ? (float)((double)d->rope_f0 / 6.283185307179586476925) : 0.f;
+    g.rope_ratio = d->rope_cols > 0 ? (float)pow((double)d->rope_base, -1.0 / 16.0) : 1.f;
+    g.rope_l2ratio = d->rope_cols > 0 ? (float)(-log2((double)d->rope_base) / 16.0) : 0.f;
+    g.vt_col0 = d->vt_col0; g.vt_out = (bf16_t*)d->vt_out; g.vt_ntok = d->vt_ntok;
+    g.vt_npad = d->vt_npad; g.C = d->C; g.out_dtype = d->out_dtype; g.ldc = d->ldc;
+    g.vec_ok = plan.vec_ok;
+    g.preact = d->preact_out; g.split_k = d->split_k > 1 ? d->split_k : 1;
+    g.ln_stats = d->ln_nblk > 0 ? nullptr : (const float2*)d->ln_stats; g.ln_colsum = d->ln_colsum;
+    g.ln_partial = d->ln_nblk > 0 ? (const float2*)d->ln_stats : nullptr; g.ln_nblk = d->ln_nblk; g.ln_eps = d->ln_eps;
+    g.twin = (bf16_t*)d->twin_out; g.ldt = d->ldt; g.stats_out = (float2*)d->stats_out;
+    g.tail_w = d->tail_w; g.tail_b = d->tail_b; g.tail_out = d->tail_out;
+    g.dact_u = (const bf16_t*)d->dact_u; g.dact_act = d->dact_act;
+    g.fuse_split2 = plan.fuse_split2;
+    g.fs_ws = plan.fuse_split2 ? (float*)d->fuse_ws : nullptr;
+    g.fs_flags = plan.fuse_split2 ? (unsigned*)((float*)d->fuse_ws + UC_FUSE_WS_FLOATS) : nullptr;
+    g.tiles_m = (int)plan.tiles_m; g.tiles_n = (int)plan.tiles_n;    // (the launcher derives the tile-order divisions)
+    g.group_m = k.gemm_group_m;
+    g.dbg = k.dbg;
+    g.stagger = plan.stagger; g.side_lds = plan.side_lds; g.nt_out = plan.nt_out;
+    g.f16 = plan.f16;
+    g.sat_flag = f16 ? d->sat_flag : nullptr;
+    g.a_mode = d->a_mode; g.relu_a = d->relu_a; g.cH = d->conv_H; g.cW = d->conv_W; g.cCin = d->conv_Cin;
+    g.cStride = d->conv_stride; g.cHo = d->conv_Ho; g.cWo = d->conv_Wo;
+    if (d->a_mode == UC_A_CONV3X3) {
+        g.dWo = uc_make_fastdiv((unsigned)d->conv_Wo); g.dHo = uc_make_fastdiv((unsigned)d->conv_Ho);
+        g.dHWo = uc_make_fastdiv((unsigned)d->conv_Ho * (unsigned)d->conv_Wo); g.dCin = uc_make_fastdiv((unsigned)d->conv_Cin);
+    }
+    g.trace = nullptr;
+#ifdef UC_DIAG
+    const int trace_on = knobs.gemm_trace;
+    static unsigned long long* trace_buf = nullptr;
+    const size_t trace_cap = 1 << 16;
+    if (trace_on) {
+        if (!trace_buf) (void)hipMalloc((void**)&trace_buf, trace_cap * 6 * sizeof(unsigned long long));
+        g.trace = trace_buf;
+    }
+#endif
+    if (d->a_mode == UC_A_CONV3X3) (f16 ? glds_launch_conv_f16 : glds_launch_conv)(g, plan, st);
+    else if (f16) glds_launch_dense_all_f16(g, plan, st);
+    else if (plan.epi == GLDS_EPI_BF16) glds_launch_dense_bf16(g, plan, st);
+    else if (plan.epi == GLDS_EPI_F32) glds_launch_dense_f32(g, plan, st);
+    else if (plan.epi == GLDS_EPI_BS) glds_launch_dense_bs(g, plan, st);
+    else glds_launch_dense_all(g, plan, st);
+    UC_CHECK_LAUNCH("uc_gemm(glds)");
+#ifdef UC_DIAG
+    if (trace_on) {   // diagnostics only (diag build): per-CU timeline statistics of this launch to stderr
+        (void)hipStreamSynchronize(st);
+        size_t nwg = (size_t)plan.tiles_m * plan.tiles_n * (size_t)plan.slices;
+        if (nwg > trace_cap) nwg = trace_cap;
+        unsigned long long* h = (unsigned long long*)malloc(nwg * 6 * sizeof(unsigned long long));
+        (void)hipMemcpy(h, trace_buf, nwg * 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        double pro = 0, loop = 0, epi = 0; unsigned long long tmin = ~0ull, tmax = 0;
+        for (size_t i = 0; i < nwg; ++i) {
+            pro += (double)(h[i*6+1] - h[i*6+0]); loop += (double)(h[i*6+2] - h[i*6+1]); epi += (double)(h[i*6+3] - h[i*6+2]);
+            if (h[i*6+0] < tmin) tmin = h[i*6+0];
+            if (h[i*6+3] > tmax) tmax = h[i*6+3];
+        }
+        // per-CU gaps: sort WGs by (xcc, hw id cu/se bits) then start time
+        struct Rec { unsigned long long key, s, e; };
+        Rec* r = (Rec*)malloc(nwg * sizeof(Rec));
+        for (size_t i = 0; i < nwg; ++i) {
+            const unsigned hw = (unsigned)h[i*6+4];
+            const unsigned cu = (hw >> 8) & 0xf, sh = (hw >> 12) & 1, se = (hw >> 13) & 7;
+            r[i].key = ((h[i*6+5] & 0xf) << 12) | (se << 8) | (sh << 4) | cu; r[i].s = h[i*6+0]; r[i].e = h[i*6+3];
+        }
+        qsort(r, nwg, sizeof(Rec), [](const void* a, const void* b) -> int {
+            const Rec* x = (const Rec*)a; const Rec* y = (const Rec*)b;
+            if (x->key != y->key) return x->key < y->key ? -1 : 1;
+            return x->s < y->s ? -1 : (x->s > y->s ? 1 : 0); });
+        double gap = 0; size_t ngap = 0, ncu = 0; double overlap = 0;
+        for (size_t i = 0; i < nwg; ++i) {
+            if (i == 0 || r[i].key != r[i-1].key) { ++ncu; continue; }
+            const double gp = (double)r[i].s - (double)r[i-1].e;
+            if (gp >= 0) { gap += gp; ++ngap; } else overlap += 1;
+        }
+        fprintf(stderr, "[uc_gemm trace] M=%lld N=%lld K=%lld kernel=%d wgs=%zu cus=%zu span=%.1f us | per WG: prologue %.2f us, loop %.2f us, epilogue %.2f us | same-CU gap %.2f us (n=%zu, overlapping pairs %.0f)\n",
+                (long long)d->M, (long long)d->N, (long long)d->K, (int)plan.kernel, nwg, ncu, (tmax - tmin) * 0.01,
+                pro / nwg * 0.01, loop / nwg * 0.01, epi / nwg * 0.01, ngap ? gap / ngap * 0.01 : 0.0, ngap, overlap);
+        free(h); free(r);
+    }
+#endif
     return UC_OK;
 }

@@ -1,6 +1,7 @@
-// Parameters / launcher of the direct-to-LDS dense bf16 GEMM (gemm_glds.hip), shared with the uc_gemm dispatcher.
+// Parameters and family launchers of the direct-to-LDS bf16 GEMM kernels (gemm_glds_kernel.h), shared with the uc_gemm dispatcher.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 struct GldsParams {
     const bf16_t* A;
@@ -60,7 +61,7 @@ struct GldsParams {
     // implicit-GEMM 3x3 convolution over an NHWC image (a_mode == UC_A_CONV3X3): K = 9*Cin, Cin % 64 == 0
     int dbg;      // diagnostics only (UC_GEMM_DBG): 1 skip the in-loop DMA, 2 skip the in-loop barrier, 4 no epilogue, 8 one K-step, 16 generic epilogue only, 32 (eight-wave kernel) no wait for the DMA, 64 (conv) A tiles staged for tap 0 only, 128 / 256 (fp32 residual epilogue) no residual read / no twin write
     int stagger;  // experiment: 100-MHz ticks of start delay per phase group for the first round of workgroups (0 = off)
-    int side_lds; // (eight-wave kernel, BF16 family; set by its launcher) the tile's row statistics / column sums / bias / RoPE positions are
+    int side_lds; // (eight-wave kernel, BF16 family) the tile's row statistics / column sums / bias / RoPE positions are
                   // DMA-staged into 8 KiB of LDS behind the ring at kernel start: the epilogue's first loads are LDS reads, not an exposed L2 / HBM round trip
     int nt_out;   // output (+ residual) streams of more than half the 256 MB Infinity Cache: non-temporal epilogue loads / stores
     unsigned long long* trace;   // diagnostics (UC_GEMM_TRACE): per-workgroup {start, loop start, loop end, end} 100-MHz ticks + HW id
@@ -71,6 +72,12 @@ struct GldsParams {
     uc_fastdiv dWo, dHo, dHWo, dCin;   // exact fast division by cWo, cHo, cHo*cWo, cCin (conv index math)
 };
 
-// variant: 0 = 128x128 tile (4 waves), 1 = 256x128 (8 waves), 2 = 256x256 (16 waves)
-// auto_variant: the variant came from the dispatcher's heuristic (not UC_GEMM_VARIANT): the launcher may refine it per epilogue family
-int uc_launch_gemm_glds(const GldsParams& p, int variant, hipStream_t st, bool auto_variant = false);
+// One launcher per epilogue family, each in its own translation unit (gemm_glds_*.hip): they compile in parallel and each kernel
+// carries only the epilogue code its launches can reach.  They launch the kernel the plan names (gemm_plan.h) and decide nothing.
+void glds_launch_dense_bf16(const GldsParams& p, const GemmPlan& plan, hipStream_t st);
+void glds_launch_dense_f32(const GldsParams& p, const GemmPlan& plan, hipStream_t st);
+void glds_launch_dense_bs(const GldsParams& p, const GemmPlan& plan, hipStream_t st);
+void glds_launch_dense_all(const GldsParams& p, const GemmPlan& plan, hipStream_t st);
+void glds_launch_dense_all_f16(const GldsParams& p, const GemmPlan& plan, hipStream_t st);
+void glds_launch_conv(const GldsParams& p, const GemmPlan& plan, hipStream_t st);       // GLDS_EPI_ALL or GLDS_EPI_RES16
+void glds_launch_conv_f16(const GldsParams& p, const GemmPlan& plan, hipStream_t st);   // GLDS_EPI_ALL or GLDS_EPI_RES16

@@ -1082,8 +1082,6 @@ __device__ __forceinline__ void glds_epilogue_generic(glds_pe_t p, float4_t (&ac
     if (p.out_dtype == UC_F16 && p.sat_flag && __any(!(amax <= UC_F16_MAX)) && lane == 0) atomicOr(p.sat_flag, 1);
 }
 
-enum { GLDS_EPI_ALL = 0, GLDS_EPI_BF16 = 1, GLDS_EPI_F32 = 2, GLDS_EPI_BS = 3, GLDS_EPI_RES16 = 4 };
-
 // Fused narrow tail of a 128-wide tile (two wave columns of 64): out4[m][o] = tail_b[o] + sum_n act(acc[m][n] + bias[n]) * tail_w[o][n].
 // The DPT regressor's conv3x3 -> ReLU -> Conv2d(128 -> 4, 1x1): the 128-channel map is never stored.  Per wave: its 64 columns of
 // tail_w (as float4 over the four outputs) and of the bias sit in its LDS block; a lane multiplies its 16 values of a row by
@@ -1943,73 +1941,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_glds4_kernel(GldsParams p) {
     }
 }
 
-template <int EPI>
-static void launch_glds4(GldsParams p, hipStream_t st) {
-    p.tiles_m = (int)ceil_div64(p.M, 256);
-    p.tiles_n = (int)ceil_div64(p.N, 256);
-    p.dNwg = uc_make_fastdiv((unsigned)(p.tiles_m * p.tiles_n));
-    p.dPerGroup = uc_make_fastdiv((unsigned)(p.group_m * p.tiles_n));
-    p.dGm = uc_make_fastdiv((unsigned)p.group_m);
-    p.dGmLast = uc_make_fastdiv((unsigned)std::max(1, p.tiles_m % p.group_m));
-    auto kfn = gemm_bf16_glds4_kernel<EPI>;
-    constexpr int smem = 2 * 512 * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3((unsigned)p.tiles_m * p.tiles_n), dim3(256), smem, st, p);
-}
-
-// what the four-wave kernel takes: whole 8-row groups, one mode per 128-column wave tile, no split-K, 32-bit row pitches
-static inline bool glds4_ok(const GldsParams& p) {
-    return p.a_mode == UC_A_DENSE && p.M % 8 == 0 && p.N % 8 == 0 && p.M >= 8 && p.N >= 8 && p.split_k <= 1 && p.K >= 64 &&
-           (p.vt_col0 < 0 || p.vt_col0 % 128 == 0) && (p.rope_cols <= 0 || p.rope_cols % 128 == 0) && p.lda * 2 < ((int64_t)1 << 31) &&
-           p.K * 2 < ((int64_t)1 << 31) && p.M < ((int64_t)1 << 31) && p.N < ((int64_t)1 << 31);
-}
-
-template <int EPI>
-static void launch_glds8(GldsParams p, hipStream_t st) {
-    p.tiles_m = (int)ceil_div64(p.M, 256);
-    p.tiles_n = (int)ceil_div64(p.N, 256);
-    p.dNwg = uc_make_fastdiv((unsigned)(p.tiles_m * p.tiles_n));
-    p.dPerGroup = uc_make_fastdiv((unsigned)(p.group_m * p.tiles_n));
-    p.dGm = uc_make_fastdiv((unsigned)p.group_m);
-    p.dGmLast = uc_make_fastdiv((unsigned)std::max(1, p.tiles_m % p.group_m));
-    auto kfn = gemm_bf16_glds8_kernel<EPI>;
-    constexpr int smem = 2 * 512 * 128 + (EPI == GLDS_EPI_BF16 ? GLDS_SIDE_BYTES : 0);
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    p.side_lds = (EPI == GLDS_EPI_BF16 && uc_knobs().gemm_side_lds && p.ln_stats && !p.ln_partial && p.ln_colsum && p.bias && p.split_k <= 1 &&
-                  !(p.dbg & 16) && al16(p.ln_stats) && al16(p.ln_colsum) && al16(p.bias) &&
-                  (p.rope_cols <= 0 || (p.rope_pos && al16(p.rope_pos)))) ? 1 : 0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3((unsigned)p.tiles_m * p.tiles_n * (unsigned)p.split_k), dim3(512), smem, st, p);
-}
-
-template <int BM_, int BN_, int WM_, int WN_, int STAGES, int A_MODE, int BK_ = 64, int WGS_PER_CU = 1, int EPI = GLDS_EPI_ALL, bool F16 = false>
-static void launch_variant_mode(GldsParams p, hipStream_t st) {
-    p.tiles_m = (int)ceil_div64(p.M, BM_);
-    p.tiles_n = (int)ceil_div64(p.N, BN_);
-    p.dNwg = uc_make_fastdiv((unsigned)(p.tiles_m * p.tiles_n));
-    p.dPerGroup = uc_make_fastdiv((unsigned)(p.group_m * p.tiles_n));
-    p.dGm = uc_make_fastdiv((unsigned)p.group_m);
-    p.dGmLast = uc_make_fastdiv((unsigned)std::max(1, p.tiles_m % p.group_m));
-    auto kfn = gemm_bf16_glds_kernel<BM_, BN_, WM_, WN_, STAGES, A_MODE, BK_, WGS_PER_CU, EPI, F16>;
-    constexpr int smem = STAGES * (BM_ + BN_) * BK_ * 2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_set = true;
-    }
-    const unsigned slices = (BM_ == 128 && BN_ == 128 && p.fuse_split2) ? 2u : (unsigned)p.split_k;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)p.tiles_m * p.tiles_n * slices), dim3(WM_ * WN_ * 64), smem, st, p);
-}
-
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // 3x3 / pad 1 / stride 1 convolution on maps at least 64 wide, ROW-WALKING form (round 3).  The implicit-GEMM kernel above stages
 // a 256-pixel x 64-channel A tile per (tap, channel chunk): every input pixel crosses the LDS-DMA path nine times.  In the NT
@@ -2174,35 +2105,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows_kernel(GldsParams p) {
 #endif
     __syncthreads();     // every wave is done with the slabs and the ring: they become the epilogue's bounce space (8 KiB per wave)
     glds_epilogue_dispatch<FA, A_MODE, EPI, F16>(pe, acc, 0, wave_m, wave_n, tid, wave, 0, smem);
-}
-
-// shapes the row-walking conv kernel takes: stride 1, whole 64-channel chunks, 128-column tiles, maps 64 .. wide whose rows tile 256
-// pixels exactly (a tile = whole row segments of one image), 32-bit source windows
-static inline bool conv_rows_ok(const GldsParams& p) {
-    if (p.a_mode != UC_A_CONV3X3 || p.cStride != 1 || p.cCin % 64 != 0 || p.N % 128 != 0 || p.split_k > 1) return false;
-    const int W = p.cW, H = p.cH;
-    if (W < 64 || !(W % 256 == 0 || 256 % W == 0)) return false;
-    const int R = W >= 256 ? 1 : 256 / W;
-    if (H % R != 0 || p.M % 256 != 0) return false;
-    return ((int64_t)(R + 3) * W + 4) * p.cCin * 2 < ((int64_t)1 << 31) && p.N * p.K * 2 < ((int64_t)1 << 31) && p.M < ((int64_t)1 << 30);
-}
-
-template <int EPI, bool F16>
-static void launch_conv_rows(GldsParams p, hipStream_t st) {
-    p.tiles_m = (int)(p.M / 256);
-    p.tiles_n = (int)(p.N / 128);
-    p.dNwg = uc_make_fastdiv((unsigned)(p.tiles_m * p.tiles_n));
-    p.dPerGroup = uc_make_fastdiv((unsigned)(p.group_m * p.tiles_n));
-    p.dGm = uc_make_fastdiv((unsigned)p.group_m);
-    p.dGmLast = uc_make_fastdiv((unsigned)std::max(1, p.tiles_m % p.group_m));
-    auto kfn = conv3x3_rows_kernel<EPI, F16>;
-    constexpr int smem = 2 * 320 * 128 + 3 * 128 * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kfn, dim3((unsigned)p.tiles_m * p.tiles_n), dim3(512), smem, st, p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -2532,132 +2434,78 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows8_kernel(GldsParams p) {
     glds_epilogue_dispatch<FA, A_MODE, EPI, F16>(pe, acc, 0, wave_m, wave_n, tid, wave, 0, smem);
 }
 
-// shapes the eight-wave row-walking kernel takes: stride 1, whole 64-channel chunks (an even number of 32-channel super-steps), 128-column
-// tiles, maps 128 .. wide whose rows tile 512 pixels exactly (a tile = whole row segments of one image), 32-bit source windows
-// returns 0: not a shape of this kernel; 1: the segmented form (rows tile 512 pixels: no register masks); 2: the flat form (round 6: any
-// map at least 16 wide, any pixel count — tiles of 512 consecutive pixels, the last one masked)
-static inline int conv_rows8_ok(const GldsParams& p) {
-    if (p.a_mode != UC_A_CONV3X3 || p.cStride != 1 || p.cCin % 64 != 0 || p.N % 128 != 0 || p.split_k > 1) return 0;
-    const int W = p.cW, H = p.cH;
-    if (p.N * p.K * 2 >= ((int64_t)1 << 31) || p.M >= ((int64_t)1 << 30)) return 0;
-    if (W >= 128 && (W % 512 == 0 || 512 % W == 0)) {
-        const int R = W >= 512 ? 1 : 512 / W;
-        if (H % R == 0 && p.M % 512 == 0 && ((int64_t)(R + 3) * W + 4) * p.cCin * 2 < ((int64_t)1 << 31)) return 1;
-    }
-    if (W < 16 || g_uc_conv_rows_flat.load(std::memory_order_relaxed) == 0) return 0;
-    return ((int64_t)(530 + 2 * W) * p.cCin * 2 < ((int64_t)1 << 31)) ? 2 : 0;
-}
 
-// where the eight-wave form is routed by default: everywhere its shape rules allow — measured ahead of both other forms on every
-// DPT-head shape, bf16 and fp16, with and without ReLU on load (512^2 128->128 +16-19 %, 256^2 256->128 +24 %
-// over the 256-pixel row kernel, 256 output channels +8-12 % over the 256x256 implicit-GEMM tile)
-static inline bool conv_rows8_wins(const GldsParams&) { return true; }
+// ---------------------------------------------------------------------------------------------------------------------------
+// Launch of a routed uc_gemm (gemm_plan.h): the plan names the kernel and its grid, the launchers below only carry it out.
 
-template <int EPI, bool F16>
-static void launch_conv_rows8(GldsParams p, hipStream_t st) {
-    const bool flat = conv_rows8_ok(p) == 2;
-    p.tiles_m = (int)((p.M + 511) / 512);
-    p.tiles_n = (int)(p.N / 128);
+// one kernel on the plan's grid: tile-order fast divisions, the dynamic-LDS limit (set once per kernel), the launch
+template <auto KFN, int THREADS, int SMEM>
+static void glds_launch(GldsParams p, const GemmPlan& plan, hipStream_t st) {
+    p.tiles_m = (int)plan.tiles_m;
+    p.tiles_n = (int)plan.tiles_n;
     p.dNwg = uc_make_fastdiv((unsigned)(p.tiles_m * p.tiles_n));
     p.dPerGroup = uc_make_fastdiv((unsigned)(p.group_m * p.tiles_n));
     p.dGm = uc_make_fastdiv((unsigned)p.group_m);
     p.dGmLast = uc_make_fastdiv((unsigned)std::max(1, p.tiles_m % p.group_m));
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(KFN, dim3((unsigned)p.tiles_m * (unsigned)p.tiles_n * (unsigned)plan.slices), dim3(THREADS), SMEM, st, p);
+}
+
+template <int BM_, int BN_, int WM_, int WN_, int STAGES, int A_MODE, int BK_, int WGS_PER_CU, int EPI, bool F16>
+static void glds_launch_tile(const GldsParams& p, const GemmPlan& plan, hipStream_t st) {
+    glds_launch<gemm_bf16_glds_kernel<BM_, BN_, WM_, WN_, STAGES, A_MODE, BK_, WGS_PER_CU, EPI, F16>, WM_ * WN_ * 64,
+                STAGES * (BM_ + BN_) * BK_ * 2>(p, plan, st);
+}
+
+template <int EPI, bool F16, bool FLAT>
+static void glds_launch_rows8(const GldsParams& p, const GemmPlan& plan, hipStream_t st) {
     constexpr int smem = 2 * 33 * 1024 + 2 * 3 * 128 * 64;
-    auto launch = [&](auto kfn, bool& attr_set) {
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(kfn, dim3((unsigned)p.tiles_m * p.tiles_n), dim3(512), smem, st, p);
-    };
-    static bool set0 = false, set1 = false, set2 = false, set3 = false;
-    if constexpr (EPI == GLDS_EPI_RES16) {      // (glds_launch_conv_res16: no ReLU on load)
-        if (flat) launch(conv3x3_rows8_kernel<EPI, F16, false, true>, set2);
-        else launch(conv3x3_rows8_kernel<EPI, F16, false>, set0);
-    } else if (flat) {
-        if (p.relu_a) launch(conv3x3_rows8_kernel<EPI, F16, true, true>, set3);
-        else launch(conv3x3_rows8_kernel<EPI, F16, false, true>, set2);
-    } else if (p.relu_a) launch(conv3x3_rows8_kernel<EPI, F16, true>, set1);
-    else launch(conv3x3_rows8_kernel<EPI, F16, false>, set0);
+    if constexpr (EPI == GLDS_EPI_RES16) glds_launch<conv3x3_rows8_kernel<EPI, F16, false, FLAT>, 512, smem>(p, plan, st);   // (no ReLU on load)
+    else if (plan.relu_a) glds_launch<conv3x3_rows8_kernel<EPI, F16, true, FLAT>, 512, smem>(p, plan, st);
+    else glds_launch<conv3x3_rows8_kernel<EPI, F16, false, FLAT>, 512, smem>(p, plan, st);
 }
 
-// A convolution whose every tile takes the 16-bit residual epilogue (glds_epilogue_res16): 16-bit output, one or two residuals of the
-// same dtype laid out like it, bias or none, no activation — the residual conv units' second convolution.  Its own epilogue family
-// (one kernel per family: inlined next to the other drains it cost the fused-tail launches 5 % through the register allocation).
-static inline bool glds_res16_ok(const GldsParams& p) {
-    const int out16 = p.f16 ? UC_F16 : UC_BF16;
-    return p.a_mode == UC_A_CONV3X3 && p.vec_ok && p.N % 64 == 0 && p.split_k <= 1 && !p.preact && !p.dact_u && !UC_DBG(p, 16) && p.out_dtype == out16 &&
-           p.residual && p.res_dtype == out16 && p.act == UC_ACT_NONE && !p.relu_a && !p.tail_out && !p.ln_stats && !p.ln_partial && !p.stats_out && !p.twin &&
-           (p.ldr & 7) == 0 && p.vt_col0 < 0 && p.rope_cols <= 0;
-}
-// the eight-wave row kernel where the default routing takes it, else the 256x256 implicit-GEMM tile; false: not a shape of this family's kernels
-template <bool F16>
-static bool glds_launch_conv_res16(const GldsParams& p, int variant, hipStream_t st) {
-    if (!glds_res16_ok(p)) return false;
-    const int rows_mode = g_uc_conv_rows.load(std::memory_order_relaxed);
-    if (conv_rows8_ok(p) && (rows_mode == 3 || (rows_mode == 1 && conv_rows8_wins(p) && ((p.M + 511) / 512) * (p.N / 128) >= 256))) {
-        launch_conv_rows8<GLDS_EPI_RES16, F16>(p, st);
-        return true;
-    }
-    // (not the launches the 256-pixel row kernel takes: glds_launch_variants' rule)
-    const bool rows256 = rows_mode > 0 && rows_mode < 3 && conv_rows_ok(p) && (rows_mode >= 2 || (p.N == 128 && p.cCin >= 256)) && (p.M / 256) * (p.N / 128) >= 256;
-    if (variant == 2 && !rows256) {
-        launch_variant_mode<256, 256, 4, 4, 2, UC_A_CONV3X3, 64, 1, GLDS_EPI_RES16, F16>(p, st);
-        return true;
-    }
-    return false;
-}
-
-// Tile variants of one (A_MODE, EPI) pair: 0 = 128x128 (2x2 waves of 64x64), 1 = 256x128 (4x2), 2 = 256x256 (4x4), 3 = 256x128x32 with
-// two co-resident workgroups per CU.
+// the kernels of one (A_MODE, EPI, F16) family: the eight- / four-wave and 128x64 kernels are dense bf16 only, the row-walking ones
+// convolutions only, and the RES16 family has the eight-wave row kernel and the 256x256 tile
 template <int A_MODE, int EPI, bool F16 = false>
-static void glds_launch_variants(const GldsParams& p, int variant, hipStream_t st) {
-    const int deep = uc_knobs().gemm_small_stages;
-    const int64_t sk = p.split_k > 1 ? p.split_k : 1;
-    if constexpr (A_MODE == UC_A_CONV3X3) {
-        // Where it wins (conv_rows 1): 128 output channels and >= 256 input channels — 256^2 256 -> 128: 850 -> 959 TFLOP/s (fp16 834 -> 926).
-        // With 128 input channels it is level (873 -> 891, fp16 875 -> 864), with 256 output channels the 256x256 tile of the
-        // implicit-GEMM kernel streams half the weights per MFMA and stays ahead (1016 / 1106 vs 1000 / 1003 at 128^2 / 64^2): the weight
-        // tiles, which this form does not reduce, are what a conv tile's LDS-DMA traffic mostly is.  Fewer tiles than CUs: the
-        // latency-regime variants below.
-        const int rows_mode = g_uc_conv_rows.load(std::memory_order_relaxed);
-        // conv_rows 3: the eight-wave 512-pixel form wherever the shape allows; 1 (default): where it wins
-        // (fewer tiles than CUs: the latency-regime variants below — unless forced: conv_rows 3 makes the kernel choice, and with it the
-        //  summation order, independent of the batch size)
-        if (conv_rows8_ok(p) && (rows_mode == 3 || (rows_mode == 1 && conv_rows8_wins(p) && ((p.M + 511) / 512) * (p.N / 128) >= 256))) {
-            launch_conv_rows8<EPI, F16>(p, st);
-            return;
+static void glds_launch_family(const GldsParams& p, const GemmPlan& plan, hipStream_t st) {
+    constexpr bool dense_bf16 = A_MODE == UC_A_DENSE && !F16, conv = A_MODE == UC_A_CONV3X3;
+    if constexpr (EPI == GLDS_EPI_RES16) {
+        switch (plan.kernel) {
+            case UC_GK_CONV_ROWS8: glds_launch_rows8<EPI, F16, false>(p, plan, st); break;
+            case UC_GK_CONV_ROWS8_FLAT: glds_launch_rows8<EPI, F16, true>(p, plan, st); break;
+            case UC_GK_T256x256: glds_launch_tile<256, 256, 4, 4, 2, A_MODE, 64, 1, EPI, F16>(p, plan, st); break;
+            default: break;
         }
-        if (rows_mode > 0 && rows_mode < 3 && conv_rows_ok(p) && (rows_mode >= 2 || (p.N == 128 && p.cCin >= 256)) && (p.M / 256) * (p.N / 128) >= 256) {
-            launch_conv_rows<EPI, F16>(p, st);
-            return;
-        }
-    }
-    switch (variant) {
-        case 1:
-            // latency regime (fewer workgroups than CUs: every K-step waits for its own DMA): a 3-stage ring keeps two stages in flight
-            if (deep == 3 && ceil_div64(p.M, 256) * ceil_div64(p.N, 128) * sk <= 256) launch_variant_mode<256, 128, 4, 2, 3, A_MODE, 64, 1, EPI, F16>(p, st);
-            else launch_variant_mode<256, 128, 4, 2, 2, A_MODE, 64, 1, EPI, F16>(p, st);
+    } else switch (plan.kernel) {
+        case UC_GK_T128x128_S2: glds_launch_tile<128, 128, 2, 2, 2, A_MODE, 64, 1, EPI, F16>(p, plan, st); break;
+        case UC_GK_T128x128_S3: glds_launch_tile<128, 128, 2, 2, 3, A_MODE, 64, 1, EPI, F16>(p, plan, st); break;
+        case UC_GK_T256x128_S2: glds_launch_tile<256, 128, 4, 2, 2, A_MODE, 64, 1, EPI, F16>(p, plan, st); break;
+        case UC_GK_T256x128_S3: glds_launch_tile<256, 128, 4, 2, 3, A_MODE, 64, 1, EPI, F16>(p, plan, st); break;
+        case UC_GK_T256x256: glds_launch_tile<256, 256, 4, 4, 2, A_MODE, 64, 1, EPI, F16>(p, plan, st); break;
+        case UC_GK_T256x128_BK32: glds_launch_tile<256, 128, 4, 2, 3, A_MODE, 32, 2, EPI, F16>(p, plan, st); break;
+        case UC_GK_T128x64:
+            if constexpr (dense_bf16) glds_launch_tile<128, 64, 2, 1, 3, A_MODE, 64, 1, EPI, F16>(p, plan, st);
             break;
-        case 2: launch_variant_mode<256, 256, 4, 4, 2, A_MODE, 64, 1, EPI, F16>(p, st); break;
-        case 3: launch_variant_mode<256, 128, 4, 2, 3, A_MODE, 32, 2, EPI, F16>(p, st); break;
-        case 6:   // 256x256x64 with eight waves of 128x64 and register-resident next-chunk fragments (dense only)
-            // (its DMA addresses row groups of 8 uniformly: matrices whose last group is partial stay on the 16-wave kernel)
-            if (!F16 && A_MODE == UC_A_DENSE && p.M % 8 == 0 && p.N % 8 == 0) {
-                if constexpr (A_MODE == UC_A_DENSE && !F16) launch_glds8<EPI>(p, st);
-            } else launch_variant_mode<256, 256, 4, 4, 2, A_MODE, 64, 1, EPI, F16>(p, st);
+        case UC_GK_EIGHT_WAVE:
+            if constexpr (dense_bf16) glds_launch<gemm_bf16_glds8_kernel<EPI>, 512, 2 * 512 * 128 + (EPI == GLDS_EPI_BF16 ? GLDS_SIDE_BYTES : 0)>(p, plan, st);
             break;
-        case 7:   // 256x256x64 with four waves of 128x128, accumulators in AGPRs, hand-scheduled K-loop (dense only)
-            if (!F16 && glds4_ok(p)) {
-                if constexpr (A_MODE == UC_A_DENSE && !F16) launch_glds4<EPI>(p, st);
-            } else launch_variant_mode<256, 256, 4, 4, 2, A_MODE, 64, 1, EPI, F16>(p, st);
+        case UC_GK_FOUR_WAVE:
+            if constexpr (dense_bf16) glds_launch<gemm_bf16_glds4_kernel<EPI>, 256, 2 * 512 * 128>(p, plan, st);
             break;
-        case 4:   // 128x64 (two waves): the latency regime's small tile — launches whose 128x128 tiles cover at most half the CUs
-            if constexpr (A_MODE == UC_A_DENSE && !F16) { launch_variant_mode<128, 64, 2, 1, 3, A_MODE, 64, 1, EPI, F16>(p, st); break; }
-            [[fallthrough]];
-        default:
-            if (deep == 3 && ceil_div64(p.M, 128) * ceil_div64(p.N, 128) * sk <= 512) launch_variant_mode<128, 128, 2, 2, 3, A_MODE, 64, 1, EPI, F16>(p, st);
-            else launch_variant_mode<128, 128, 2, 2, 2, A_MODE, 64, 1, EPI, F16>(p, st);
+        case UC_GK_CONV_ROWS:
+            if constexpr (conv) glds_launch<conv3x3_rows_kernel<EPI, F16>, 512, 2 * 320 * 128 + 3 * 128 * 128>(p, plan, st);
             break;
+        case UC_GK_CONV_ROWS8:
+            if constexpr (conv) glds_launch_rows8<EPI, F16, false>(p, plan, st);
+            break;
+        case UC_GK_CONV_ROWS8_FLAT:
+            if constexpr (conv) glds_launch_rows8<EPI, F16, true>(p, plan, st);
+            break;
+        default: break;
     }
 }
