@@ -1,0 +1,60 @@
+// CPU driver of uc_attention_fwd_plan / uc_attention_bwd_plan (uniception_amd/csrc/attention_plan.h) for tests/test_attention_plan.py.
+// stdin: one launch per line, `name=value` tokens — `fn=fwd` or `fn=bwd`, the AttnFwdDesc / AttnBwdDesc fields by their names (O as an
+// integer address) and the knob snapshot (p64, bwd64, role_split, cus, dbg).
+// stdout: one line per launch, forward `kernel grid_x grid_y grid_z block nqt fixup_grid`, backward `dq dq_grid dkv dkv_grid`.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <string>
+#include "attention_plan.h"
+
+static const char* const FWD_KERNELS[] = {"reg128", "dma4", "dma8", "rs8", "p64", "p64_tail", "reg128_drop", "f32_32", "f32_64",
+                                          "f32_32_drop", "f32_64_drop", "dma4_dbg"};
+static const char* const DQ_KERNELS[] = {"dq32", "dq64", "dq32_drop"};
+static const char* const DKV_KERNELS[] = {"dkv32", "dkv64", "dkv32_drop"};
+
+static bool set_field(AttnFwdDesc& f, AttnBwdDesc& b, AttnKnobs& k, const std::string& n, const char* v) {
+    const long long i = strtoll(v, nullptr, 0);
+#define FB(x) if (n == #x) { f.x = (decltype(f.x))i; b.x = (decltype(b.x))i; return true; }
+#define F(x) if (n == #x) { f.x = (decltype(f.x))i; return true; }
+#define K(x) if (n == #x) { k.x = (int)i; return true; }
+    FB(B) FB(H) FB(Nq) FB(Nk) FB(q_sb) FB(q_sn) FB(q_sh) FB(k_sb) FB(k_sn) FB(k_sh) FB(v_sb) FB(v_sn) FB(v_sh) FB(o_sb) FB(o_sn) FB(o_sh)
+    FB(drop) F(dtype) F(v_layout) F(D) F(O)
+    K(p64) K(bwd64) K(role_split) K(cus) K(dbg)
+#undef FB
+#undef F
+#undef K
+    return false;
+}
+
+int main() {
+    char line[4096];
+    while (fgets(line, sizeof line, stdin)) {
+        AttnFwdDesc f;
+        AttnBwdDesc b;
+        memset(&f, 0, sizeof f);
+        memset(&b, 0, sizeof b);
+        AttnKnobs k = {1, 1, 0, 256, 0};   // the library's defaults on a 256-CU device
+        bool bwd = false;
+        for (char* t = strtok(line, " \t\n"); t; t = strtok(nullptr, " \t\n")) {
+            char* eq = strchr(t, '=');
+            const std::string n = eq ? std::string(t, eq - t) : std::string();
+            if (eq && n == "fn" && (!strcmp(eq + 1, "fwd") || !strcmp(eq + 1, "bwd"))) {
+                bwd = !strcmp(eq + 1, "bwd");
+                continue;
+            }
+            if (!eq || !set_field(f, b, k, n, eq + 1)) {
+                fprintf(stderr, "bad token %s\n", t);
+                return 2;
+            }
+        }
+        if (bwd) {
+            const AttnBwdPlan p = uc_attention_bwd_plan(b, k);
+            printf("%s %u %s %u\n", DQ_KERNELS[p.dq], p.dq_grid, DKV_KERNELS[p.dkv], p.dkv_grid);
+        } else {
+            const AttnFwdPlan p = uc_attention_fwd_plan(f, k);
+            printf("%s %u %u %u %d %d %d\n", FWD_KERNELS[p.kernel], p.grid[0], p.grid[1], p.grid[2], p.block, p.nqt, p.fixup_grid);
+        }
+    }
+    return 0;
+}

@@ -690,6 +690,25 @@ def test_attention_bf16_spiked_keys(gpu):
     assert rel_l2(out.cpu().float(), ref) < 8e-3
 
 
+def test_attention_bf16_register_staged(gpu):
+    """The register-staged attn_bf16_kernel: an output whose strides are multiples of 4 elements but not of 8 (a [B, Nq, H, 68]
+    buffer sliced to 64 channels, odd H) fails the LDS-DMA kernels' 16-byte stores — the only launch that takes it
+    (attention_plan.h; tests/test_attention_plan.py: dma_o_strides_4).  The four padding channels stay untouched."""
+    from uniception_amd import ops
+    B, H, Nq, Nk, D = 2, 3, 300, 260, 64
+    g = torch.Generator().manual_seed(11)
+    q = (torch.randn(B, Nq, H, D, generator=g) * 1.5).bfloat16()
+    k = (torch.randn(B, Nk, H, D, generator=g) * 1.5).bfloat16()
+    v = torch.randn(B, Nk, H, D, generator=g).bfloat16()
+    ref = sdpa_ref(q, k, v, D ** -0.5)
+    buf = torch.full((B, Nq, H, 68), float("nan"), dtype=torch.bfloat16, device=gpu)
+    out = buf[..., :D]
+    assert out.stride()[:3] == (Nq * H * 68, H * 68, 68) and (H * 68) % 8 == 4
+    ops.attention(q.to(gpu), k.to(gpu), ops.vt_pack(v.to(gpu)), D ** -0.5, v_packed=True, out=out)
+    assert rel_l2(out.cpu().float(), ref) < 8e-3
+    assert torch.isnan(buf[..., D:]).all()
+
+
 @pytest.mark.parametrize("B,H,Nq,Nk", [(2, 3, 1024, 1024), (1, 2, 1369, 1369), (2, 1, 300, 1370), (1, 2, 256, 100), (3, 2, 512, 700), (1, 1, 260, 4096),
                                        (1, 2, 130, 65), (9, 16, 196, 196)])
 def test_attention_persistent_kernel(gpu, B, H, Nq, Nk):

@@ -22,9 +22,6 @@ python tools/rocpd_stats.py $db > $out/${tag}_train_step_kernel_stats_dpt_pairs6
 rm -rf $out/train
 python bench.py --mode train --steps 10 --warmup 3 --full > $out/${tag}_bench_train_dpt_pairs64.json 2> $out/bench_train.err
 cat $out/${tag}_bench_train_dpt_pairs64.json
-# SQ counters of the bf16 attention forward (VERDICT r3 next #9 asks for the evidence): tools/pmc_attn.sh, eight-wave workgroups
-bash tools/pmc_attn.sh "8" > $out/${tag}_probe_attention_sq_counters.txt 2>&1
-rm -rf gpurun_out/pmc_attn
 # the per-shape dense GEMM table and the two probes of the round
 python tools/bench_model_gemms2.py 128 auto,2,6,7 enc,dec 0.4 > $out/${tag}_model_gemm_shapes.txt 2>&1
 python tools/bench_attention_ab.py > $out/${tag}_attention_ab_same_box.txt 2>&1

@@ -19,5 +19,5 @@ if len(sys.argv) > 1:
     print(f"UC_ATTN_DBG={os.environ.get('UC_ATTN_DBG', '0')}: {t*1e6:7.1f} us  {4.0*B*H*N*N*64/t/1e12:6.1f} TFLOP/s-equivalent")
 else:
     for d in ("0", "1", "2", "3", "4", "5", "8", "16", "24", "0"):
-        env = dict(os.environ, UC_ATTN_DBG=d, UC_ATTN_NW=os.environ.get("UC_ATTN_NW", "4"))
+        env = dict(os.environ, UC_ATTN_DBG=d)
         subprocess.run([sys.executable, __file__, "run"], env=env)

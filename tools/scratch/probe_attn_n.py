@@ -14,4 +14,4 @@ for (B, H, N) in [(64, 16, 1024), (64, 16, 1280), (64, 16, 1344), (64, 16, 1370)
     q = torch.randn(B, N, H, 64, device=dev).bfloat16(); k = torch.randn(B, N, H, 64, device=dev).bfloat16(); v = torch.randn(B, N, H, 64, device=dev).bfloat16()
     vt = ops.vt_pack(v)
     t = timeit(lambda: ops.attention(q, k, vt, 0.125, v_packed=True))
-    print(f"dma={os.environ.get('UC_ATTN_DMA','1')} B={B} H={H} N={N}: {t*1e6:8.1f} us {4.0*B*H*N*N*64/t/1e12:7.1f} TF/s", flush=True)
+    print(f"B={B} H={H} N={N}: {t*1e6:8.1f} us {4.0*B*H*N*N*64/t/1e12:7.1f} TF/s", flush=True)

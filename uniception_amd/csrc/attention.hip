@@ -16,6 +16,7 @@
 #include "common.h"
 #include "knobs.h"
 #include "attention_p64.h"
+#include "attention_plan.h"
 #include <stdlib.h>
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -316,7 +317,7 @@ __device__ __forceinline__ att_uint4_t att_make_srd(const void* base) {
                          (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pa >> 32) & 0xffffu)), 0xffffff00u, 0x00020000u};
 }
 
-// What bounds it (round 2, tools/scratch/probe_attn_anatomy.py + tools/pmc_attn.sh, B = 64, H = 16, N = 1024): the costs of the exp2
+// What bounds it (round 2, tools/scratch/probe_attn_anatomy.py and its SQ counters, B = 64, H = 16, N = 1024): the costs of the exp2
 // work and of the PV products are ADDITIVE (-18 % without the exps, -20 % without the PV MFMAs, -2 % without the per-tile
 // barrier; static priorities or a start stagger per workgroup slot: nothing).  SQ_ACTIVE_INST_VALU — which includes a matrix
 // instruction for its whole 32 cycles — is 81-86 % of the wave-resident time of a SIMD: matrix and vector instructions of the
@@ -938,6 +939,106 @@ extern "C" int uc_attention_drop_mask(void* mask, int B, int H, int Nq, int Nk, 
     return UC_OK;
 }
 
+#ifdef UC_DIAG
+// diag build: the four-wave DMA kernel with its anatomy switches (results are wrong): 1 no per-tile barrier, 2 no exp (P = S),
+// 4 no PV MFMAs
+static void launch_attn_dma4_dbg(int dbg, dim3 grid, hipStream_t st, const AttnParams& p) {
+    if (dbg == 1) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 1>), grid, dim3(256), 0, st, p);
+    else if (dbg == 2) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 2>), grid, dim3(256), 0, st, p);
+    else if (dbg == 3) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 3>), grid, dim3(256), 0, st, p);
+    else if (dbg == 4) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 4>), grid, dim3(256), 0, st, p);
+    else if (dbg == 5) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 5>), grid, dim3(256), 0, st, p);
+    else if (dbg == 8) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 8>), grid, dim3(256), 0, st, p);
+    else if (dbg == 16) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 16>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 24>), grid, dim3(256), 0, st, p);
+}
+#endif
+
+// uc_attention_fwd and, with drop_p > 0, uc_attention_fwd_drop (`fn`: the entry point the messages name): validate, fill AttnParams,
+// snapshot the knobs, plan the launch (attention_plan.h) and carry the plan out
+static int attention_fwd_impl(const char* fn, const void* Q, const void* K, const void* V, void* O, int dtype, int v_layout,
+                              int B, int H, int Nq, int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh,
+                              int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh,
+                              int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale, float* lse, float drop_p,
+                              unsigned long long seed, uc_stream_t stream) {
+    const bool drop = drop_p != 0.f;
+    UC_REQUIRE(Q && K && V && O, "%s: null pointer", fn);
+    UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0, "%s: bad shape", fn);
+    UC_REQUIRE(H <= 65535 && B <= 65535, "%s: B and H must fit a grid dimension", fn);
+    if (dtype == UC_BF16) {
+        UC_REQUIRE(D == 64, "%s(bf16): head_dim must be 64 (got %d)", fn, D);
+        UC_REQUIRE(v_layout == UC_V_PACKED_T, "%s(bf16): V must be in the packed VT layout (uc_vt_pack)", fn);
+        UC_REQUIRE(q_sb % 8 == 0 && q_sn % 8 == 0 && q_sh % 8 == 0 && k_sb % 8 == 0 && k_sn % 8 == 0 && k_sh % 8 == 0,
+                   "%s(bf16): Q/K strides must be multiples of 8 elements", fn);
+        UC_REQUIRE(o_sb % 4 == 0 && o_sn % 4 == 0 && o_sh % 4 == 0, "%s(bf16): O strides must be multiples of 4", fn);
+        UC_REQUIRE(((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0) && ((uintptr_t)O % 8 == 0),
+                   "%s(bf16): pointer alignment", fn);
+    } else if (dtype == UC_F32) {
+        UC_REQUIRE(v_layout == UC_V_ROWMAJOR, "%s(f32): V must be row-major", fn);
+        UC_REQUIRE(D <= 64, "%s(f32): head_dim must be <= 64 (got %d)", fn, D);
+    } else {
+        uc_set_error("%s: unsupported dtype %d", fn, dtype);
+        return UC_ERR_BAD_ARG;
+    }
+    // the knob snapshot: uc_knobs() first (it stores the environment's initial values of the run-time switchable ones)
+    const UcKnobs& kn = uc_knobs();
+    AttnKnobs knobs = {};
+    knobs.p64 = g_uc_attn_p64.load(std::memory_order_relaxed);
+    knobs.role_split = g_uc_attn_rs.load(std::memory_order_relaxed);
+    knobs.cus = uc_num_cus();
+#ifdef UC_DIAG
+    knobs.dbg = kn.attn_dbg;
+#endif
+    const AttnFwdDesc desc = {dtype, v_layout, B, H, Nq, Nk, D, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh,
+                              (uintptr_t)O, drop};
+    const AttnFwdPlan plan = uc_attention_fwd_plan(desc, knobs);
+
+    AttnParams p;
+    p.Q = Q; p.K = K; p.V = V; p.O = O; p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.D = D;
+    p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
+    p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
+    p.npad = (Nk + 63) / 64 * 64;
+    p.scale = scale;
+    p.lse = lse;
+    p.prio_young = drop ? 0 : kn.attn_prio;
+    p.drop = uc_make_dropout(drop_p, seed);
+    if (plan.nqt) { p.dGroup = uc_make_fastdiv((unsigned)(8 * plan.nqt)); p.dNq = uc_make_fastdiv((unsigned)plan.nqt); p.dH = uc_make_fastdiv((unsigned)H); }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(plan.grid[0], plan.grid[1], plan.grid[2]), block(plan.block);
+    switch (plan.kernel) {
+        case UC_AF_REG128: hipLaunchKernelGGL(attn_bf16_kernel, grid, block, 0, st, p); break;
+        case UC_AF_DMA4: hipLaunchKernelGGL(attn_bf16_dma_kernel<4>, grid, block, 0, st, p); break;
+        case UC_AF_DMA8: hipLaunchKernelGGL(attn_bf16_dma_kernel<8>, grid, block, 0, st, p); break;
+        case UC_AF_RS8: hipLaunchKernelGGL(attn_bf16_rs_kernel, grid, block, 0, st, p); break;
+        case UC_AF_P64:
+        case UC_AF_P64_TAIL: {
+            AttnP64Params pp;
+            pp.Q = Q; pp.K = K; pp.V = V; pp.O = O; pp.lse = lse; pp.B = B; pp.H = H; pp.Nq = Nq; pp.Nk = Nk;
+            pp.q_sb = q_sb; pp.q_sn = q_sn; pp.q_sh = q_sh; pp.k_sb = k_sb; pp.k_sn = k_sn; pp.k_sh = k_sh; pp.o_sb = o_sb; pp.o_sn = o_sn; pp.o_sh = o_sh;
+            pp.npad = p.npad; pp.c = scale * 1.44269504088896340736f; pp.q_prescaled = 0;
+            pp.nq = (Nq + 255) / 256; pp.dNq = uc_make_fastdiv((unsigned)pp.nq); pp.dH = uc_make_fastdiv((unsigned)H);
+            pp.dbg = nullptr;
+            if (plan.kernel == UC_AF_P64_TAIL) hipLaunchKernelGGL(attn_bf16_p64_kernel<true>, grid, block, 0, st, pp);
+            else hipLaunchKernelGGL(attn_bf16_p64_kernel<false>, grid, block, 0, st, pp);
+            UC_CHECK_LAUNCH("uc_attention_fwd (persistent kernel)");
+            hipLaunchKernelGGL(attn_bf16_fixup_kernel, dim3((unsigned)plan.fixup_grid), dim3(256), 0, st, p);
+            break;
+        }
+        case UC_AF_REG128_DROP: hipLaunchKernelGGL(attn_bf16_drop_kernel, grid, block, 0, st, p); break;
+        case UC_AF_F32_32: hipLaunchKernelGGL((attn_f32_kernel<32>), grid, block, 0, st, p); break;
+        case UC_AF_F32_64: hipLaunchKernelGGL((attn_f32_kernel<64>), grid, block, 0, st, p); break;
+        case UC_AF_F32_32_DROP: hipLaunchKernelGGL((attn_f32_kernel<32, true>), grid, block, 0, st, p); break;
+        case UC_AF_F32_64_DROP: hipLaunchKernelGGL((attn_f32_kernel<64, true>), grid, block, 0, st, p); break;
+        case UC_AF_DMA4_DBG:
+#ifdef UC_DIAG
+            launch_attn_dma4_dbg(plan.dbg, grid, st, p);
+#endif
+            break;
+    }
+    UC_CHECK_LAUNCH(fn);
+    return UC_OK;
+}
+
 // Attention forward with dropout of the probabilities (training, attn_drop > 0): the argument list of uc_attention_fwd + (drop_p, seed).
 // bf16: the register-staged 128-query kernel with the mask applied between the softmax and the second product; fp32: the verification
 // kernel.  drop_p == 0 is uc_attention_fwd.
@@ -947,140 +1048,16 @@ extern "C" int uc_attention_fwd_drop(const void* Q, const void* K, const void* V
                                      int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale, float* lse, float drop_p,
                                      unsigned long long seed, uc_stream_t stream) {
     UC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "uc_attention_fwd_drop: drop_p must be in [0, 1) (got %g)", (double)drop_p);
-    if (drop_p == 0.f)
-        return uc_attention_fwd(Q, K, V, O, dtype, v_layout, B, H, Nq, Nk, D, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh,
-                                scale, lse, stream);
-    UC_REQUIRE(Q && K && V && O, "uc_attention_fwd_drop: null pointer");
-    UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0, "uc_attention_fwd_drop: bad shape");
-    UC_REQUIRE(H <= 65535 && B <= 65535, "uc_attention_fwd_drop: B and H must fit a grid dimension");
-    AttnParams p;
-    p.Q = Q; p.K = K; p.V = V; p.O = O; p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.D = D;
-    p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
-    p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
-    p.npad = (Nk + 63) / 64 * 64;
-    p.scale = scale;
-    p.lse = lse;
-    p.prio_young = 0;
-    p.drop = uc_make_dropout(drop_p, seed);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_BF16) {
-        UC_REQUIRE(D == 64, "uc_attention_fwd_drop(bf16): head_dim must be 64 (got %d)", D);
-        UC_REQUIRE(v_layout == UC_V_PACKED_T, "uc_attention_fwd_drop(bf16): V must be in the packed VT layout (uc_vt_pack)");
-        UC_REQUIRE(q_sb % 8 == 0 && q_sn % 8 == 0 && q_sh % 8 == 0 && k_sb % 8 == 0 && k_sn % 8 == 0 && k_sh % 8 == 0,
-                   "uc_attention_fwd_drop(bf16): Q/K strides must be multiples of 8 elements");
-        UC_REQUIRE(o_sb % 4 == 0 && o_sn % 4 == 0 && o_sh % 4 == 0, "uc_attention_fwd_drop(bf16): O strides must be multiples of 4");
-        UC_REQUIRE(((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0) && ((uintptr_t)O % 8 == 0),
-                   "uc_attention_fwd_drop(bf16): pointer alignment");
-        hipLaunchKernelGGL(attn_bf16_drop_kernel, dim3((Nq + 127) / 128, H, B), dim3(256), 0, st, p);
-    } else if (dtype == UC_F32) {
-        UC_REQUIRE(v_layout == UC_V_ROWMAJOR, "uc_attention_fwd_drop(f32): V must be row-major");
-        UC_REQUIRE(D <= 64, "uc_attention_fwd_drop(f32): head_dim must be <= 64 (got %d)", D);
-        const dim3 grid((Nq + 127) / 128, H, B);
-        if (D <= 32) hipLaunchKernelGGL((attn_f32_kernel<32, true>), grid, dim3(128), 0, st, p);
-        else hipLaunchKernelGGL((attn_f32_kernel<64, true>), grid, dim3(128), 0, st, p);
-    } else {
-        uc_set_error("uc_attention_fwd_drop: unsupported dtype %d", dtype);
-        return UC_ERR_BAD_ARG;
-    }
-    UC_CHECK_LAUNCH("uc_attention_fwd_drop");
-    return UC_OK;
+    const bool drop = drop_p != 0.f;
+    return attention_fwd_impl(drop ? "uc_attention_fwd_drop" : "uc_attention_fwd", Q, K, V, O, dtype, v_layout, B, H, Nq, Nk, D, q_sb, q_sn,
+                              q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh, scale, lse, drop ? drop_p : 0.f, drop ? seed : 0ull,
+                              stream);
 }
 
 extern "C" int uc_attention_fwd(const void* Q, const void* K, const void* V, void* O, int dtype, int v_layout,
                                 int B, int H, int Nq, int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh,
                                 int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh,
                                 int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale, float* lse, uc_stream_t stream) {
-    UC_REQUIRE(Q && K && V && O, "uc_attention_fwd: null pointer");
-    UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0, "uc_attention_fwd: bad shape");
-    UC_REQUIRE(H <= 65535 && B <= 65535, "uc_attention_fwd: B and H must fit a grid dimension");
-    AttnParams p;
-    p.Q = Q; p.K = K; p.V = V; p.O = O; p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.D = D;
-    p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
-    p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
-    p.npad = (Nk + 63) / 64 * 64;
-    p.scale = scale;
-    p.lse = lse;
-    p.prio_young = uc_knobs().attn_prio;
-    p.drop = uc_make_dropout(0.f, 0ull);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_BF16) {
-        UC_REQUIRE(D == 64, "uc_attention_fwd(bf16): head_dim must be 64 (got %d)", D);
-        UC_REQUIRE(v_layout == UC_V_PACKED_T, "uc_attention_fwd(bf16): V must be in the packed VT layout (uc_vt_pack)");
-        UC_REQUIRE(q_sb % 8 == 0 && q_sn % 8 == 0 && q_sh % 8 == 0 && k_sb % 8 == 0 && k_sn % 8 == 0 && k_sh % 8 == 0,
-                   "uc_attention_fwd(bf16): Q/K strides must be multiples of 8 elements");
-        UC_REQUIRE(o_sb % 4 == 0 && o_sn % 4 == 0 && o_sh % 4 == 0, "uc_attention_fwd(bf16): O strides must be multiples of 4");
-        UC_REQUIRE(((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0) && ((uintptr_t)O % 8 == 0),
-                   "uc_attention_fwd(bf16): pointer alignment");
-        // eight waves per workgroup (256 queries share each K / VT tile) when that does not add a mostly empty query tile
-        const int nw_env = uc_knobs().attn_nw;
-        const int waste8 = (Nq + 255) / 256 * 256 - Nq, waste4 = (Nq + 127) / 128 * 128 - Nq;
-        // (a launch whose 256-query tiles would not give every CU two workgroups takes 128-query tiles: one pair of 512 x 512 views is
-        //  128 tiles of 256 queries — half the chip idle — or 256 of 128)
-        const bool few8 = (int64_t)((Nq + 255) / 256) * H * B < 2 * (int64_t)uc_num_cus();
-        const int nw = nw_env == 4 || nw_env == 8 ? nw_env : ((Nq >= 256 && waste8 - waste4 < 64 && !few8) ? 8 : 4);
-        const int qtile = 32 * nw, nqt = (Nq + qtile - 1) / qtile;
-        p.dGroup = uc_make_fastdiv((unsigned)(8 * nqt)); p.dNq = uc_make_fastdiv((unsigned)nqt); p.dH = uc_make_fastdiv((unsigned)H);
-        const int use_dma = uc_knobs().attn_dma;
-        // DMA-staged kernel: whole 64-key tiles, 32-bit byte offsets inside one (batch, head)'s K rows / VT rows
-        const bool dma_ok = use_dma && (int64_t)nqt * H * B < ((int64_t)1 << 31) && (uintptr_t)O % 16 == 0 && o_sb % 8 == 0 && o_sn % 8 == 0 && o_sh % 8 == 0 && (int64_t)32 * q_sn * 2 < ((int64_t)1 << 31) && (int64_t)Nk * k_sn * 2 < ((int64_t)1 << 31) && (int64_t)64 * p.npad * 2 < ((int64_t)1 << 31);
-#ifdef UC_DIAG
-        const int dbg = uc_knobs().attn_dbg;   // diag build only (results are wrong): 1 no per-tile barrier, 2 no exp (P = S), 4 no PV MFMAs
-        if (dma_ok && nw == 4 && dbg) {
-            const dim3 g((unsigned)(nqt * H * B));
-            if (dbg == 1) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 1>), g, dim3(256), 0, st, p);
-            else if (dbg == 2) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 2>), g, dim3(256), 0, st, p);
-            else if (dbg == 3) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 3>), g, dim3(256), 0, st, p);
-            else if (dbg == 4) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 4>), g, dim3(256), 0, st, p);
-            else if (dbg == 5) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 5>), g, dim3(256), 0, st, p);
-            else if (dbg == 8) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 8>), g, dim3(256), 0, st, p);
-            else if (dbg == 16) hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 16>), g, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((attn_bf16_dma_kernel<4, 24>), g, dim3(256), 0, st, p);
-        } else
-#endif
-        // persistent 64-queries-per-wave kernel (attention_p64.h) + its fix-up scan: 32-bit DMA offsets as above, at least two key
-        // tiles, and (policy) enough (batch, head, 256-query tile) items — one per workgroup of the 2 x 256 (measured break-even: 384 items
-        // at 1024 keys, tools/bench_attention_ab.py; 256 items when an item is 64 key tiles long) —, a query count
-        // that does not leave a quarter of the last tile empty.  (A wanted log-sum-exp is no obstacle: the kernel rounds scale * log2(e) * Q
-        // to bf16, so its scores and LSE carry ~2^-9 of |q| |k| scale — and the backward's dQ kernel rounds Q the same way and recomputes
-        // exactly these scores, the dK / dV kernel rounds K instead: the same noise class either way.)
-        const int p64_mode = g_uc_attn_p64.load(std::memory_order_relaxed);
-        const int64_t p64_items = (int64_t)B * H * ((Nq + 255) / 256);
-        const int waste256 = (Nq + 255) / 256 * 256 - Nq;
-        const bool p64_ok = dma_ok && p64_mode && Nk > 64 && p64_items < ((int64_t)1 << 28) && (int64_t)64 * q_sn * 2 < ((int64_t)1 << 31) && (int64_t)64 * o_sn * 2 < ((int64_t)1 << 31) &&
-                            (p64_mode == 2 || ((p64_items >= 512 || (p64_items >= 256 && Nk >= 4096)) && waste256 * 4 <= Nq));
-        if (p64_ok && !g_uc_attn_rs.load(std::memory_order_relaxed)) {
-            AttnP64Params pp;
-            pp.Q = Q; pp.K = K; pp.V = V; pp.O = O; pp.lse = lse; pp.B = B; pp.H = H; pp.Nq = Nq; pp.Nk = Nk;
-            pp.q_sb = q_sb; pp.q_sn = q_sn; pp.q_sh = q_sh; pp.k_sb = k_sb; pp.k_sn = k_sn; pp.k_sh = k_sh; pp.o_sb = o_sb; pp.o_sn = o_sn; pp.o_sh = o_sh;
-            pp.npad = p.npad; pp.c = scale * 1.44269504088896340736f; pp.q_prescaled = 0;
-            pp.nq = (Nq + 255) / 256; pp.dNq = uc_make_fastdiv((unsigned)pp.nq); pp.dH = uc_make_fastdiv((unsigned)H);
-            pp.dbg = nullptr;
-            const int per_cu = 2, ncu = uc_num_cus();
-            int grid = per_cu * ncu / 8 * 8;
-            if (grid < 8) grid = 8;
-            const int64_t items8 = (p64_items + 7) / 8 * 8;
-            if ((int64_t)grid > items8) grid = (int)items8;
-            if (Nk & 63) hipLaunchKernelGGL(attn_bf16_p64_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, pp);
-            else hipLaunchKernelGGL(attn_bf16_p64_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, pp);
-            UC_CHECK_LAUNCH("uc_attention_fwd (persistent kernel)");
-            const int64_t nblocks = (int64_t)B * H * ((Nq + 63) / 64);
-            int fgrid = (int)((nblocks + 255) / 256 < ncu ? (nblocks + 255) / 256 : ncu);
-            hipLaunchKernelGGL(attn_bf16_fixup_kernel, dim3((unsigned)fgrid), dim3(256), 0, st, p);
-        } else
-        if (dma_ok && nw == 8 && g_uc_attn_rs.load(std::memory_order_relaxed)) hipLaunchKernelGGL(attn_bf16_rs_kernel, dim3((unsigned)(nqt * H * B)), dim3(512), 0, st, p);
-        else if (dma_ok && nw == 8) hipLaunchKernelGGL(attn_bf16_dma_kernel<8>, dim3((unsigned)(nqt * H * B)), dim3(512), 0, st, p);
-        else if (dma_ok) hipLaunchKernelGGL(attn_bf16_dma_kernel<4>, dim3((unsigned)(nqt * H * B)), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(attn_bf16_kernel, dim3((Nq + 127) / 128, H, B), dim3(256), 0, st, p);
-    } else if (dtype == UC_F32) {
-        UC_REQUIRE(v_layout == UC_V_ROWMAJOR, "uc_attention_fwd(f32): V must be row-major");
-        UC_REQUIRE(D <= 64, "uc_attention_fwd(f32): head_dim must be <= 64 (got %d)", D);
-        const dim3 grid((Nq + 127) / 128, H, B);
-        if (D <= 32) hipLaunchKernelGGL((attn_f32_kernel<32>), grid, dim3(128), 0, st, p);
-        else hipLaunchKernelGGL((attn_f32_kernel<64>), grid, dim3(128), 0, st, p);
-    } else {
-        uc_set_error("uc_attention_fwd: unsupported dtype %d", dtype);
-        return UC_ERR_BAD_ARG;
-    }
-    UC_CHECK_LAUNCH("uc_attention_fwd");
-    return UC_OK;
+    return attention_fwd_impl("uc_attention_fwd", Q, K, V, O, dtype, v_layout, B, H, Nq, Nk, D, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh,
+                              v_sb, v_sn, v_sh, o_sb, o_sn, o_sh, scale, lse, 0.f, 0ull, stream);
 }

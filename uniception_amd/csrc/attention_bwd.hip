@@ -19,6 +19,7 @@
 // 2-way conflicts between rows r and r+2, which the MFMA/VALU work hides), single-buffered, 2-3 workgroups per CU.
 #include "common.h"
 #include "knobs.h"
+#include "attention_plan.h"
 #include <math.h>
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -121,32 +122,6 @@ __device__ __forceinline__ void ab_rope_inverse(float16_t (&g)[2], const int64_t
             turn *= ratio;
         }
     }
-}
-
-// delta[b,h,q] = sum_d dO[q,d] * O[q,d]
-__global__ void attn_delta_kernel(AttnBwdParams p) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t total = (int64_t)p.B * p.H * p.Nq;
-    if (idx >= total) return;
-    const int q = (int)(idx % p.Nq);
-    const int h = (int)((idx / p.Nq) % p.H);
-    const int b = (int)(idx / ((int64_t)p.Nq * p.H));
-    const bf16_t* o = p.O + (int64_t)b * p.o_sb + (int64_t)q * p.o_sn + (int64_t)h * p.o_sh;
-    const bf16_t* d = p.dO + (int64_t)b * p.o_sb + (int64_t)q * p.o_sn + (int64_t)h * p.o_sh;
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const uint4 a = *reinterpret_cast<const uint4*>(o + c * 8);
-        const uint4 g = *reinterpret_cast<const uint4*>(d + c * 8);
-        const unsigned* au = reinterpret_cast<const unsigned*>(&a);
-        const unsigned* gu = reinterpret_cast<const unsigned*>(&g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            s += __uint_as_float(au[e] << 16) * __uint_as_float(gu[e] << 16);
-            s += __uint_as_float(au[e] & 0xffff0000u) * __uint_as_float(gu[e] & 0xffff0000u);
-        }
-    }
-    p.delta[idx] = s;
 }
 
 // =================================================================================================================
@@ -498,42 +473,26 @@ static int attention_bwd_impl(const void* Q, const void* K, const void* V, const
     p.rope_turn0 = rope_qpos ? (float)((double)rope_f0 / 6.283185307179586476925) : 0.f;
     p.rope_ratio = rope_qpos ? (float)pow((double)rope_base, -1.0 / 16.0) : 1.f;
     p.drop = drop;
-    hipStream_t st = (hipStream_t)stream;
-    if (drop.thr) {      // attention dropout: the 32-row kernels with the forward's mask re-evaluated per element
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, dim3((unsigned)(((Nq + 127) / 128) * H * B)), dim3(256), 0, st, p);
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, dim3((unsigned)(((Nk + 127) / 128) * H * B)), dim3(256), 0, st, p);
-        UC_CHECK_LAUNCH("uc_attention_bwd_drop");
-        return UC_OK;
-    }
-    const int64_t total = (int64_t)B * H * Nq;
-    (void)total;      // (delta is computed by the dQ kernel since round 4; attn_delta_kernel remains for reference)
+    // the knob snapshot: uc_knobs() first (it stores the environment's initial values of the run-time switchable ones)
     (void)uc_knobs();
-    const int k64 = g_uc_attn_bwd64.load();
-    const int64_t v_ext = ((int64_t)(B - 1) * v_sb + (int64_t)(H - 1) * v_sh + (int64_t)(Nk - 1) * v_sn + 64) * 2;
-    // 64 queries per wave (attention_bwd64.h) when a 256-query workgroup is mostly real queries; the 32-query kernel otherwise
-    const bool dq64 = Nk > 64 && v_ext < (int64_t)0xffffffffll && (k64 == 2 || (k64 == 1 && Nq >= 192 && ((Nq + 255) / 256) * 256 * 3 <= Nq * 4));
-    if (dq64) {
-        const int64_t items = (int64_t)((Nq + 255) / 256) * H * B;
-        const int grid = (int)min((int64_t)(uc_num_cus() / 8 * 8), (items + 7) / 8 * 8);
-        hipLaunchKernelGGL(attn_bwd_dq64_kernel, dim3((unsigned)grid), dim3(256), 0, st, p);
-    } else hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, dim3((unsigned)(((Nq + 127) / 128) * H * B)), dim3(256), 0, st, p);
-    // 64 keys per wave (attention_bwd64.h) when a 256-key workgroup is mostly real keys; the 32-key kernel otherwise
-    // (its Q / dO / scratch descriptors span the whole tensors: 32-bit byte offsets)
-    const int64_t q_ext = ((int64_t)(B - 1) * q_sb + (int64_t)(H - 1) * q_sh + (int64_t)(Nq - 1) * q_sn + 64) * 2;
-    const int64_t o_ext = ((int64_t)(B - 1) * o_sb + (int64_t)(H - 1) * o_sh + (int64_t)(Nq - 1) * o_sn + 64) * 2;
-    const bool fits32 = q_ext < (int64_t)0xffffffffll && o_ext < (int64_t)0xffffffffll && (int64_t)B * H * 2 * p.nq_pad * 4 < (int64_t)0xffffffffll;
-    // query rows past Nq of a (batch, head) are read through those descriptors and must be FINITE (their P is exp2(-1e30 + s) = 0): true
-    // when the next batch's rows follow directly (or the tensor ends: zero fill), not when a strided view leaves a gap of foreign memory
-    // between batches — such views take the 32-key kernel, whose loads are bounded per (batch, head)
-    const bool rows_follow = B == 1 || (q_sb == (int64_t)Nq * q_sn && o_sb == (int64_t)Nq * o_sn);
-    const bool use64 = Nq > 64 && fits32 && rows_follow && (k64 == 2 || (k64 == 1 && Nk >= 192 && ((Nk + 255) / 256) * 256 * 3 <= Nk * 4));
-    if (use64) {      // persistent: one workgroup per CU, workgroup g on XCD g % 8
-        const int64_t items = (int64_t)((Nk + 255) / 256) * H * B;
-        const int grid = (int)min((int64_t)(uc_num_cus() / 8 * 8), (items + 7) / 8 * 8);
-        hipLaunchKernelGGL(attn_bwd_dkv64_kernel, dim3((unsigned)grid), dim3(256), 0, st, p);
+    AttnKnobs knobs = {};
+    knobs.bwd64 = g_uc_attn_bwd64.load(std::memory_order_relaxed);
+    knobs.cus = uc_num_cus();
+    const AttnBwdDesc desc = {B, H, Nq, Nk, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh, drop.thr != 0};
+    const AttnBwdPlan plan = uc_attention_bwd_plan(desc, knobs);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 gq(plan.dq_grid), gkv(plan.dkv_grid), block(256);
+    switch (plan.dq) {
+        case UC_AB_DQ32: hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, gq, block, 0, st, p); break;
+        case UC_AB_DQ64: hipLaunchKernelGGL(attn_bwd_dq64_kernel, gq, block, 0, st, p); break;
+        case UC_AB_DQ32_DROP: hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, gq, block, 0, st, p); break;
     }
-    else hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, dim3((unsigned)(((Nk + 127) / 128) * H * B)), dim3(256), 0, st, p);
-    UC_CHECK_LAUNCH("uc_attention_bwd");
+    switch (plan.dkv) {
+        case UC_AB_DKV32: hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, gkv, block, 0, st, p); break;
+        case UC_AB_DKV64: hipLaunchKernelGGL(attn_bwd_dkv64_kernel, gkv, block, 0, st, p); break;
+        case UC_AB_DKV32_DROP: hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, gkv, block, 0, st, p); break;
+    }
+    UC_CHECK_LAUNCH(desc.drop ? "uc_attention_bwd_drop" : "uc_attention_bwd");
     return UC_OK;
 }
 

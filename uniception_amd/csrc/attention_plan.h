@@ -1,0 +1,181 @@
+// Routing of one attention forward / backward launch (uc_attention_fwd[_drop], uc_attention_bwd[_drop]): which kernel, grid and
+// workgroup size a launch gets.
+//
+// Host-only, header-only and pure: no HIP header and no global state, so the system C++ compiler builds it
+// (tests/test_attention_plan.py).  The entry points read every knob once into an AttnKnobs snapshot and call the plan once; they
+// carry it out and decide nothing.  A knob switched at run time (uc_tuning_set) therefore takes effect between launches, never
+// inside one.
+#pragma once
+#include <stdint.h>
+#include "../../include/uc_hip.h"
+
+enum AttnFwdKernel {
+    UC_AF_REG128,        // attn_bf16_kernel: register-staged, 128 queries per workgroup, grid (query tiles, H, B)
+    UC_AF_DMA4,          // attn_bf16_dma_kernel<4>: LDS-DMA staged, 128 queries per workgroup, 1-D grid
+    UC_AF_DMA8,          // attn_bf16_dma_kernel<8>: 256 queries per workgroup
+    UC_AF_RS8,           // attn_bf16_rs_kernel: the eight-wave kernel as role-split segments
+    UC_AF_P64,           // attn_bf16_p64_kernel<false> (persistent, 64 queries per wave) + attn_bf16_fixup_kernel
+    UC_AF_P64_TAIL,      // attn_bf16_p64_kernel<true>: the same with a partial last key tile
+    UC_AF_REG128_DROP,   // attn_bf16_drop_kernel: attn_bf16_kernel with dropout of the probabilities
+    UC_AF_F32_32,        // attn_f32_kernel<32>: fp32 verification kernel, head_dim <= 32
+    UC_AF_F32_64,        // attn_f32_kernel<64>: head_dim <= 64
+    UC_AF_F32_32_DROP,   // attn_f32_kernel<32, true>
+    UC_AF_F32_64_DROP,   // attn_f32_kernel<64, true>
+    UC_AF_DMA4_DBG,      // attn_bf16_dma_kernel<4, dbg>: diag build only (UC_ATTN_DBG, wrong results)
+};
+
+enum AttnDqKernel {
+    UC_AB_DQ32,          // attn_bwd_dq_kernel<false>: 128 queries (4 waves x 32) per workgroup
+    UC_AB_DQ64,          // attn_bwd_dq64_kernel: persistent, 64 queries per wave
+    UC_AB_DQ32_DROP,     // attn_bwd_dq_kernel<true>
+};
+
+enum AttnDkvKernel {
+    UC_AB_DKV32,         // attn_bwd_dkv_kernel<false>: 128 keys per workgroup
+    UC_AB_DKV64,         // attn_bwd_dkv64_kernel: persistent, 64 keys per wave
+    UC_AB_DKV32_DROP,    // attn_bwd_dkv_kernel<true>
+};
+
+// every knob the routing reads, read once per launch
+struct AttnKnobs {
+    int p64;          // persistent 64-queries-per-wave forward: 0 never, 1 where the launch has enough items, 2 wherever the shape allows
+    int bwd64;        // 64-rows-per-wave backward kernels: 0 never, 1 where a workgroup's rows are mostly real, 2 always
+    int role_split;   // eight-wave forward as role-split segments: 0 / 1
+    int cus;          // compute units of the device
+    int dbg;          // UC_ATTN_DBG anatomy switches (diag build only; 0 in the release build)
+};
+
+// the arguments of a forward launch the routing looks at (not ABI)
+struct AttnFwdDesc {
+    int dtype, v_layout;
+    int B, H, Nq, Nk, D;
+    int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+    uintptr_t O;      // the output's address (for its alignment)
+    bool drop;        // dropout of the probabilities (drop_p > 0)
+};
+
+struct AttnBwdDesc {
+    int B, H, Nq, Nk;
+    int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+    bool drop;
+};
+
+struct AttnFwdPlan {
+    AttnFwdKernel kernel;
+    unsigned grid[3];   // x, y, z
+    int block;          // threads per workgroup
+    int nqt;            // query tiles per (batch, head) of the DMA kernels (AttnParams dGroup / dNq; bf16 without dropout, else 0)
+    int fixup_grid;     // attn_bf16_fixup_kernel's grid (P64 / P64_TAIL)
+    int dbg;            // the anatomy switches of UC_AF_DMA4_DBG
+};
+
+struct AttnBwdPlan {
+    AttnDqKernel dq;
+    AttnDkvKernel dkv;
+    unsigned dq_grid, dkv_grid;   // 1-D grids, 256 threads per workgroup
+};
+
+static inline AttnFwdPlan uc_attention_fwd_plan(const AttnFwdDesc& d, const AttnKnobs& k) {
+    AttnFwdPlan plan = {};
+    plan.block = 256;
+    // the grid of the register-staged and fp32 kernels: one workgroup per 128 queries of a (batch, head)
+    plan.grid[0] = (unsigned)((d.Nq + 127) / 128); plan.grid[1] = (unsigned)d.H; plan.grid[2] = (unsigned)d.B;
+    if (d.dtype == UC_F32) {
+        plan.kernel = d.D <= 32 ? (d.drop ? UC_AF_F32_32_DROP : UC_AF_F32_32) : (d.drop ? UC_AF_F32_64_DROP : UC_AF_F32_64);
+        plan.block = 128;
+        return plan;
+    }
+    if (d.drop) {   // bf16 with dropout: the register-staged kernel with the mask between the softmax and the second product
+        plan.kernel = UC_AF_REG128_DROP;
+        return plan;
+    }
+    const int Nq = d.Nq, Nk = d.Nk, H = d.H, B = d.B;
+    const int npad = (Nk + 63) / 64 * 64;
+    // eight waves per workgroup (256 queries share each K / VT tile) when that does not add a mostly empty query tile
+    const int waste8 = (Nq + 255) / 256 * 256 - Nq, waste4 = (Nq + 127) / 128 * 128 - Nq;
+    // (a launch whose 256-query tiles would not give every CU two workgroups takes 128-query tiles: one pair of 512 x 512 views is
+    //  128 tiles of 256 queries — half the chip idle — or 256 of 128)
+    const bool few8 = (int64_t)((Nq + 255) / 256) * H * B < 2 * (int64_t)k.cus;
+    // (the diag build's anatomy switches exist in the four-wave kernel only)
+    const int nw = !k.dbg && Nq >= 256 && waste8 - waste4 < 64 && !few8 ? 8 : 4;
+    const int qtile = 32 * nw, nqt = (Nq + qtile - 1) / qtile;
+    plan.nqt = nqt;
+    // DMA-staged kernel: whole 64-key tiles, 32-bit byte offsets inside one (batch, head)'s K rows / VT rows
+    const bool dma_ok = (int64_t)nqt * H * B < ((int64_t)1 << 31) && d.O % 16 == 0 && d.o_sb % 8 == 0 && d.o_sn % 8 == 0 && d.o_sh % 8 == 0 &&
+                        (int64_t)32 * d.q_sn * 2 < ((int64_t)1 << 31) && (int64_t)Nk * d.k_sn * 2 < ((int64_t)1 << 31) &&
+                        (int64_t)64 * npad * 2 < ((int64_t)1 << 31);
+    if (!dma_ok) {
+        plan.kernel = UC_AF_REG128;
+        return plan;
+    }
+    plan.grid[0] = (unsigned)(nqt * H * B); plan.grid[1] = plan.grid[2] = 1;
+    plan.block = 64 * nw;
+    if (k.dbg) {
+        plan.kernel = UC_AF_DMA4_DBG;
+        plan.dbg = k.dbg;
+        return plan;
+    }
+    // persistent 64-queries-per-wave kernel (attention_p64.h) + its fix-up scan: 32-bit DMA offsets as above, at least two key
+    // tiles, and (policy) enough (batch, head, 256-query tile) items — one per workgroup of the 2 x 256 (measured break-even: 384 items
+    // at 1024 keys, tools/bench_attention_ab.py; 256 items when an item is 64 key tiles long) —, a query count
+    // that does not leave a quarter of the last tile empty.  (A wanted log-sum-exp is no obstacle: the kernel rounds scale * log2(e) * Q
+    // to bf16, so its scores and LSE carry ~2^-9 of |q| |k| scale — and the backward's dQ kernel rounds Q the same way and recomputes
+    // exactly these scores, the dK / dV kernel rounds K instead: the same noise class either way.)  The role-split kernel vetoes it.
+    const int64_t p64_items = (int64_t)B * H * ((Nq + 255) / 256);
+    const bool p64_ok = k.p64 && !k.role_split && Nk > 64 && p64_items < ((int64_t)1 << 28) && (int64_t)64 * d.q_sn * 2 < ((int64_t)1 << 31) &&
+                        (int64_t)64 * d.o_sn * 2 < ((int64_t)1 << 31) &&
+                        (k.p64 == 2 || ((p64_items >= 512 || (p64_items >= 256 && Nk >= 4096)) && waste8 * 4 <= Nq));
+    if (p64_ok) {
+        plan.kernel = Nk & 63 ? UC_AF_P64_TAIL : UC_AF_P64;
+        // two workgroups per CU in whole groups of 8 (one per XCD), at least 8, at most the items rounded up to 8
+        int64_t grid = 2 * k.cus / 8 * 8;
+        if (grid < 8) grid = 8;
+        const int64_t items8 = (p64_items + 7) / 8 * 8;
+        if (grid > items8) grid = items8;
+        plan.grid[0] = (unsigned)grid;
+        plan.block = 256;
+        const int64_t nblocks = (int64_t)B * H * ((Nq + 63) / 64), fblocks = (nblocks + 255) / 256;   // one thread per 64-query block
+        plan.fixup_grid = (int)(fblocks < k.cus ? fblocks : k.cus);
+        return plan;
+    }
+    plan.kernel = nw == 8 ? (k.role_split ? UC_AF_RS8 : UC_AF_DMA8) : UC_AF_DMA4;
+    return plan;
+}
+
+static inline AttnBwdPlan uc_attention_bwd_plan(const AttnBwdDesc& d, const AttnKnobs& k) {
+    AttnBwdPlan plan = {};
+    const int Nq = d.Nq, Nk = d.Nk, H = d.H, B = d.B;
+    plan.dq_grid = (unsigned)(((Nq + 127) / 128) * H * B);
+    plan.dkv_grid = (unsigned)(((Nk + 127) / 128) * H * B);
+    if (d.drop) {   // attention dropout: the 32-row kernels with the forward's mask re-evaluated per element
+        plan.dq = UC_AB_DQ32_DROP;
+        plan.dkv = UC_AB_DKV32_DROP;
+        return plan;
+    }
+    // the persistent kernels: one workgroup per CU (in whole groups of 8: workgroup g on XCD g % 8), at most the items rounded up to 8
+    auto persistent = [&](int64_t items) {
+        const int64_t g = k.cus / 8 * 8, items8 = (items + 7) / 8 * 8;
+        return (unsigned)(g < items8 ? g : items8);
+    };
+    const int64_t v_ext = ((int64_t)(B - 1) * d.v_sb + (int64_t)(H - 1) * d.v_sh + (int64_t)(Nk - 1) * d.v_sn + 64) * 2;
+    // 64 queries per wave (attention_bwd64.h) when a 256-query workgroup is mostly real queries; the 32-query kernel otherwise
+    const bool dq64 = Nk > 64 && v_ext < (int64_t)0xffffffffll &&
+                      (k.bwd64 == 2 || (k.bwd64 == 1 && Nq >= 192 && ((Nq + 255) / 256) * 256 * 3 <= Nq * 4));
+    plan.dq = dq64 ? UC_AB_DQ64 : UC_AB_DQ32;
+    if (dq64) plan.dq_grid = persistent((int64_t)((Nq + 255) / 256) * H * B);
+    // 64 keys per wave (attention_bwd64.h) when a 256-key workgroup is mostly real keys; the 32-key kernel otherwise
+    // (its Q / dO / scratch descriptors span the whole tensors: 32-bit byte offsets)
+    const int64_t q_ext = ((int64_t)(B - 1) * d.q_sb + (int64_t)(H - 1) * d.q_sh + (int64_t)(Nq - 1) * d.q_sn + 64) * 2;
+    const int64_t o_ext = ((int64_t)(B - 1) * d.o_sb + (int64_t)(H - 1) * d.o_sh + (int64_t)(Nq - 1) * d.o_sn + 64) * 2;
+    const int64_t nq_pad = (Nq + 127) / 128 * 128;
+    const bool fits32 = q_ext < (int64_t)0xffffffffll && o_ext < (int64_t)0xffffffffll && (int64_t)B * H * 2 * nq_pad * 4 < (int64_t)0xffffffffll;
+    // query rows past Nq of a (batch, head) are read through those descriptors and must be FINITE (their P is exp2(-1e30 + s) = 0): true
+    // when the next batch's rows follow directly (or the tensor ends: zero fill), not when a strided view leaves a gap of foreign memory
+    // between batches — such views take the 32-key kernel, whose loads are bounded per (batch, head)
+    const bool rows_follow = B == 1 || (d.q_sb == (int64_t)Nq * d.q_sn && d.o_sb == (int64_t)Nq * d.o_sn);
+    const bool dkv64 = Nq > 64 && fits32 && rows_follow &&
+                       (k.bwd64 == 2 || (k.bwd64 == 1 && Nk >= 192 && ((Nk + 255) / 256) * 256 * 3 <= Nk * 4));
+    plan.dkv = dkv64 ? UC_AB_DKV64 : UC_AB_DKV32;
+    if (dkv64) plan.dkv_grid = persistent((int64_t)((Nk + 255) / 256) * H * B);
+    return plan;
+}
