@@ -41,7 +41,7 @@ enum uc_status {
 
 /* Text of the last error on the calling thread ("" if none). */
 const char* uc_last_error(void);
-/* ABI version; bumped when a signature or the uc_gemm_desc layout changes.
+/* ABI version; bumped when a signature or a descriptor layout changes.
  *   1: forward path.  2: training entry points, uc_gemm_desc gained preact_out / split_k / dact_u, uc_attention_fwd gained lse,
  *      fp8 attention, DINOv2 token ops.  3: uc_attention_fwd_fp8_k8, uc_k_pack_fp8 added.  4/5: see INTEGRATION.md.
  *   6: uc_adaptor_program_bwd added.  7: uc_build_flavor, uc_tuning_set / uc_tuning_get (environment knobs read once; no
@@ -52,9 +52,11 @@ const char* uc_last_error(void);
  *       small-M path, uc_gemm_fuse_ws_bytes): the library no longer allocates.
  *   12: uc_swiglu / uc_swiglu_bwd added (DINOv2 giant's SwiGLU FFN); tuning knob conv_rows takes 3 (eight-wave row-walking 3x3
  *       convolution wherever the shape allows).
- *   14 (round 6): attention dropout — uc_attention_fwd_drop, uc_attention_bwd_drop, uc_attention_bwd_f32_drop, uc_attention_drop_mask
- *       added; tuning knob conv_rows_flat. */
-#define UC_ABI_VERSION 14
+ *   14 (round 6): attention dropout — three dropout twins of the attention entry points, uc_attention_drop_mask added; tuning knob
+ *       conv_rows_flat.
+ *   15: uc_attention_fwd / uc_attention_bwd take one descriptor each (uc_attention_desc, uc_attention_bwd_desc): dtype selects bf16 or
+ *       fp32, drop_p > 0 dropout; the fp32 backward and the three dropout twins are gone. */
+#define UC_ABI_VERSION 15
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -247,7 +249,7 @@ int uc_attention_fwd_x3(const float* Q, const float* K, const float* V, float* O
  *  own; all NULL / 0: Q and K are taken as they are.) */
 
 /* ------------------------------------------------------------------------------------
- * Scaled-dot-product attention, no mask, no dropout:  O = softmax(Q K^T * scale) V
+ * Scaled-dot-product attention, no mask:  O = softmax(Q K^T * scale) V  (dropout of the probabilities: drop_p, see below)
  *   (F.scaled_dot_product_attention call sites: libs/croco/blocks.py:123-125,
  *    utils/transformer_blocks.py:244-246, 373-375).
  * Element addressing (d contiguous):  Q[b*q_sb + n*q_sn + h*q_sh + d], same for K and O, so
@@ -268,12 +270,22 @@ int uc_attention_fwd_x3(const float* Q, const float* K, const float* V, float* O
  * ---------------------------------------------------------------------------------- */
 enum uc_v_layout { UC_V_ROWMAJOR = 0, UC_V_PACKED_T = 1 };
 
-int uc_attention_fwd(const void* Q, const void* K, const void* V, void* O, int dtype, int v_layout,
-                     int B, int H, int Nq, int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh,
-                     int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn,
-                     int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale,
-                     float* lse /* optional fp32 [B,H,Nq]: log-sum-exp of the scaled scores, saved for the backward */,
-                     uc_stream_t stream);
+typedef struct uc_attention_desc {
+    int dtype;           /* UC_BF16 (packed VT, head_dim 64) or UC_F32 (row-major V, head_dim <= 64) */
+    int v_layout;        /* uc_v_layout */
+    int B, H, Nq, Nk, D;
+    const void* Q;
+    const void* K;
+    const void* V;
+    void* O;
+    int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+    float scale;
+    float* lse;          /* optional fp32 [B,H,Nq]: log-sum-exp of the scaled scores, saved for the backward */
+    float drop_p;        /* dropout of the probabilities (see "Attention dropout" below), in [0, 1); 0: none */
+    unsigned long long seed;   /* the dropout's seed (ignored when drop_p == 0) */
+} uc_attention_desc;
+
+int uc_attention_fwd(const uc_attention_desc* desc, uc_stream_t stream);
 
 /* FP8 attention forward (BASELINE config 5): same contract as uc_attention_fwd with UC_BF16 operands and D == 64, but both
  * products run on the K=64 block-scaled e4m3 MFMA (unit scales).  Q, K: bf16 strided views (converted to e4m3 inside the
@@ -495,23 +507,39 @@ int uc_pixel_unshuffle(const float* src, void* dst, int dst_dtype, int B, int h,
 int uc_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
              float weight_decay, int step, float grad_scale, uc_stream_t stream);
 
-/* Attention backward (forward: uc_attention_fwd, which must have been called with a non-NULL lse).
- *   inputs : Q,K,V,O,dO as [B,N,H,64] strided views (bf16; dO addressed with O's strides), LSE fp32 [B,H,Nq] (natural log of
- *            the softmax denominator of the scaled scores);
- *   outputs: dQ [B,Nq,H,64], dK, dV [B,Nk,H,64] bf16 (own strides, e.g. slices of one fused dqkv buffer).
- *   delta is fp32 scratch of 2 * B * H * (Nq rounded up to 128) floats (ABI 13; before: B * H * Nq): per (batch, head) the dQ kernel
- *   leaves -LSE * log2(e) (absent queries: -1e30) and -rowsum(dO*O) (0) there, the dK / dV kernel starts its accumulators from them.
- *   All operands are row-major: the transposed MFMA operands are formed inside the kernels with LDS transpose-reads.
- *   rope_qpos / rope_kpos (both or neither; int64 [B*Nq,2] / [B*Nk,2] (y,x)): Q and K were rotated by RoPE-2D (base, F0) before the
- *   forward — dQ and dK are then returned as gradients of the UN-rotated q / k (the inverse rotation rides in the kernels' epilogues
- *   instead of two uc_rope2d passes).  NULL: gradients of the rotated operands. */
-int uc_attention_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
-                     void* dQ, void* dK, void* dV, float* delta, int B, int H, int Nq, int Nk, int64_t q_sb, int64_t q_sn,
-                     int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh,
-                     int64_t o_sb, int64_t o_sn, int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh, int64_t dk_sb,
-                     int64_t dk_sn, int64_t dk_sh, int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale,
-                     const int64_t* rope_qpos, const int64_t* rope_kpos, float rope_base, float rope_f0,
-                     uc_stream_t stream);
+/* Attention backward (forward: uc_attention_fwd, which must have been called with a non-NULL lse), bf16 or fp32.
+ *   bf16: Q,K,V,O,dO as [B,N,H,64] strided views, dQ [B,Nq,H,64], dK, dV [B,Nk,H,64] (own strides, e.g. slices of one fused dqkv
+ *   buffer).  All operands are row-major: the transposed MFMA operands are formed inside the kernels with LDS transpose-reads.
+ *   fp32 (verification mode): the same math on row-major fp32 operands, head_dim D <= 64, no packed transposes needed; no RoPE. */
+typedef struct uc_attention_bwd_desc {
+    int dtype;           /* UC_BF16 (D == 64) or UC_F32 (D <= 64) */
+    int B, H, Nq, Nk, D;
+    const void* Q;
+    const void* K;
+    const void* V;
+    const void* O;       /* the forward's output (with dropout: the dropped one) */
+    const void* dO;      /* addressed with O's strides */
+    const float* LSE;    /* fp32 [B,H,Nq]: natural log of the softmax denominator of the (undropped) scaled scores */
+    void* dQ;
+    void* dK;
+    void* dV;
+    float* delta;        /* fp32 scratch.  bf16: 2 * B * H * (Nq rounded up to 128) floats (ABI 13; before: B * H * Nq): per (batch, head)
+                            the dQ kernel leaves -LSE * log2(e) (absent queries: -1e30) and -rowsum(dO*O) (0) there, the dK / dV kernel
+                            starts its accumulators from them.  fp32: [B,H,Nq] */
+    int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+    int64_t dq_sb, dq_sn, dq_sh, dk_sb, dk_sn, dk_sh, dv_sb, dv_sn, dv_sh;
+    float scale;
+    /* rope_qpos / rope_kpos (bf16 only; both or neither; int64 [B*Nq,2] / [B*Nk,2] (y,x)): Q and K were rotated by RoPE-2D (rope_base,
+       rope_f0) before the forward — dQ and dK are then returned as gradients of the UN-rotated q / k (the inverse rotation rides in the
+       kernels' epilogues instead of two uc_rope2d passes).  NULL: gradients of the rotated operands. */
+    const int64_t* rope_qpos;
+    const int64_t* rope_kpos;
+    float rope_base, rope_f0;
+    float drop_p;        /* the forward's dropout (drop_p, seed); drop_p 0: none */
+    unsigned long long seed;
+} uc_attention_bwd_desc;
+
+int uc_attention_bwd(const uc_attention_bwd_desc* desc, uc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * DPT head backward helpers (forward ops: uc_bilinear_nhwc, uc_convt_scatter, uc_gemm conv mode, uc_conv1x1_to4).
@@ -541,39 +569,10 @@ int uc_conv1x1_to4_bwd(const void* feat, int dtype, const float* w, const float*
  * No mask is stored: whether probability (b, h, q, k) is kept is a counter-based hash of (seed, b * H + h, q, k) against
  * round(drop_p * 2^32), evaluated identically by the forward kernel, by both backward kernels (which rebuild P from the LSE) and by
  * uc_attention_drop_mask.  O = (P o mask / (1 - drop_p)) V; the LSE written is that of the undropped scores.  drop_p in [0, 1).
+ * uc_attention_fwd / uc_attention_bwd with desc->drop_p > 0: bf16 (packed VT, head_dim 64) and fp32 (row-major V, head_dim <= 64).
  * ---------------------------------------------------------------------------------- */
-/* uc_attention_fwd's argument list + (drop_p, seed).  bf16 (packed VT, head_dim 64) and fp32 (row-major V, head_dim <= 64). */
-int uc_attention_fwd_drop(const void* Q, const void* K, const void* V, void* O, int dtype, int v_layout, int B, int H, int Nq,
-                          int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh,
-                          int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale,
-                          float* lse, float drop_p, unsigned long long seed, uc_stream_t stream);
-/* uc_attention_bwd's argument list + the forward's (drop_p, seed); O is the forward's (dropped) output. */
-int uc_attention_bwd_drop(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
-                          void* dQ, void* dK, void* dV, float* delta, int B, int H, int Nq, int Nk, int64_t q_sb, int64_t q_sn,
-                          int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh,
-                          int64_t o_sb, int64_t o_sn, int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh, int64_t dk_sb,
-                          int64_t dk_sn, int64_t dk_sh, int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale,
-                          const int64_t* rope_qpos, const int64_t* rope_kpos, float rope_base, float rope_f0, float drop_p,
-                          unsigned long long seed, uc_stream_t stream);
-/* uc_attention_bwd_f32's argument list + the forward's (drop_p, seed). */
-int uc_attention_bwd_f32_drop(const float* Q, const float* K, const float* V, const float* O, const float* dO,
-                              const float* LSE, float* dQ, float* dK, float* dV, float* delta, int B, int H, int Nq, int Nk,
-                              int D, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh,
-                              int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh,
-                              int64_t dq_sb, int64_t dq_sn, int64_t dq_sh, int64_t dk_sb, int64_t dk_sn, int64_t dk_sh,
-                              int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale, float drop_p, unsigned long long seed,
-                              uc_stream_t stream);
 /* The keep mask those kernels apply, as bytes [B, H, Nq, Nk] (1 = kept): for reference implementations and tests. */
 int uc_attention_drop_mask(void* mask, int B, int H, int Nq, int Nk, float drop_p, unsigned long long seed, uc_stream_t stream);
-
-/* fp32 verification-mode attention backward: same math, row-major fp32 operands (head_dim D <= 64), no packed
- * transposes needed.  delta fp32 [B,H,Nq] is scratch. */
-int uc_attention_bwd_f32(const float* Q, const float* K, const float* V, const float* O, const float* dO,
-                         const float* LSE, float* dQ, float* dK, float* dV, float* delta, int B, int H, int Nq, int Nk,
-                         int D, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh,
-                         int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh,
-                         int64_t dq_sb, int64_t dq_sn, int64_t dq_sh, int64_t dk_sb, int64_t dk_sn, int64_t dk_sh,
-                         int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale, uc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -78,21 +78,48 @@ def test_release_library_allocates_nothing():
     assert "void* fuse_ws;" in hdr and "uc_gemm_fuse_ws_bytes" in hdr
 
 
-def test_gemm_descriptor_layout_matches_header():
-    """Field order of the ctypes mirror == field order of struct uc_gemm_desc."""
-    from uniception_amd._lib import GemmDesc
+# C type of a descriptor field -> the ctypes types its mirror may declare (pointers of any kind: c_void_p)
+_CTYPES = {"int": (ctypes.c_int,), "int64_t": (ctypes.c_int64,), "float": (ctypes.c_float,),
+           "unsigned long long": (ctypes.c_ulonglong, ctypes.c_uint64), "*": (ctypes.c_void_p,)}
 
+
+def header_struct_fields(name):
+    """[(field, C type)] of `typedef struct NAME {...} NAME;` in uc_hip.h, pointers as '*'."""
     text = open(HEADER).read()
-    body = re.search(r"typedef struct uc_gemm_desc \{(.*?)\} uc_gemm_desc;", text, flags=re.S).group(1)
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
+    fields = []
     for decl in body.split(";"):
         decl = decl.strip()
         if not decl:
             continue
-        decl = re.sub(r"^(const\s+)?(void|float|int64_t|int)\s*\*?\s*", "", decl)
-        names += [n.strip().lstrip("*").strip() for n in decl.split(",")]
-    assert names == [f[0] for f in GemmDesc._fields_]
+        m = re.match(r"^(?:const\s+)?(void|float|int64_t|int|unsigned long long)\s*(\*?)\s*(.*)$", decl, flags=re.S)
+        assert m, f"{name}: unparsed field declaration {decl!r}"
+        for n in m.group(3).split(","):
+            n = n.strip()
+            fields.append((n.lstrip("*").strip(), "*" if m.group(2) or n.startswith("*") else m.group(1)))
+    return fields
+
+
+def check_descriptor_layout(struct, mirror):
+    """Field order, names and types of a ctypes mirror == those of the C descriptor (an int64_t stride mirrored as c_int fails)."""
+    from uniception_amd import _lib
+
+    fields = header_struct_fields(struct)
+    mirrored = getattr(_lib, mirror)._fields_
+    assert [n for n, _ in fields] == [n for n, _ in mirrored]
+    wrong = [(n, ctype, t.__name__) for (n, ctype), (_, t) in zip(fields, mirrored) if t not in _CTYPES[ctype]]
+    assert not wrong, wrong
+
+
+def test_gemm_descriptor_layout_matches_header():
+    """Field order (and types) of the ctypes mirror == those of struct uc_gemm_desc."""
+    check_descriptor_layout("uc_gemm_desc", "GemmDesc")
+
+
+@pytest.mark.parametrize("struct,mirror", [("uc_attention_desc", "AttnDesc"), ("uc_attention_bwd_desc", "AttnBwdDesc")])
+def test_attention_descriptor_layout_matches_header(struct, mirror):
+    check_descriptor_layout(struct, mirror)
 
 
 def test_product_path_fails_loudly_without_gpu():
@@ -153,3 +180,31 @@ def test_package_reaches_no_vendor_blas():
                     if pat.search(code) and not code.lstrip().startswith(('"', "'")):
                         hits.append(f"{os.path.relpath(os.path.join(d, f), root)}:{i}: {line.strip()}")
     assert not hits, hits
+
+
+def test_attention_descriptors_are_checked_before_any_launch():
+    """uc_attention_fwd / uc_attention_bwd reject a bad descriptor with their own message before they touch the device (the pointers
+    below are never dereferenced): the fp32 backward has no RoPE form, the bf16 backward only head_dim 64, drop_p lies in [0, 1)."""
+    import ctypes as C
+    from uniception_amd import _lib
+
+    lib = _lib.load()
+
+    def bwd(**kw):
+        d = _lib.AttnBwdDesc(dtype=_lib.UC_F32, B=1, H=1, Nq=8, Nk=8, D=32, scale=1.0)
+        for n in ("Q", "K", "V", "O", "dO", "LSE", "dQ", "dK", "dV", "delta"):
+            setattr(d, n, 4096)
+        for n, v in kw.items():
+            setattr(d, n, v)
+        return lib.uc_attention_bwd(C.byref(d), None), lib.uc_last_error().decode()
+
+    status, msg = bwd(rope_qpos=4096, rope_kpos=4096, rope_base=100.0, rope_f0=1.0)
+    assert status != 0 and msg.startswith("uc_attention_bwd(f32)") and "RoPE" in msg, msg
+    status, msg = bwd(dtype=_lib.UC_BF16)
+    assert status != 0 and "head_dim must be 64" in msg, msg
+    status, msg = bwd(drop_p=1.0)
+    assert status != 0 and "drop_p" in msg, msg
+    status, msg = bwd(dtype=_lib.UC_F16)
+    assert status != 0 and "unsupported dtype" in msg, msg
+    d = _lib.AttnDesc(dtype=_lib.UC_F32, B=1, H=1, Nq=8, Nk=8, D=32, Q=4096, K=4096, V=4096, O=4096, scale=1.0, drop_p=-0.5)
+    assert lib.uc_attention_fwd(C.byref(d), None) != 0 and lib.uc_last_error().decode().startswith("uc_attention_fwd: drop_p")

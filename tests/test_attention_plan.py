@@ -3,8 +3,8 @@ launch gets.
 
 tests/attention_plan_driver.cpp is compiled with the system C++ compiler against the host-only header and fed one descriptor + knob
 snapshot per line.  Expected plans: forward `kernel grid_x grid_y grid_z block nqt fixup_grid`, backward `dq dq_grid dkv dkv_grid`,
-as the routing had them when it was written inline in uc_attention_fwd and attention_bwd_impl; the bench rows agree with the kernel
-traces of the bench configurations.  O is an integer address: 4096 is 256-byte aligned, 4104 8-byte aligned."""
+as the routing had them when it was written inline in uc_attention_fwd, attention_bwd_impl and attention_bwd_f32_impl; the bench rows
+agree with the kernel traces of the bench configurations.  O is an integer address: 4096 is 256-byte aligned, 4104 8-byte aligned."""
 import json
 import os
 import shutil
@@ -31,7 +31,7 @@ def fwd(B, H, Nq, Nk=None, dtype=BF16, D=64, **kw):
 
 
 def bwd(B, H, Nq, Nk=None, **kw):
-    """q / O / dO as contiguous [B, Nq, H, 64], k / v as contiguous [B, Nk, H, 64]"""
+    """q / O / dO as contiguous [B, Nq, H, 64], k / v as contiguous [B, Nk, H, 64]; bf16 unless dtype / D say otherwise"""
     Nk = Nq if Nk is None else Nk
     row = dict(fn="bwd", B=B, H=H, Nq=Nq, Nk=Nk, q_sb=Nq * H * 64, q_sn=H * 64, q_sh=64, k_sb=Nk * H * 64, k_sn=H * 64, k_sh=64,
                v_sb=Nk * H * 64, v_sn=H * 64, v_sh=64, o_sb=Nq * H * 64, o_sn=H * 64, o_sh=64)
@@ -113,6 +113,11 @@ BWD_RULES = {
  "fits32_scratch_over": (bwd(1, 65535, 8320, 256, q_sn=8, q_sh=8, o_sn=8, o_sh=8), "dq64 256 dkv32 131070"),
  "v_ext_over": (bwd(1, 16, 1024, 1025, v_sn=2097152, v_sb=1025 * 2097152), "dq32 128 dkv64 80"),
  "drop": (bwd(64, 16, 1024, drop=1), "dq32_drop 8192 dkv32_drop 8192"),
+ # fp32: one workgroup of 128 rows per (row tile, head, batch), the head_dim <= 32 or <= 64 instantiation, the delta pass first
+ "f32_d32": (bwd(2, 4, 300, 200, dtype=F32, D=32), "f32_dq32 3,4,2 f32_dkv32 2,4,2 128 10"),
+ "f32_d33": (bwd(2, 4, 300, 200, dtype=F32, D=33), "f32_dq64 3,4,2 f32_dkv64 2,4,2 128 10"),
+ "f32_d64_drop": (bwd(2, 4, 300, 200, dtype=F32, drop=1), "f32_dq64 3,4,2 f32_dkv64 2,4,2 128 10"),
+ "f32_knobs_ignored": (bwd(1, 1, 1, 129, dtype=F32, D=1, bwd64=2, cus=8), "f32_dq32 1,1,1 f32_dkv32 2,1,1 128 1"),
 }
 
 

@@ -491,14 +491,22 @@ def test_swiglu_gate_and_its_backward(gpu, dtype, tol, M, H):
         ops.swiglu(torch.zeros(4, 12, device=gpu))       # H = 6: not a multiple of 8
 
 
-@pytest.mark.parametrize("dtype,B,H,Nq,Nk,D", [(torch.bfloat16, 2, 3, 200, 136, 64), (torch.bfloat16, 1, 2, 128, 64, 64), (torch.bfloat16, 2, 2, 70, 300, 64),
-                                             (torch.float32, 2, 2, 100, 77, 64), (torch.float32, 1, 3, 33, 50, 32)])
-def test_attention_with_dropout_forward_and_backward(gpu, dtype, B, H, Nq, Nk, D):
-    """uc_attention_fwd_drop / uc_attention_bwd_drop / uc_attention_bwd_f32_drop against fp32 PyTorch autograd over
+_DROP_ROWS = [(torch.bfloat16, 2, 3, 200, 136, 64, 0.3), (torch.bfloat16, 1, 2, 128, 64, 64, 0.3), (torch.bfloat16, 2, 2, 70, 300, 64, 0.3),
+              (torch.float32, 2, 2, 100, 77, 64, 0.3), (torch.float32, 1, 3, 33, 50, 32, 0.3),
+              (torch.float32, 2, 2, 100, 77, 64, 0.0), (torch.float32, 1, 3, 33, 50, 32, 0.0)]
+
+
+# (the dropout rows keep the ids they had before p was a column; the p = 0 rows are the fp32 backward without dropout)
+@pytest.mark.parametrize("dtype,B,H,Nq,Nk,D,p", _DROP_ROWS,
+                         ids=[f"dtype{i}-{B}-{H}-{Nq}-{Nk}-{D}" if p else f"f32_nodrop-{B}-{H}-{Nq}-{Nk}-{D}"
+                              for i, (_, B, H, Nq, Nk, D, p) in enumerate(_DROP_ROWS)])
+def test_attention_with_dropout_forward_and_backward(gpu, dtype, B, H, Nq, Nk, D, p):
+    """uc_attention_fwd / uc_attention_bwd with drop_p > 0 (bf16 and fp32) against fp32 PyTorch autograd over
     softmax(S) o mask / (1 - p) @ V with the mask uc_attention_drop_mask reports: output, LSE (of the UNdropped scores), dQ, dK, dV;
-    ragged query and key counts, strided q / k / v views, the inverse RoPE riding in the bf16 backward as without dropout."""
+    ragged query and key counts, strided q / k / v views, the inverse RoPE riding in the bf16 backward as without dropout.  p = 0:
+    the same checks of the fp32 kernels without dropout (head_dim 32 and 64)."""
     from uniception_amd import ops
-    p, seed = 0.3, 0x1234_5678_9ABC_DEF1
+    seed = 0x1234_5678_9ABC_DEF1
     g = torch.Generator().manual_seed(Nq * 13 + Nk)
     qkv = torch.randn(B, max(Nq, Nk), 3, H, D, generator=g).to(dtype)
     q, k, v = qkv[:, :Nq, 0], qkv[:, :Nk, 1], qkv[:, :Nk, 2]
@@ -524,8 +532,9 @@ def test_attention_with_dropout_forward_and_backward(gpu, dtype, B, H, Nq, Nk, D
     assert rel_l2(dq.cpu().float(), qf.grad) < tol
     assert rel_l2(dk.cpu().float(), kf.grad) < tol
     # another seed is another mask; p = 0 is the plain kernel
-    o2 = ops.attention(qd, kd, ops.vt_pack(vd) if bf else vd, scale, v_packed=bf, dropout=(p, seed + 1))
-    assert rel_l2(o2.float(), o.float()) > 0.1
+    if p:
+        o2 = ops.attention(qd, kd, ops.vt_pack(vd) if bf else vd, scale, v_packed=bf, dropout=(p, seed + 1))
+        assert rel_l2(o2.float(), o.float()) > 0.1
     o0 = ops.attention(qd, kd, ops.vt_pack(vd) if bf else vd, scale, v_packed=bf, dropout=(0.0, seed))
     assert torch.equal(o0, ops.attention(qd, kd, ops.vt_pack(vd) if bf else vd, scale, v_packed=bf))
 

@@ -50,6 +50,30 @@ class GemmDesc(C.Structure):
     ]
 
 
+class AttnDesc(C.Structure):
+    # field order == struct uc_attention_desc in include/uc_hip.h
+    _fields_ = [
+        ("dtype", i32), ("v_layout", i32), ("B", i32), ("H", i32), ("Nq", i32), ("Nk", i32), ("D", i32),
+        ("Q", vp), ("K", vp), ("V", vp), ("O", vp),
+        ("q_sb", i64), ("q_sn", i64), ("q_sh", i64), ("k_sb", i64), ("k_sn", i64), ("k_sh", i64),
+        ("v_sb", i64), ("v_sn", i64), ("v_sh", i64), ("o_sb", i64), ("o_sn", i64), ("o_sh", i64),
+        ("scale", f32), ("lse", vp), ("drop_p", f32), ("seed", u64),
+    ]
+
+
+class AttnBwdDesc(C.Structure):
+    # field order == struct uc_attention_bwd_desc in include/uc_hip.h
+    _fields_ = [
+        ("dtype", i32), ("B", i32), ("H", i32), ("Nq", i32), ("Nk", i32), ("D", i32),
+        ("Q", vp), ("K", vp), ("V", vp), ("O", vp), ("dO", vp), ("LSE", vp), ("dQ", vp), ("dK", vp), ("dV", vp), ("delta", vp),
+        ("q_sb", i64), ("q_sn", i64), ("q_sh", i64), ("k_sb", i64), ("k_sn", i64), ("k_sh", i64),
+        ("v_sb", i64), ("v_sn", i64), ("v_sh", i64), ("o_sb", i64), ("o_sn", i64), ("o_sh", i64),
+        ("dq_sb", i64), ("dq_sn", i64), ("dq_sh", i64), ("dk_sb", i64), ("dk_sn", i64), ("dk_sh", i64),
+        ("dv_sb", i64), ("dv_sn", i64), ("dv_sh", i64),
+        ("scale", f32), ("rope_qpos", vp), ("rope_kpos", vp), ("rope_base", f32), ("rope_f0", f32), ("drop_p", f32), ("seed", u64),
+    ]
+
+
 # name -> argtypes (every function returns int except uc_last_error)
 SIGNATURES = {
     "uc_abi_version": [],
@@ -63,7 +87,7 @@ SIGNATURES = {
     "uc_ln_stats_finalize": [vp, i64, i32, f32, vp, vp],
     "uc_split_bf16x3": [vp, vp, i64, i32, i32, vp],
     "uc_add_view_pe": [vp, vp, i64, i32, i32, i32, i32, vp],
-    "uc_attention_fwd": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32] + [i64] * 12 + [f32, vp, vp],
+    "uc_attention_fwd": [C.POINTER(AttnDesc), vp],
     "uc_attention_x3_workspace_bytes": [i32, i32, i32, i32],
     "uc_gemm_fuse_ws_bytes": [],
     "uc_attention_fwd_x3": [vp, vp, vp, vp, vp, i32, i32, i32, i32] + [i64] * 12 + [f32, vp, vp, vp, vp, i32, vp],
@@ -100,23 +124,19 @@ SIGNATURES = {
     "uc_pointmap_loss": [vp, i64, i64, i64, vp, f32, f32, vp, vp, i32, i32, i32, vp],
     "uc_pixel_unshuffle": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "uc_adamw": [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp],
-    "uc_attention_bwd": [vp] * 10 + [i32] * 4 + [i64] * 21 + [f32, vp, vp, f32, f32, vp],
+    "uc_attention_bwd": [C.POINTER(AttnBwdDesc), vp],
     "uc_bilinear_nhwc_bwd": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "uc_convt_gather": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "uc_im2col_t": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, vp],
     "uc_dilate_nhwc": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "uc_conv1x1_to4_bwd": [vp, i32, vp, vp, vp, vp, vp, i64, i32, i32, vp],
-    "uc_attention_bwd_f32": [vp] * 10 + [i32] * 5 + [i64] * 21 + [f32, vp],
-    "uc_attention_fwd_drop": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32] + [i64] * 12 + [f32, vp, f32, u64, vp],
-    "uc_attention_bwd_drop": [vp] * 10 + [i32] * 4 + [i64] * 21 + [f32, vp, vp, f32, f32, f32, u64, vp],
-    "uc_attention_bwd_f32_drop": [vp] * 10 + [i32] * 5 + [i64] * 21 + [f32, f32, u64, vp],
     "uc_attention_drop_mask": [vp, i32, i32, i32, i32, f32, u64, vp],
 }
 
 _lib = None
 
 
-ABI_VERSION = 14   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 15   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

@@ -369,7 +369,7 @@ def _attention_fwd(q, k, v, scale, lse, dropout=None):
 def attn_dropout(training: bool, p: float):
     """(p, seed) for a sub-layer's attention dropout, or None (eval mode / rate 0).  The seed comes from PyTorch's CPU generator —
     torch.manual_seed reproduces it, and a checkpointed block's re-computation draws the same one (preserve_rng_state) — and keys the
-    counter-based mask the forward and backward kernels evaluate (uc_attention_fwd_drop)."""
+    counter-based mask the forward and backward kernels evaluate (uc_attention_fwd's drop_p / seed)."""
     if not training or p <= 0.0:
         return None
     if p >= 1.0:

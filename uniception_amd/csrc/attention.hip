@@ -33,7 +33,7 @@ struct AttnParams {
     float* lse;   // optional [B,H,Nq]: log-sum-exp of the scaled scores (saved for the backward)
     uc_fastdiv dGroup, dNq, dH;   // exact fast division by 8*nq, nq, H (workgroup -> (query tile, batch, head) in the DMA kernel)
     int prio_young;               // eight-wave workgroups: s_setprio 1 for waves 4-7 (the younger half loses every VALU arbitration to the older one)
-    UcDropout drop;               // attention dropout (uc_attention_fwd_drop; thr 0 elsewhere)
+    UcDropout drop;               // attention dropout (uc_attention_fwd with drop_p > 0; thr 0 elsewhere)
 };
 
 #define KV_TILE 64
@@ -916,7 +916,7 @@ __global__ __launch_bounds__(128) void attn_f32_kernel(AttnParams p) {
     }
 }
 
-// keep mask of uc_attention_fwd_drop / uc_attention_bwd_drop as bytes [B, H, Nq, Nk] (1 = kept): what a reference implementation
+// keep mask of uc_attention_fwd / uc_attention_bwd with drop_p > 0 as bytes [B, H, Nq, Nk] (1 = kept): what a reference implementation
 // multiplies the probabilities with (tests), evaluated by the same function as the kernels
 __global__ void attn_drop_mask_kernel(unsigned char* mask, int H, int Nq, int Nk, int64_t total, UcDropout d) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -954,27 +954,29 @@ static void launch_attn_dma4_dbg(int dbg, dim3 grid, hipStream_t st, const AttnP
 }
 #endif
 
-// uc_attention_fwd and, with drop_p > 0, uc_attention_fwd_drop (`fn`: the entry point the messages name): validate, fill AttnParams,
-// snapshot the knobs, plan the launch (attention_plan.h) and carry the plan out
-static int attention_fwd_impl(const char* fn, const void* Q, const void* K, const void* V, void* O, int dtype, int v_layout,
-                              int B, int H, int Nq, int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh,
-                              int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh,
-                              int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale, float* lse, float drop_p,
-                              unsigned long long seed, uc_stream_t stream) {
-    const bool drop = drop_p != 0.f;
+// uc_attention_fwd: validate, fill AttnParams, snapshot the knobs, plan the launch (attention_plan.h) and carry the plan out
+extern "C" int uc_attention_fwd(const uc_attention_desc* desc, uc_stream_t stream) {
+    UC_REQUIRE(desc, "uc_attention_fwd: null descriptor");
+    const uc_attention_desc& d = *desc;
+    const char* fn = "uc_attention_fwd";
+    const void *Q = d.Q, *K = d.K, *V = d.V;
+    void* O = d.O;
+    const int dtype = d.dtype, B = d.B, H = d.H, Nq = d.Nq, Nk = d.Nk, D = d.D;
+    UC_REQUIRE(d.drop_p >= 0.f && d.drop_p < 1.f, "%s: drop_p must be in [0, 1) (got %g)", fn, (double)d.drop_p);
+    const bool drop = d.drop_p != 0.f;
     UC_REQUIRE(Q && K && V && O, "%s: null pointer", fn);
     UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0, "%s: bad shape", fn);
     UC_REQUIRE(H <= 65535 && B <= 65535, "%s: B and H must fit a grid dimension", fn);
     if (dtype == UC_BF16) {
         UC_REQUIRE(D == 64, "%s(bf16): head_dim must be 64 (got %d)", fn, D);
-        UC_REQUIRE(v_layout == UC_V_PACKED_T, "%s(bf16): V must be in the packed VT layout (uc_vt_pack)", fn);
-        UC_REQUIRE(q_sb % 8 == 0 && q_sn % 8 == 0 && q_sh % 8 == 0 && k_sb % 8 == 0 && k_sn % 8 == 0 && k_sh % 8 == 0,
+        UC_REQUIRE(d.v_layout == UC_V_PACKED_T, "%s(bf16): V must be in the packed VT layout (uc_vt_pack)", fn);
+        UC_REQUIRE(d.q_sb % 8 == 0 && d.q_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sb % 8 == 0 && d.k_sn % 8 == 0 && d.k_sh % 8 == 0,
                    "%s(bf16): Q/K strides must be multiples of 8 elements", fn);
-        UC_REQUIRE(o_sb % 4 == 0 && o_sn % 4 == 0 && o_sh % 4 == 0, "%s(bf16): O strides must be multiples of 4", fn);
+        UC_REQUIRE(d.o_sb % 4 == 0 && d.o_sn % 4 == 0 && d.o_sh % 4 == 0, "%s(bf16): O strides must be multiples of 4", fn);
         UC_REQUIRE(((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0) && ((uintptr_t)O % 8 == 0),
                    "%s(bf16): pointer alignment", fn);
     } else if (dtype == UC_F32) {
-        UC_REQUIRE(v_layout == UC_V_ROWMAJOR, "%s(f32): V must be row-major", fn);
+        UC_REQUIRE(d.v_layout == UC_V_ROWMAJOR, "%s(f32): V must be row-major", fn);
         UC_REQUIRE(D <= 64, "%s(f32): head_dim must be <= 64 (got %d)", fn, D);
     } else {
         uc_set_error("%s: unsupported dtype %d", fn, dtype);
@@ -989,19 +991,17 @@ static int attention_fwd_impl(const char* fn, const void* Q, const void* K, cons
 #ifdef UC_DIAG
     knobs.dbg = kn.attn_dbg;
 #endif
-    const AttnFwdDesc desc = {dtype, v_layout, B, H, Nq, Nk, D, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh,
-                              (uintptr_t)O, drop};
-    const AttnFwdPlan plan = uc_attention_fwd_plan(desc, knobs);
+    const AttnFwdPlan plan = uc_attention_fwd_plan(d, knobs);
 
     AttnParams p;
     p.Q = Q; p.K = K; p.V = V; p.O = O; p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.D = D;
-    p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
-    p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
+    p.q_sb = d.q_sb; p.q_sn = d.q_sn; p.q_sh = d.q_sh; p.k_sb = d.k_sb; p.k_sn = d.k_sn; p.k_sh = d.k_sh;
+    p.v_sb = d.v_sb; p.v_sn = d.v_sn; p.v_sh = d.v_sh; p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh;
     p.npad = (Nk + 63) / 64 * 64;
-    p.scale = scale;
-    p.lse = lse;
+    p.scale = d.scale;
+    p.lse = d.lse;
     p.prio_young = drop ? 0 : kn.attn_prio;
-    p.drop = uc_make_dropout(drop_p, seed);
+    p.drop = uc_make_dropout(drop ? d.drop_p : 0.f, drop ? d.seed : 0ull);
     if (plan.nqt) { p.dGroup = uc_make_fastdiv((unsigned)(8 * plan.nqt)); p.dNq = uc_make_fastdiv((unsigned)plan.nqt); p.dH = uc_make_fastdiv((unsigned)H); }
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(plan.grid[0], plan.grid[1], plan.grid[2]), block(plan.block);
@@ -1013,9 +1013,10 @@ static int attention_fwd_impl(const char* fn, const void* Q, const void* K, cons
         case UC_AF_P64:
         case UC_AF_P64_TAIL: {
             AttnP64Params pp;
-            pp.Q = Q; pp.K = K; pp.V = V; pp.O = O; pp.lse = lse; pp.B = B; pp.H = H; pp.Nq = Nq; pp.Nk = Nk;
-            pp.q_sb = q_sb; pp.q_sn = q_sn; pp.q_sh = q_sh; pp.k_sb = k_sb; pp.k_sn = k_sn; pp.k_sh = k_sh; pp.o_sb = o_sb; pp.o_sn = o_sn; pp.o_sh = o_sh;
-            pp.npad = p.npad; pp.c = scale * 1.44269504088896340736f; pp.q_prescaled = 0;
+            pp.Q = Q; pp.K = K; pp.V = V; pp.O = O; pp.lse = d.lse; pp.B = B; pp.H = H; pp.Nq = Nq; pp.Nk = Nk;
+            pp.q_sb = d.q_sb; pp.q_sn = d.q_sn; pp.q_sh = d.q_sh; pp.k_sb = d.k_sb; pp.k_sn = d.k_sn; pp.k_sh = d.k_sh;
+            pp.o_sb = d.o_sb; pp.o_sn = d.o_sn; pp.o_sh = d.o_sh;
+            pp.npad = p.npad; pp.c = d.scale * 1.44269504088896340736f; pp.q_prescaled = 0;
             pp.nq = (Nq + 255) / 256; pp.dNq = uc_make_fastdiv((unsigned)pp.nq); pp.dH = uc_make_fastdiv((unsigned)H);
             pp.dbg = nullptr;
             if (plan.kernel == UC_AF_P64_TAIL) hipLaunchKernelGGL(attn_bf16_p64_kernel<true>, grid, block, 0, st, pp);
@@ -1037,27 +1038,4 @@ static int attention_fwd_impl(const char* fn, const void* Q, const void* K, cons
     }
     UC_CHECK_LAUNCH(fn);
     return UC_OK;
-}
-
-// Attention forward with dropout of the probabilities (training, attn_drop > 0): the argument list of uc_attention_fwd + (drop_p, seed).
-// bf16: the register-staged 128-query kernel with the mask applied between the softmax and the second product; fp32: the verification
-// kernel.  drop_p == 0 is uc_attention_fwd.
-extern "C" int uc_attention_fwd_drop(const void* Q, const void* K, const void* V, void* O, int dtype, int v_layout,
-                                     int B, int H, int Nq, int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh,
-                                     int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh,
-                                     int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale, float* lse, float drop_p,
-                                     unsigned long long seed, uc_stream_t stream) {
-    UC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "uc_attention_fwd_drop: drop_p must be in [0, 1) (got %g)", (double)drop_p);
-    const bool drop = drop_p != 0.f;
-    return attention_fwd_impl(drop ? "uc_attention_fwd_drop" : "uc_attention_fwd", Q, K, V, O, dtype, v_layout, B, H, Nq, Nk, D, q_sb, q_sn,
-                              q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh, scale, lse, drop ? drop_p : 0.f, drop ? seed : 0ull,
-                              stream);
-}
-
-extern "C" int uc_attention_fwd(const void* Q, const void* K, const void* V, void* O, int dtype, int v_layout,
-                                int B, int H, int Nq, int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh,
-                                int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh,
-                                int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale, float* lse, uc_stream_t stream) {
-    return attention_fwd_impl("uc_attention_fwd", Q, K, V, O, dtype, v_layout, B, H, Nq, Nk, D, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh,
-                              v_sb, v_sn, v_sh, o_sb, o_sn, o_sh, scale, lse, 0.f, 0ull, stream);
 }

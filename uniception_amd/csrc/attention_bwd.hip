@@ -44,7 +44,7 @@ struct AttnBwdParams {
     float rope_turn0;           // F0 / (2 pi): rotation per unit position of channel 0, in turns
     float rope_ratio;           // base^(-1/16)
     unsigned long long* dbg;    // probe builds (-DB64_TIMING): per-workgroup cycle stamps
-    UcDropout drop;             // attention dropout (uc_attention_bwd_drop; thr 0 elsewhere): the forward's mask, re-evaluated
+    UcDropout drop;             // attention dropout (uc_attention_bwd with drop_p > 0; thr 0 elsewhere): the forward's mask, re-evaluated
 };
 
 #define TB (64 * 128)   // bytes of one 64-row tile
@@ -136,7 +136,7 @@ __device__ __forceinline__ void ab_xcd_order(int w, int nt, int nbh, int& tile, 
     else { const int rem = w - (nbh / 8) * 8 * nt; bh = (nbh / 8) * 8 + rem / nt; tile = rem % nt; }
 }
 
-// DROP (attention dropout, uc_attention_bwd_drop): the forward computed O = P' V with P' = P o mask / (1 - p).  dV = P'^T dO;
+// DROP (attention dropout, uc_attention_bwd with drop_p > 0): the forward computed O = P' V with P' = P o mask / (1 - p).  dV = P'^T dO;
 // dP' = dO V^T; dP = dP' o mask / (1 - p); dS = P o (dP - delta) with delta = rowsum(dP o P) = rowsum(dP' o P') = rowsum(dO o O) as
 // without dropout.  The accumulator chain that starts at -delta holds dP' - delta: dS = P ((acc + delta) m - delta), m = mask / (1 - p).
 template <bool DROP = false>
@@ -443,83 +443,54 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
 
 #include "attention_bwd64.h"
 
-static int attention_bwd_impl(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
-                              void* dQ, void* dK, void* dV, float* delta, int B, int H, int Nq, int Nk, int64_t q_sb,
-                              int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn,
-                              int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh,
-                              int64_t dk_sb, int64_t dk_sn, int64_t dk_sh, int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale,
-                              const int64_t* rope_qpos, const int64_t* rope_kpos, float rope_base, float rope_f0, const UcDropout& drop,
-                              uc_stream_t stream) {
-    UC_REQUIRE(Q && K && V && O && dO && LSE && dQ && dK && dV && delta, "uc_attention_bwd: null pointer");
-    UC_REQUIRE((rope_qpos == nullptr) == (rope_kpos == nullptr), "uc_attention_bwd: rope_qpos and rope_kpos go together");
-    UC_REQUIRE(!rope_qpos || (rope_base > 0.f && rope_f0 != 0.f), "uc_attention_bwd: the inverse RoPE needs base > 0 and F0 != 0");
+// the bf16 backward of uc_attention_bwd (which has checked the pointers and drop_p)
+static int attention_bwd_impl(const uc_attention_bwd_desc& d, uc_stream_t stream) {
+    const int B = d.B, H = d.H, Nq = d.Nq, Nk = d.Nk;
+    UC_REQUIRE((d.rope_qpos == nullptr) == (d.rope_kpos == nullptr), "uc_attention_bwd: rope_qpos and rope_kpos go together");
+    UC_REQUIRE(!d.rope_qpos || (d.rope_base > 0.f && d.rope_f0 != 0.f), "uc_attention_bwd: the inverse RoPE needs base > 0 and F0 != 0");
     UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && B <= 65535 && H <= 65535, "uc_attention_bwd: bad shape");
-    UC_REQUIRE(q_sn % 8 == 0 && k_sn % 8 == 0 && v_sn % 8 == 0 && o_sn % 8 == 0 && q_sh % 8 == 0 && k_sh % 8 == 0 && v_sh % 8 == 0 &&
-                   o_sh % 8 == 0 && q_sb % 8 == 0 && k_sb % 8 == 0 && v_sb % 8 == 0 && o_sb % 8 == 0,
+    UC_REQUIRE(d.D == 64, "uc_attention_bwd(bf16): head_dim must be 64 (got %d)", d.D);
+    UC_REQUIRE(d.q_sn % 8 == 0 && d.k_sn % 8 == 0 && d.v_sn % 8 == 0 && d.o_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sh % 8 == 0 &&
+                   d.v_sh % 8 == 0 && d.o_sh % 8 == 0 && d.q_sb % 8 == 0 && d.k_sb % 8 == 0 && d.v_sb % 8 == 0 && d.o_sb % 8 == 0,
                "uc_attention_bwd: input strides must be multiples of 8 elements");
-    UC_REQUIRE(dq_sn % 4 == 0 && dk_sn % 4 == 0 && dv_sn % 4 == 0 && dq_sh % 4 == 0 && dk_sh % 4 == 0 && dv_sh % 4 == 0 &&
-                   dq_sb % 4 == 0 && dk_sb % 4 == 0 && dv_sb % 4 == 0,
+    UC_REQUIRE(d.dq_sn % 4 == 0 && d.dk_sn % 4 == 0 && d.dv_sn % 4 == 0 && d.dq_sh % 4 == 0 && d.dk_sh % 4 == 0 && d.dv_sh % 4 == 0 &&
+                   d.dq_sb % 4 == 0 && d.dk_sb % 4 == 0 && d.dv_sb % 4 == 0,
                "uc_attention_bwd: output strides must be multiples of 4 elements");
     AttnBwdParams p;
-    p.Q = (const bf16_t*)Q; p.K = (const bf16_t*)K; p.V = (const bf16_t*)V; p.O = (const bf16_t*)O; p.dO = (const bf16_t*)dO;
-    p.LSE = LSE; p.delta = delta; p.aux = delta;
+    p.Q = (const bf16_t*)d.Q; p.K = (const bf16_t*)d.K; p.V = (const bf16_t*)d.V; p.O = (const bf16_t*)d.O; p.dO = (const bf16_t*)d.dO;
+    p.LSE = d.LSE; p.delta = d.delta; p.aux = d.delta;
     p.nq_pad = (Nq + 127) / 128 * 128;
-    p.dQ = (bf16_t*)dQ; p.dK = (bf16_t*)dK; p.dV = (bf16_t*)dV;
+    p.dQ = (bf16_t*)d.dQ; p.dK = (bf16_t*)d.dK; p.dV = (bf16_t*)d.dV;
     p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk;
-    p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh; p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh;
-    p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh; p.dq_sb = dq_sb; p.dq_sn = dq_sn; p.dq_sh = dq_sh; p.dk_sb = dk_sb; p.dk_sn = dk_sn;
-    p.dk_sh = dk_sh; p.dv_sb = dv_sb; p.dv_sn = dv_sn; p.dv_sh = dv_sh; p.scale = scale;
-    p.rope_qpos = rope_qpos; p.rope_kpos = rope_kpos; p.dbg = nullptr;
-    p.rope_turn0 = rope_qpos ? (float)((double)rope_f0 / 6.283185307179586476925) : 0.f;
-    p.rope_ratio = rope_qpos ? (float)pow((double)rope_base, -1.0 / 16.0) : 1.f;
-    p.drop = drop;
+    p.q_sb = d.q_sb; p.q_sn = d.q_sn; p.q_sh = d.q_sh; p.k_sb = d.k_sb; p.k_sn = d.k_sn; p.k_sh = d.k_sh; p.v_sb = d.v_sb; p.v_sn = d.v_sn;
+    p.v_sh = d.v_sh; p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh; p.dq_sb = d.dq_sb; p.dq_sn = d.dq_sn; p.dq_sh = d.dq_sh;
+    p.dk_sb = d.dk_sb; p.dk_sn = d.dk_sn; p.dk_sh = d.dk_sh; p.dv_sb = d.dv_sb; p.dv_sn = d.dv_sn; p.dv_sh = d.dv_sh; p.scale = d.scale;
+    p.rope_qpos = d.rope_qpos; p.rope_kpos = d.rope_kpos; p.dbg = nullptr;
+    p.rope_turn0 = d.rope_qpos ? (float)((double)d.rope_f0 / 6.283185307179586476925) : 0.f;
+    p.rope_ratio = d.rope_qpos ? (float)pow((double)d.rope_base, -1.0 / 16.0) : 1.f;
+    p.drop = uc_make_dropout(d.drop_p, d.drop_p != 0.f ? d.seed : 0ull);
     // the knob snapshot: uc_knobs() first (it stores the environment's initial values of the run-time switchable ones)
     (void)uc_knobs();
     AttnKnobs knobs = {};
     knobs.bwd64 = g_uc_attn_bwd64.load(std::memory_order_relaxed);
     knobs.cus = uc_num_cus();
-    const AttnBwdDesc desc = {B, H, Nq, Nk, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh, drop.thr != 0};
-    const AttnBwdPlan plan = uc_attention_bwd_plan(desc, knobs);
+    const AttnBwdPlan plan = uc_attention_bwd_plan(d, knobs);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 gq(plan.dq_grid), gkv(plan.dkv_grid), block(256);
+    const dim3 gq(plan.dq_grid[0]), gkv(plan.dkv_grid[0]), block(plan.block);
     switch (plan.dq) {
         case UC_AB_DQ32: hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, gq, block, 0, st, p); break;
         case UC_AB_DQ64: hipLaunchKernelGGL(attn_bwd_dq64_kernel, gq, block, 0, st, p); break;
         case UC_AB_DQ32_DROP: hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, gq, block, 0, st, p); break;
+        default: break;   // (the fp32 kernels: attention_bwd_f32_impl)
     }
     switch (plan.dkv) {
         case UC_AB_DKV32: hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, gkv, block, 0, st, p); break;
         case UC_AB_DKV64: hipLaunchKernelGGL(attn_bwd_dkv64_kernel, gkv, block, 0, st, p); break;
         case UC_AB_DKV32_DROP: hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, gkv, block, 0, st, p); break;
+        default: break;
     }
-    UC_CHECK_LAUNCH(desc.drop ? "uc_attention_bwd_drop" : "uc_attention_bwd");
+    UC_CHECK_LAUNCH("uc_attention_bwd");
     return UC_OK;
-}
-
-extern "C" int uc_attention_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
-                                void* dQ, void* dK, void* dV, float* delta, int B, int H, int Nq, int Nk, int64_t q_sb,
-                                int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn,
-                                int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh,
-                                int64_t dk_sb, int64_t dk_sn, int64_t dk_sh, int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale,
-                                const int64_t* rope_qpos, const int64_t* rope_kpos, float rope_base, float rope_f0, uc_stream_t stream) {
-    return attention_bwd_impl(Q, K, V, O, dO, LSE, dQ, dK, dV, delta, B, H, Nq, Nk, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh,
-                              o_sb, o_sn, o_sh, dq_sb, dq_sn, dq_sh, dk_sb, dk_sn, dk_sh, dv_sb, dv_sn, dv_sh, scale, rope_qpos, rope_kpos,
-                              rope_base, rope_f0, uc_make_dropout(0.f, 0ull), stream);
-}
-
-// Backward of uc_attention_fwd_drop: uc_attention_bwd's arguments + the forward's (drop_p, seed).  O is the forward's (dropped) output,
-// LSE that of the undropped scores.
-extern "C" int uc_attention_bwd_drop(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
-                                     void* dQ, void* dK, void* dV, float* delta, int B, int H, int Nq, int Nk, int64_t q_sb,
-                                     int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn,
-                                     int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh,
-                                     int64_t dk_sb, int64_t dk_sn, int64_t dk_sh, int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale,
-                                     const int64_t* rope_qpos, const int64_t* rope_kpos, float rope_base, float rope_f0, float drop_p,
-                                     unsigned long long seed, uc_stream_t stream) {
-    UC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "uc_attention_bwd_drop: drop_p must be in [0, 1) (got %g)", (double)drop_p);
-    return attention_bwd_impl(Q, K, V, O, dO, LSE, dQ, dK, dV, delta, B, H, Nq, Nk, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh,
-                              o_sb, o_sn, o_sh, dq_sb, dq_sn, dq_sh, dk_sb, dk_sn, dk_sh, dv_sb, dv_sn, dv_sh, scale, rope_qpos, rope_kpos,
-                              rope_base, rope_f0, uc_make_dropout(drop_p, seed), stream);
 }
 
 // =================================================================================================================
@@ -681,57 +652,47 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_f32_kernel(AttnBwdF32Params 
     }
 }
 
-static int attention_bwd_f32_impl(const float* Q, const float* K, const float* V, const float* O, const float* dO,
-                                  const float* LSE, float* dQ, float* dK, float* dV, float* delta, int B, int H, int Nq,
-                                  int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn,
-                                  int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn,
-                                  int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh, int64_t dk_sb, int64_t dk_sn,
-                                  int64_t dk_sh, int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale, const UcDropout& drop,
-                                  uc_stream_t stream) {
-    UC_REQUIRE(Q && K && V && O && dO && LSE && dQ && dK && dV && delta, "uc_attention_bwd_f32: null pointer");
-    UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0 && D <= 64 && B <= 65535 && H <= 65535, "uc_attention_bwd_f32: bad shape (head_dim <= 64)");
+// the fp32 backward of uc_attention_bwd
+static int attention_bwd_f32_impl(const uc_attention_bwd_desc& d, uc_stream_t stream) {
+    const int B = d.B, H = d.H, Nq = d.Nq, Nk = d.Nk, D = d.D;
+    UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0 && D <= 64 && B <= 65535 && H <= 65535, "uc_attention_bwd(f32): bad shape (head_dim <= 64)");
+    UC_REQUIRE(!d.rope_qpos && !d.rope_kpos, "uc_attention_bwd(f32): the fp32 backward takes no RoPE positions");
     AttnBwdF32Params p;
-    p.Q = Q; p.K = K; p.V = V; p.O = O; p.dO = dO; p.LSE = LSE; p.dQ = dQ; p.dK = dK; p.dV = dV; p.delta = delta;
+    p.Q = (const float*)d.Q; p.K = (const float*)d.K; p.V = (const float*)d.V; p.O = (const float*)d.O; p.dO = (const float*)d.dO;
+    p.LSE = d.LSE; p.dQ = (float*)d.dQ; p.dK = (float*)d.dK; p.dV = (float*)d.dV; p.delta = d.delta;
     p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.D = D;
-    p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh; p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh;
-    p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh; p.dq_sb = dq_sb; p.dq_sn = dq_sn; p.dq_sh = dq_sh; p.dk_sb = dk_sb; p.dk_sn = dk_sn;
-    p.dk_sh = dk_sh; p.dv_sb = dv_sb; p.dv_sn = dv_sn; p.dv_sh = dv_sh; p.scale = scale;
-    p.drop = drop;
+    p.q_sb = d.q_sb; p.q_sn = d.q_sn; p.q_sh = d.q_sh; p.k_sb = d.k_sb; p.k_sn = d.k_sn; p.k_sh = d.k_sh; p.v_sb = d.v_sb; p.v_sn = d.v_sn;
+    p.v_sh = d.v_sh; p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh; p.dq_sb = d.dq_sb; p.dq_sn = d.dq_sn; p.dq_sh = d.dq_sh;
+    p.dk_sb = d.dk_sb; p.dk_sn = d.dk_sn; p.dk_sh = d.dk_sh; p.dv_sb = d.dv_sb; p.dv_sn = d.dv_sn; p.dv_sh = d.dv_sh; p.scale = d.scale;
+    p.drop = uc_make_dropout(d.drop_p, d.drop_p != 0.f ? d.seed : 0ull);
+    const AttnBwdPlan plan = uc_attention_bwd_plan(d, AttnKnobs{});   // (the fp32 routing reads no knob)
     hipStream_t st = (hipStream_t)stream;
-    const int64_t total = (int64_t)B * H * Nq;
-    hipLaunchKernelGGL(attn_delta_f32_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, st, p);
-    if (D <= 32) {
-        hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<32>), dim3((Nq + 127) / 128, H, B), dim3(128), 0, st, p);
-        hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<32>), dim3((Nk + 127) / 128, H, B), dim3(128), 0, st, p);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<64>), dim3((Nq + 127) / 128, H, B), dim3(128), 0, st, p);
-        hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<64>), dim3((Nk + 127) / 128, H, B), dim3(128), 0, st, p);
+    const dim3 gq(plan.dq_grid[0], plan.dq_grid[1], plan.dq_grid[2]), gkv(plan.dkv_grid[0], plan.dkv_grid[1], plan.dkv_grid[2]);
+    const dim3 block(plan.block);
+    hipLaunchKernelGGL(attn_delta_f32_kernel, dim3(plan.delta_grid), dim3(256), 0, st, p);
+    switch (plan.dq) {
+        case UC_AB_F32_DQ32: hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<32>), gq, block, 0, st, p); break;
+        case UC_AB_F32_DQ64: hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<64>), gq, block, 0, st, p); break;
+        default: break;   // (the bf16 kernels: attention_bwd_impl)
     }
-    UC_CHECK_LAUNCH("uc_attention_bwd_f32");
+    switch (plan.dkv) {
+        case UC_AB_F32_DKV32: hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<32>), gkv, block, 0, st, p); break;
+        case UC_AB_F32_DKV64: hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<64>), gkv, block, 0, st, p); break;
+        default: break;
+    }
+    UC_CHECK_LAUNCH("uc_attention_bwd");
     return UC_OK;
 }
 
-extern "C" int uc_attention_bwd_f32(const float* Q, const float* K, const float* V, const float* O, const float* dO,
-                                    const float* LSE, float* dQ, float* dK, float* dV, float* delta, int B, int H, int Nq,
-                                    int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn,
-                                    int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn,
-                                    int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh, int64_t dk_sb, int64_t dk_sn,
-                                    int64_t dk_sh, int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale, uc_stream_t stream) {
-    return attention_bwd_f32_impl(Q, K, V, O, dO, LSE, dQ, dK, dV, delta, B, H, Nq, Nk, D, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh,
-                                  o_sb, o_sn, o_sh, dq_sb, dq_sn, dq_sh, dk_sb, dk_sn, dk_sh, dv_sb, dv_sn, dv_sh, scale,
-                                  uc_make_dropout(0.f, 0ull), stream);
-}
-
-// fp32 backward of uc_attention_fwd_drop (verification mode): uc_attention_bwd_f32's arguments + the forward's (drop_p, seed)
-extern "C" int uc_attention_bwd_f32_drop(const float* Q, const float* K, const float* V, const float* O, const float* dO,
-                                         const float* LSE, float* dQ, float* dK, float* dV, float* delta, int B, int H, int Nq,
-                                         int Nk, int D, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn,
-                                         int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn,
-                                         int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh, int64_t dk_sb, int64_t dk_sn,
-                                         int64_t dk_sh, int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale, float drop_p,
-                                         unsigned long long seed, uc_stream_t stream) {
-    UC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "uc_attention_bwd_f32_drop: drop_p must be in [0, 1) (got %g)", (double)drop_p);
-    return attention_bwd_f32_impl(Q, K, V, O, dO, LSE, dQ, dK, dV, delta, B, H, Nq, Nk, D, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh,
-                                  o_sb, o_sn, o_sh, dq_sb, dq_sn, dq_sh, dk_sb, dk_sn, dk_sh, dv_sb, dv_sn, dv_sh, scale,
-                                  uc_make_dropout(drop_p, seed), stream);
+// Attention backward, bf16 or fp32, with dropout when drop_p > 0 (O is then the forward's dropped output, LSE that of the undropped
+// scores)
+extern "C" int uc_attention_bwd(const uc_attention_bwd_desc* desc, uc_stream_t stream) {
+    UC_REQUIRE(desc, "uc_attention_bwd: null descriptor");
+    const uc_attention_bwd_desc& d = *desc;
+    UC_REQUIRE(d.drop_p >= 0.f && d.drop_p < 1.f, "uc_attention_bwd: drop_p must be in [0, 1) (got %g)", (double)d.drop_p);
+    UC_REQUIRE(d.Q && d.K && d.V && d.O && d.dO && d.LSE && d.dQ && d.dK && d.dV && d.delta, "uc_attention_bwd: null pointer");
+    if (d.dtype == UC_BF16) return attention_bwd_impl(d, stream);
+    if (d.dtype == UC_F32) return attention_bwd_f32_impl(d, stream);
+    uc_set_error("uc_attention_bwd: unsupported dtype %d", d.dtype);
+    return UC_ERR_BAD_ARG;
 }

@@ -1,5 +1,5 @@
-// Routing of one attention forward / backward launch (uc_attention_fwd[_drop], uc_attention_bwd[_drop]): which kernel, grid and
-// workgroup size a launch gets.
+// Routing of one attention forward / backward launch (uc_attention_fwd, uc_attention_bwd; bf16 and fp32, with and without dropout): which
+// kernel, grid and workgroup size a launch gets.
 //
 // Host-only, header-only and pure: no HIP header and no global state, so the system C++ compiler builds it
 // (tests/test_attention_plan.py).  The entry points read every knob once into an AttnKnobs snapshot and call the plan once; they
@@ -28,12 +28,16 @@ enum AttnDqKernel {
     UC_AB_DQ32,          // attn_bwd_dq_kernel<false>: 128 queries (4 waves x 32) per workgroup
     UC_AB_DQ64,          // attn_bwd_dq64_kernel: persistent, 64 queries per wave
     UC_AB_DQ32_DROP,     // attn_bwd_dq_kernel<true>
+    UC_AB_F32_DQ32,      // attn_bwd_dq_f32_kernel<32>: fp32 verification kernel (dropout a run-time test), head_dim <= 32, grid (query tiles, H, B)
+    UC_AB_F32_DQ64,      // attn_bwd_dq_f32_kernel<64>: head_dim <= 64
 };
 
 enum AttnDkvKernel {
     UC_AB_DKV32,         // attn_bwd_dkv_kernel<false>: 128 keys per workgroup
     UC_AB_DKV64,         // attn_bwd_dkv64_kernel: persistent, 64 keys per wave
     UC_AB_DKV32_DROP,    // attn_bwd_dkv_kernel<true>
+    UC_AB_F32_DKV32,     // attn_bwd_dkv_f32_kernel<32>: grid (key tiles, H, B)
+    UC_AB_F32_DKV64,     // attn_bwd_dkv_f32_kernel<64>
 };
 
 // every knob the routing reads, read once per launch
@@ -43,21 +47,6 @@ struct AttnKnobs {
     int role_split;   // eight-wave forward as role-split segments: 0 / 1
     int cus;          // compute units of the device
     int dbg;          // UC_ATTN_DBG anatomy switches (diag build only; 0 in the release build)
-};
-
-// the arguments of a forward launch the routing looks at (not ABI)
-struct AttnFwdDesc {
-    int dtype, v_layout;
-    int B, H, Nq, Nk, D;
-    int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
-    uintptr_t O;      // the output's address (for its alignment)
-    bool drop;        // dropout of the probabilities (drop_p > 0)
-};
-
-struct AttnBwdDesc {
-    int B, H, Nq, Nk;
-    int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
-    bool drop;
 };
 
 struct AttnFwdPlan {
@@ -72,20 +61,24 @@ struct AttnFwdPlan {
 struct AttnBwdPlan {
     AttnDqKernel dq;
     AttnDkvKernel dkv;
-    unsigned dq_grid, dkv_grid;   // 1-D grids, 256 threads per workgroup
+    unsigned dq_grid[3], dkv_grid[3];   // x, y, z (bf16: 1-D)
+    int block;                          // threads per workgroup of both launches
+    unsigned delta_grid;                // fp32: attn_delta_f32_kernel's 1-D grid of 256 threads, launched first; else 0
 };
 
-static inline AttnFwdPlan uc_attention_fwd_plan(const AttnFwdDesc& d, const AttnKnobs& k) {
+// (the plans read only the shape, strides, dtype, v_layout, the output's address and drop_p of the descriptor)
+static inline AttnFwdPlan uc_attention_fwd_plan(const uc_attention_desc& d, const AttnKnobs& k) {
     AttnFwdPlan plan = {};
     plan.block = 256;
     // the grid of the register-staged and fp32 kernels: one workgroup per 128 queries of a (batch, head)
     plan.grid[0] = (unsigned)((d.Nq + 127) / 128); plan.grid[1] = (unsigned)d.H; plan.grid[2] = (unsigned)d.B;
+    const bool drop = d.drop_p != 0.f;
     if (d.dtype == UC_F32) {
-        plan.kernel = d.D <= 32 ? (d.drop ? UC_AF_F32_32_DROP : UC_AF_F32_32) : (d.drop ? UC_AF_F32_64_DROP : UC_AF_F32_64);
+        plan.kernel = d.D <= 32 ? (drop ? UC_AF_F32_32_DROP : UC_AF_F32_32) : (drop ? UC_AF_F32_64_DROP : UC_AF_F32_64);
         plan.block = 128;
         return plan;
     }
-    if (d.drop) {   // bf16 with dropout: the register-staged kernel with the mask between the softmax and the second product
+    if (drop) {   // bf16 with dropout: the register-staged kernel with the mask between the softmax and the second product
         plan.kernel = UC_AF_REG128_DROP;
         return plan;
     }
@@ -101,7 +94,7 @@ static inline AttnFwdPlan uc_attention_fwd_plan(const AttnFwdDesc& d, const Attn
     const int qtile = 32 * nw, nqt = (Nq + qtile - 1) / qtile;
     plan.nqt = nqt;
     // DMA-staged kernel: whole 64-key tiles, 32-bit byte offsets inside one (batch, head)'s K rows / VT rows
-    const bool dma_ok = (int64_t)nqt * H * B < ((int64_t)1 << 31) && d.O % 16 == 0 && d.o_sb % 8 == 0 && d.o_sn % 8 == 0 && d.o_sh % 8 == 0 &&
+    const bool dma_ok = (int64_t)nqt * H * B < ((int64_t)1 << 31) && (uintptr_t)d.O % 16 == 0 && d.o_sb % 8 == 0 && d.o_sn % 8 == 0 && d.o_sh % 8 == 0 &&
                         (int64_t)32 * d.q_sn * 2 < ((int64_t)1 << 31) && (int64_t)Nk * d.k_sn * 2 < ((int64_t)1 << 31) &&
                         (int64_t)64 * npad * 2 < ((int64_t)1 << 31);
     if (!dma_ok) {
@@ -142,12 +135,24 @@ static inline AttnFwdPlan uc_attention_fwd_plan(const AttnFwdDesc& d, const Attn
     return plan;
 }
 
-static inline AttnBwdPlan uc_attention_bwd_plan(const AttnBwdDesc& d, const AttnKnobs& k) {
+static inline AttnBwdPlan uc_attention_bwd_plan(const uc_attention_bwd_desc& d, const AttnKnobs& k) {
     AttnBwdPlan plan = {};
     const int Nq = d.Nq, Nk = d.Nk, H = d.H, B = d.B;
-    plan.dq_grid = (unsigned)(((Nq + 127) / 128) * H * B);
-    plan.dkv_grid = (unsigned)(((Nk + 127) / 128) * H * B);
-    if (d.drop) {   // attention dropout: the 32-row kernels with the forward's mask re-evaluated per element
+    if (d.dtype == UC_F32) {   // one thread per query row (dQ) / per key row (dK, dV), 128 per workgroup, after the delta pass
+        const bool d32 = d.D <= 32;
+        plan.dq = d32 ? UC_AB_F32_DQ32 : UC_AB_F32_DQ64;
+        plan.dkv = d32 ? UC_AB_F32_DKV32 : UC_AB_F32_DKV64;
+        plan.dq_grid[0] = (unsigned)((Nq + 127) / 128); plan.dkv_grid[0] = (unsigned)((Nk + 127) / 128);
+        plan.dq_grid[1] = plan.dkv_grid[1] = (unsigned)H; plan.dq_grid[2] = plan.dkv_grid[2] = (unsigned)B;
+        plan.block = 128;
+        plan.delta_grid = (unsigned)(((int64_t)B * H * Nq + 255) / 256);
+        return plan;
+    }
+    plan.block = 256;
+    plan.dq_grid[1] = plan.dq_grid[2] = plan.dkv_grid[1] = plan.dkv_grid[2] = 1;
+    plan.dq_grid[0] = (unsigned)(((Nq + 127) / 128) * H * B);
+    plan.dkv_grid[0] = (unsigned)(((Nk + 127) / 128) * H * B);
+    if (d.drop_p != 0.f) {   // attention dropout: the 32-row kernels with the forward's mask re-evaluated per element
         plan.dq = UC_AB_DQ32_DROP;
         plan.dkv = UC_AB_DKV32_DROP;
         return plan;
@@ -162,7 +167,7 @@ static inline AttnBwdPlan uc_attention_bwd_plan(const AttnBwdDesc& d, const Attn
     const bool dq64 = Nk > 64 && v_ext < (int64_t)0xffffffffll &&
                       (k.bwd64 == 2 || (k.bwd64 == 1 && Nq >= 192 && ((Nq + 255) / 256) * 256 * 3 <= Nq * 4));
     plan.dq = dq64 ? UC_AB_DQ64 : UC_AB_DQ32;
-    if (dq64) plan.dq_grid = persistent((int64_t)((Nq + 255) / 256) * H * B);
+    if (dq64) plan.dq_grid[0] = persistent((int64_t)((Nq + 255) / 256) * H * B);
     // 64 keys per wave (attention_bwd64.h) when a 256-key workgroup is mostly real keys; the 32-key kernel otherwise
     // (its Q / dO / scratch descriptors span the whole tensors: 32-bit byte offsets)
     const int64_t q_ext = ((int64_t)(B - 1) * d.q_sb + (int64_t)(H - 1) * d.q_sh + (int64_t)(Nq - 1) * d.q_sn + 64) * 2;
@@ -176,6 +181,6 @@ static inline AttnBwdPlan uc_attention_bwd_plan(const AttnBwdDesc& d, const Attn
     const bool dkv64 = Nq > 64 && fits32 && rows_follow &&
                        (k.bwd64 == 2 || (k.bwd64 == 1 && Nk >= 192 && ((Nk + 255) / 256) * 256 * 3 <= Nk * 4));
     plan.dkv = dkv64 ? UC_AB_DKV64 : UC_AB_DKV32;
-    if (dkv64) plan.dkv_grid = persistent((int64_t)((Nk + 255) / 256) * H * B);
+    if (dkv64) plan.dkv_grid[0] = persistent((int64_t)((Nk + 255) / 256) * H * B);
     return plan;
 }

@@ -13,8 +13,8 @@ import contextlib
 import torch
 
 from . import _lib
-from ._lib import (GemmDesc, UC_A_CONV3X3, UC_A_DENSE, UC_ACT_GELU_ERF, UC_ACT_NONE, UC_ACT_RELU, UC_BF16, UC_F16,
-                   UC_F32, UC_V_PACKED_T, UC_V_ROWMAJOR, UcHipError)
+from ._lib import (AttnBwdDesc, AttnDesc, GemmDesc, UC_A_CONV3X3, UC_A_DENSE, UC_ACT_GELU_ERF, UC_ACT_NONE, UC_ACT_RELU,
+                   UC_BF16, UC_F16, UC_F32, UC_V_PACKED_T, UC_V_ROWMAJOR, UcHipError)
 
 _DT = {torch.float32: UC_F32, torch.bfloat16: UC_BF16, torch.float16: UC_F16}
 ACT = {None: UC_ACT_NONE, "none": UC_ACT_NONE, "gelu": UC_ACT_GELU_ERF, "relu": UC_ACT_RELU}
@@ -593,7 +593,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, v
               out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None, dropout=None) -> torch.Tensor:
     """q [B,Nq,H,D], k [B,Nk,H,D] strided views (stride(3)==1); v same, or packed VT [B,H,D,Npad] when v_packed.
     Returns O [B,Nq,H,D] contiguous (== [B,Nq,H*D]).
-    dropout = (p, seed): dropout of the attention probabilities inside the kernel (uc_attention_fwd_drop: a counter-based keep
+    dropout = (p, seed): dropout of the attention probabilities inside the kernel (uc_attention_fwd with drop_p > 0: a counter-based keep
     function of (seed, batch, head, query, key); attention_drop_mask materialises it; the backward takes the same pair)."""
     _need_gpu(q, k, v)
     B, Nq, H, D = q.shape
@@ -607,17 +607,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, v
     else:
         assert v.stride(3) == 1
         vs = (v.stride(0), v.stride(1), v.stride(2))
+    d = AttnDesc()
+    d.dtype, d.v_layout = _dt(q.dtype), UC_V_PACKED_T if v_packed else UC_V_ROWMAJOR
+    d.B, d.H, d.Nq, d.Nk, d.D = B, H, Nq, Nk, D
+    d.Q, d.K, d.V, d.O = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    d.q_sb, d.q_sn, d.q_sh = q.stride(0), q.stride(1), q.stride(2)
+    d.k_sb, d.k_sn, d.k_sh = k.stride(0), k.stride(1), k.stride(2)
+    d.v_sb, d.v_sn, d.v_sh = vs
+    d.o_sb, d.o_sn, d.o_sh = out.stride(0), out.stride(1), out.stride(2)
+    d.scale, d.lse = float(scale), _p(lse)
     if dropout is not None and float(dropout[0]) > 0.0:
-        _lib.check(_lib.load().uc_attention_fwd_drop(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _dt(q.dtype), UC_V_PACKED_T if v_packed else UC_V_ROWMAJOR,
-            B, H, Nq, Nk, D, q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2), vs[0], vs[1], vs[2],
-            out.stride(0), out.stride(1), out.stride(2), float(scale), _p(lse), float(dropout[0]), int(dropout[1]), _stream()),
-            "uc_attention_fwd_drop")
-        return out
-    _lib.check(_lib.load().uc_attention_fwd(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _dt(q.dtype), UC_V_PACKED_T if v_packed else UC_V_ROWMAJOR,
-        B, H, Nq, Nk, D, q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2), vs[0], vs[1], vs[2],
-        out.stride(0), out.stride(1), out.stride(2), float(scale), _p(lse), _stream()), "uc_attention_fwd")
+        d.drop_p, d.seed = float(dropout[0]), int(dropout[1])
+    _lib.check(_lib.load().uc_attention_fwd(C.byref(d), _stream()), "uc_attention_fwd")
     return out
 
 
@@ -1056,43 +1057,23 @@ def attention_bwd(q, k, v, o, do, lse, scale: float, out=None, rope=None, dropou
     if rope is not None:
         assert dt == torch.bfloat16 and rope[0].dtype == torch.int64 and rope[1].dtype == torch.int64
         assert rope[0].is_contiguous() and rope[1].is_contiguous() and rope[0].numel() == 2 * B * Nq and rope[1].numel() == 2 * B * Nk
-    drop = dropout is not None and float(dropout[0]) > 0.0
-    if dt == torch.float32 and drop:
-        _lib.check(_lib.load().uc_attention_bwd_f32_drop(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-            dv.data_ptr(), delta.data_ptr(), B, H, Nq, Nk, D,
-            q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2),
-            o.stride(0), o.stride(1), o.stride(2), dq.stride(0), dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1),
-            dk.stride(2), dv.stride(0), dv.stride(1), dv.stride(2), float(scale), float(dropout[0]), int(dropout[1]), _stream()),
-            "uc_attention_bwd_f32_drop")
-        return dq, dk, dv
-    if drop:
-        _lib.check(_lib.load().uc_attention_bwd_drop(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(),
-            dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), B, H, Nq, Nk,
-            q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2),
-            o.stride(0), o.stride(1), o.stride(2), dq.stride(0), dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1), dk.stride(2),
-            dv.stride(0), dv.stride(1), dv.stride(2), float(scale),
-            _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None,
-            float(rope[2]) if rope is not None else 0.0, float(rope[3]) if rope is not None else 0.0,
-            float(dropout[0]), int(dropout[1]), _stream()), "uc_attention_bwd_drop")
-        return dq, dk, dv
-    if dt == torch.float32:
-        _lib.check(_lib.load().uc_attention_bwd_f32(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-            dv.data_ptr(), delta.data_ptr(), B, H, Nq, Nk, D,
-            q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2),
-            o.stride(0), o.stride(1), o.stride(2), dq.stride(0), dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1),
-            dk.stride(2), dv.stride(0), dv.stride(1), dv.stride(2), float(scale), _stream()), "uc_attention_bwd_f32")
-        return dq, dk, dv
-    _lib.check(_lib.load().uc_attention_bwd(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(),
-        dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), B, H, Nq, Nk,
-        q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2),
-        o.stride(0), o.stride(1), o.stride(2), dq.stride(0), dq.stride(1), dq.stride(2), dk.stride(0), dk.stride(1), dk.stride(2),
-        dv.stride(0), dv.stride(1), dv.stride(2), float(scale),
-        _p(rope[0]) if rope is not None else None, _p(rope[1]) if rope is not None else None,
-        float(rope[2]) if rope is not None else 0.0, float(rope[3]) if rope is not None else 0.0, _stream()), "uc_attention_bwd")
+    d = AttnBwdDesc()
+    d.dtype, d.B, d.H, d.Nq, d.Nk, d.D = _dt(dt), B, H, Nq, Nk, D
+    d.Q, d.K, d.V, d.O, d.dO, d.LSE = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr()
+    d.dQ, d.dK, d.dV, d.delta = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
+    d.q_sb, d.q_sn, d.q_sh = q.stride(0), q.stride(1), q.stride(2)
+    d.k_sb, d.k_sn, d.k_sh = k.stride(0), k.stride(1), k.stride(2)
+    d.v_sb, d.v_sn, d.v_sh = v.stride(0), v.stride(1), v.stride(2)
+    d.o_sb, d.o_sn, d.o_sh = o.stride(0), o.stride(1), o.stride(2)
+    d.dq_sb, d.dq_sn, d.dq_sh = dq.stride(0), dq.stride(1), dq.stride(2)
+    d.dk_sb, d.dk_sn, d.dk_sh = dk.stride(0), dk.stride(1), dk.stride(2)
+    d.dv_sb, d.dv_sn, d.dv_sh = dv.stride(0), dv.stride(1), dv.stride(2)
+    d.scale = float(scale)
+    if rope is not None:
+        d.rope_qpos, d.rope_kpos, d.rope_base, d.rope_f0 = rope[0].data_ptr(), rope[1].data_ptr(), float(rope[2]), float(rope[3])
+    if dropout is not None and float(dropout[0]) > 0.0:
+        d.drop_p, d.seed = float(dropout[0]), int(dropout[1])
+    _lib.check(_lib.load().uc_attention_bwd(C.byref(d), _stream()), "uc_attention_bwd")
     return dq, dk, dv
 
 
