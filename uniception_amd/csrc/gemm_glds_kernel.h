@@ -962,7 +962,17 @@ __device__ __forceinline__ void glds_epilogue_bf16_train(glds_pe_t p, float4_t (
             const float4_t pre = acc[i][j] + b4[j];
             const int off = wr_off + (((2 * j + (g >> 1)) ^ (frow & 7)) << 4);
             if constexpr (PRE) *reinterpret_cast<uint2*>(buf + 4096 + off) = (uint2){pack_bf16x2(pre.x, pre.y), pack_bf16x2(pre.z, pre.w)};
-            const float4_t v = glds_act4<ACT>(pre);
+            float4_t v = glds_act4<ACT>(pre);
+            if constexpr (DACT) {
+                // act'(u) multiplies the fp32 value, BEFORE the one rounding to bf16 (multiplying the rounded value in the drain and
+                // rounding again put 6 % of the elements more than half an ulp off: tests/test_gemm_routes_gpu.py); rows past M read row M - 1
+                const int64_t m = min(wave_m + 16 * i + frow, p.M - 1);
+                const uint2 u = *reinterpret_cast<const uint2*>((const char*)p.dact_u + (m * p.ldc + wave_n + 16 * j + 4 * g) * 2);
+                v.x *= glds_dact(__uint_as_float(u.x << 16), p.dact_act);
+                v.y *= glds_dact(__uint_as_float(u.x & 0xffff0000u), p.dact_act);
+                v.z *= glds_dact(__uint_as_float(u.y << 16), p.dact_act);
+                v.w *= glds_dact(__uint_as_float(u.y & 0xffff0000u), p.dact_act);
+            }
             *reinterpret_cast<uint2*>(buf + off) = (uint2){pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)};
         }
     };
@@ -982,18 +992,6 @@ __device__ __forceinline__ void glds_epilogue_bf16_train(glds_pe_t p, float4_t (
             uint4 v = *reinterpret_cast<const uint4*>(buf + R * 128 + (pch << 4));
             if (ps) v = (uint4){v.z, v.w, v.x, v.y};         // rows 8..15 keep their halves swapped in the bounce block
             if (16 * i + 8 * ps < rows_left) {
-                if constexpr (DACT) {
-                    const uint4 u = *reinterpret_cast<const uint4*>((const char*)p.dact_u + off);
-                    const unsigned vv[4] = {v.x, v.y, v.z, v.w}, uu[4] = {u.x, u.y, u.z, u.w};
-                    unsigned oo[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float v0 = __uint_as_float(vv[q] << 16), v1 = __uint_as_float(vv[q] & 0xffff0000u);
-                        const float u0 = __uint_as_float(uu[q] << 16), u1 = __uint_as_float(uu[q] & 0xffff0000u);
-                        oo[q] = pack_bf16x2(v0 * glds_dact(u0, p.dact_act), v1 * glds_dact(u1, p.dact_act));
-                    }
-                    v = (uint4){oo[0], oo[1], oo[2], oo[3]};
-                }
                 *reinterpret_cast<uint4*>((char*)p.C + off) = v;
                 if constexpr (PRE) {
                     uint4 w = *reinterpret_cast<const uint4*>(buf + 4096 + R * 128 + (pch << 4));
