@@ -45,7 +45,7 @@ const char* uc_last_error(void);
  *   1: forward path.  2: training entry points, uc_gemm_desc gained preact_out / split_k / dact_u, uc_attention_fwd gained lse,
  *      fp8 attention, DINOv2 token ops.  3: uc_attention_fwd_fp8_k8, uc_k_pack_fp8 added.  4/5: see INTEGRATION.md.
  *   6: uc_adaptor_program_bwd added.  7: uc_build_flavor, uc_tuning_set / uc_tuning_get (environment knobs read once; no
- *      diagnostics in the release build), uc_attention_fwd_x3.  8: uc_gemm_desc gained ln_nblk / ln_eps.  9: uc_gemm_tn_conv_tiles added.
+ *      diagnostics in the release build), uc_attention_fwd_x3.  8: uc_gemm_desc gained ln_nblk / ln_eps.  9: a tile-count query for uc_gemm_tn's conv form added.
  *   10: uc_attention_fwd_x3 takes RoPE-2D positions (rotation fused into its operand split).
  *   11: the folded LayerNorm's block statistics (uc_gemm_desc.stats_out, ln_stats with ln_nblk > 0, uc_ln_stats_finalize) are
  *       block-major [N/64][M][2] instead of [M][N/64][2]; uc_gemm_desc gained fuse_ws (caller-provided hand-over buffer of the
@@ -55,8 +55,10 @@ const char* uc_last_error(void);
  *   14 (round 6): attention dropout — three dropout twins of the attention entry points, uc_attention_drop_mask added; tuning knob
  *       conv_rows_flat.
  *   15: uc_attention_fwd / uc_attention_bwd take one descriptor each (uc_attention_desc, uc_attention_bwd_desc): dtype selects bf16 or
- *       fp32, drop_p > 0 dropout; the fp32 backward and the three dropout twins are gone. */
-#define UC_ABI_VERSION 15
+ *       fp32, drop_p > 0 dropout; the fp32 backward and the three dropout twins are gone.
+ *   16: uc_gemm_tn takes one descriptor (uc_gemm_tn_desc); uc_gemm_tn_query (tiles per K-slice and the recommended split_k of a
+ *       shape, dense or conv) replaces the conv-only tile-count query of version 9. */
+#define UC_ABI_VERSION 16
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -427,21 +429,32 @@ int uc_layernorm_bwd(const void* x, int x_dtype, const float* gamma, const void*
 
 /* "TN" contraction over tokens / pixels for weight gradients, no operand transposes (bf16 in, fp32 out):
  *     C[s][i,j] = sum_{t in K-slice s} A[t,i] * B[t,j]        A = dY [T,I] (lda),  B = X [T,J] (ldb),  dW = dY^T X
- *   conv_B > 0: B is the IMPLICIT im2col of the NHWC image [conv_B,conv_H,conv_W,conv_Cin] of a 3x3 / pad-1 conv with the
- *   given stride: B[t,(ky*3+kx)*Cin+c] = act(x[b,oy*s-1+ky,ox*s-1+kx,c]), t=(b,oy,ox), J = 9*Cin, relu_b = ReLU-on-load.
- *   C holds split_k slabs of [I,J] fp32 (sum them with uc_splitk_reduce).  I, J, lda, ldb multiples of 8.
- *   colsum_a (optional): sum_t A[t,i] — the bias gradient, formed from the A fragments already in registers (no extra pass
- *   over dY): split_k slabs of [I] fp32, or with colsum_atomic != 0 ONE [I] buffer every K slice adds to atomically (+=),
- *   e.g. the bias's gradient buffer itself.
  *   (the reference gets these products from autograd's addmm / conv backward.) */
-int uc_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t T, int64_t I, int64_t J, int conv_B, int conv_H,
-               int conv_W, int conv_Cin, int conv_stride, int relu_b, float* C, float* colsum_a, int colsum_atomic,
-               int split_k, uc_stream_t stream);
-/* Output tiles one K-slice of the conv form of uc_gemm_tn occupies (workgroups per slice) — what a caller sizes split_k with so that
- * tiles * split_k fills the CUs.  Stride-1 convs on maps a multiple of 64 wide with Cin and Cout multiples of 128 take the
- * row-walking kernel (one kernel row ky per workgroup, the three taps kx as row shifts of the staged pixels: no im2col decode, every
- * input pixel fetched three times instead of nine): 3 * (Cout/128) * (Cin/128) tiles; every other shape the implicit-im2col kernel. */
-int uc_gemm_tn_conv_tiles(int64_t Cout, int conv_H, int conv_W, int conv_Cin, int conv_stride);
+typedef struct uc_gemm_tn_desc {
+    const void* A;           /* dY [T,I] bf16, leading dim lda; 16-byte aligned */
+    int64_t lda;
+    const void* B;           /* dense: X [T,J] bf16, leading dim ldb; conv_B > 0: the NHWC image [conv_B,conv_H,conv_W,conv_Cin]; 16-byte aligned */
+    int64_t ldb;
+    int64_t T, I, J;         /* I, J, lda, ldb multiples of 8 */
+    /* conv_B > 0: B is the IMPLICIT im2col of the image of a 3x3 / pad-1 conv with the given stride:
+     * B[t,(ky*3+kx)*Cin+c] = act(x[b,oy*s-1+ky,ox*s-1+kx,c]), t=(b,oy,ox), J = 9*Cin, relu_b = ReLU-on-load.  Stride-1 convs on maps a
+     * multiple of 64 wide with Cin and I (= Cout) multiples of 128 take the row-walking kernel (one kernel row ky per workgroup, the
+     * three taps kx as row shifts of the staged pixels: no im2col decode, every input pixel fetched three times instead of nine):
+     * 3 * (I/128) * (Cin/128) workgroups per K-slice; every other shape the implicit-im2col kernel. */
+    int conv_B, conv_H, conv_W, conv_Cin, conv_stride, relu_b;
+    float* C;                /* split_k slabs of [I,J] fp32 (sum them with uc_splitk_reduce); 16-byte aligned */
+    /* colsum_a (optional): sum_t A[t,i] — the bias gradient, formed from the A fragments already in registers (no extra pass over
+     * dY): split_k slabs of [I] fp32, or with colsum_atomic != 0 ONE [I] buffer every K slice adds to atomically (+=), e.g. the
+     * bias's gradient buffer itself. */
+    float* colsum_a;
+    int colsum_atomic;
+    int split_k;             /* K slices, 1 .. 1024 (uc_gemm_tn_query recommends a count) */
+} uc_gemm_tn_desc;
+int uc_gemm_tn(const uc_gemm_tn_desc* d, uc_stream_t stream);
+/* tiles: workgroups one K-slice occupies; split_k: the slice count the library recommends for this shape (tiles * split_k fills the
+ * CUs once).  Reads the shape fields only (pointers may be NULL, d->split_k is ignored); either out-pointer may be NULL.  Returns a
+ * status like every entry point. */
+int uc_gemm_tn_query(const uc_gemm_tn_desc* d, int* tiles, int* split_k);
 
 /* out[i] = (accumulate ? out[i] : 0) + sum_s ws[s*slab_stride + i], i < n (n, slab_stride multiples of 4): reduction of the
  * split_k slabs of uc_gemm / uc_gemm_tn (a row range of every slab when slab_stride > n); with accumulate it adds the result

@@ -117,7 +117,8 @@ def test_gemm_descriptor_layout_matches_header():
     check_descriptor_layout("uc_gemm_desc", "GemmDesc")
 
 
-@pytest.mark.parametrize("struct,mirror", [("uc_attention_desc", "AttnDesc"), ("uc_attention_bwd_desc", "AttnBwdDesc")])
+@pytest.mark.parametrize("struct,mirror", [("uc_attention_desc", "AttnDesc"), ("uc_attention_bwd_desc", "AttnBwdDesc"),
+                                           ("uc_gemm_tn_desc", "GemmTnDesc")])
 def test_attention_descriptor_layout_matches_header(struct, mirror):
     check_descriptor_layout(struct, mirror)
 

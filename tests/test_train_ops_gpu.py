@@ -386,6 +386,10 @@ def test_gemm_tn_dense(gpu, T, I, J, sk):
     # fused bias gradient: column sums of the first operand
     assert rel_l2(cs.sum(0).cpu(), a.float().sum(0)) < 2e-5
     assert torch.equal(ops.splitk_reduce(ops.gemm_tn(a.to(gpu), b.to(gpu), split_k=sk)), c)
+    # split_k omitted: as many slabs as the library recommends for the shape
+    ws_auto = ops.gemm_tn(a.to(gpu), b.to(gpu))
+    assert ws_auto.shape == (ops.gemm_tn_query(a.to(gpu), b.to(gpu))[1], I, J)
+    assert rel_l2(ops.splitk_reduce(ws_auto).cpu(), ref) < 2e-5
 
 
 def test_gemm_tn_strided_operands(gpu):
@@ -426,13 +430,14 @@ def test_gemm_tn_conv_rows_kernel(gpu, relu, B, H, W, Cin, Cout, sk):
     against torch's conv backward on the same bf16 inputs, image borders (first / last row and column segments, a one-row image),
     several images, ReLU on load, K slices that do not divide the segment count, more slices than segments."""
     from uniception_amd import ops
-    assert ops.gemm_tn_conv_tiles(Cout, H, W, Cin, 1) == 3 * (Cout // 128) * (Cin // 128)
     g = torch.Generator().manual_seed(H * W + Cin + Cout)
     x = torch.randn(B, H, W, Cin, generator=g).bfloat16()
     dy = torch.randn(B, H, W, Cout, generator=g).bfloat16()
     wref = torch.zeros(Cout, Cin, 3, 3, requires_grad=True)
     xa = x.float().relu() if relu else x.float()
     F.conv2d(xa.permute(0, 3, 1, 2), wref, stride=1, padding=1).backward(dy.float().permute(0, 3, 1, 2))
+    tiles, sk_auto = ops.gemm_tn_query(dy.view(-1, Cout).to(gpu), x.to(gpu), conv=(1, relu))
+    assert tiles == 3 * (Cout // 128) * (Cin // 128)
     ws, cs = ops.gemm_tn(dy.view(-1, Cout).to(gpu), x.to(gpu), split_k=sk, conv=(1, relu), colsum=True)
     dW = ops.splitk_reduce(ws).view(Cout, 3, 3, Cin).permute(0, 3, 1, 2)
     assert rel_l2(dW.cpu(), wref.grad) < 2e-5
@@ -440,6 +445,10 @@ def test_gemm_tn_conv_rows_kernel(gpu, relu, B, H, W, Cin, Cout, sk):
     into = torch.full((Cout,), 2.0, device=gpu)
     ws2 = ops.gemm_tn(dy.view(-1, Cout).to(gpu), x.to(gpu), split_k=sk, conv=(1, relu), colsum_into=into)
     assert torch.equal(ws2, ws) and rel_l2((into - 2.0).cpu(), dy.float().sum((0, 1, 2))) < 2e-5
+    # split_k omitted: as many slabs as the library recommends for the shape
+    ws_auto = ops.gemm_tn(dy.view(-1, Cout).to(gpu), x.to(gpu), conv=(1, relu))
+    assert ws_auto.shape[0] == sk_auto
+    assert rel_l2(ops.splitk_reduce(ws_auto).view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).cpu(), wref.grad) < 2e-5
 
 
 @pytest.mark.parametrize("act", ["gelu", "relu"])

@@ -74,6 +74,15 @@ class AttnBwdDesc(C.Structure):
     ]
 
 
+class GemmTnDesc(C.Structure):
+    # field order == struct uc_gemm_tn_desc in include/uc_hip.h
+    _fields_ = [
+        ("A", vp), ("lda", i64), ("B", vp), ("ldb", i64), ("T", i64), ("I", i64), ("J", i64),
+        ("conv_B", i32), ("conv_H", i32), ("conv_W", i32), ("conv_Cin", i32), ("conv_stride", i32), ("relu_b", i32),
+        ("C", vp), ("colsum_a", vp), ("colsum_atomic", i32), ("split_k", i32),
+    ]
+
+
 # name -> argtypes (every function returns int except uc_last_error)
 SIGNATURES = {
     "uc_abi_version": [],
@@ -109,8 +118,8 @@ SIGNATURES = {
     "uc_assemble_tokens": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "uc_token_slice": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "uc_layernorm_bwd": [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i64, i32, f32, vp],
-    "uc_gemm_tn": [vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp],
-    "uc_gemm_tn_conv_tiles": [i64, i32, i32, i32, i32],
+    "uc_gemm_tn": [C.POINTER(GemmTnDesc), vp],
+    "uc_gemm_tn_query": [C.POINTER(GemmTnDesc), C.POINTER(i32), C.POINTER(i32)],
     "uc_splitk_reduce": [vp, i32, i64, i64, vp, i32, vp],
     "uc_colsum": [vp, i32, i64, i64, i64, vp, vp],
     "uc_act_bwd": [vp, vp, vp, i32, i32, i64, vp],
@@ -136,7 +145,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 15   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 16   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

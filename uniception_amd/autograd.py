@@ -7,7 +7,8 @@ sub-layer's backward is one Function calling uc_hip entry points:
     pre-LN sub-layer  x_out = x + f(LN(x)):   backward gets d(x_out) and returns
         dx = LN_bwd(x, gamma, df/dh) + d(x_out)              (residual add fused into uc_layernorm_bwd)
     linear y = h W^T + b:
-        dW = dy^T h   -> uc_gemm_tn (both operands row-major, transposing LDS reads, split-K slabs + uc_splitk_reduce —
+        dW = dy^T h   -> uc_gemm_tn (both operands row-major, transposing LDS reads, as many split-K slabs as the library
+                         recommends for the shape, + uc_splitk_reduce —
                          straight into the flat gradient buffer under the Trainer); fp32 mode: uc_transpose2d + fp32 uc_gemm
         db = column sums of dy formed inside uc_gemm_tn; dh = uc_gemm(dy, W^T)   (W^T prepared once per weight version)
     attention: uc_attention_fwd saves LSE; uc_attention_bwd recomputes P tile by tile (dQ kernel + dK/dV kernel)
@@ -39,12 +40,6 @@ def _c(g: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 
 def _tp(x2d: torch.Tensor, dt: torch.dtype, with_copy: bool = False):
     return ops.transpose2d(x2d, dt, pad_to=KPAD, with_copy=with_copy)
-
-
-def _split_k(I: int, J: int, T: int) -> int:
-    """Few 256x256 output tiles, very long reduction: split it so tiles*sk just fills the 256 CUs once."""
-    tiles = ((I + 255) // 256) * ((J + 255) // 256)
-    return max(1, min(T // 512, 256 // tiles))
 
 
 def _split_k_x3(I: int, J: int, T: int, dt) -> int:
@@ -157,16 +152,15 @@ def _wgrad(dy2d: torch.Tensor, x2d: torch.Tensor, dt: torch.dtype, bias: bool = 
         a = dy2d if dy2d.dtype == dt else ops.convert(_c(dy2d), dt)
         b = x2d if x2d.dtype == dt else ops.convert(_c(x2d), dt)
         if _tn_ok(a, b):
-            sk = _split_k(a.shape[1], b.shape[1], a.shape[0])
             K = b.shape[1]
             bt = _bias_target(bias_sink, a.shape[1]) if bias else None
             if bt is not None:      # bias gradient added atomically into the bias's own gradient buffer: db is returned None
-                ws, db = ops.gemm_tn(a, b, split_k=sk, colsum_into=bt), None
+                ws, db = ops.gemm_tn(a, b, colsum_into=bt), None
             elif bias:
-                ws, cs = ops.gemm_tn(a, b, split_k=sk, colsum=True)
+                ws, cs = ops.gemm_tn(a, b, colsum=True)
                 db = _reduce_slabs(cs.unsqueeze(1)).reshape(-1)
             else:
-                ws, db = ops.gemm_tn(a, b, split_k=sk), None
+                ws, db = ops.gemm_tn(a, b), None
             if sink is not None and all(_sinkable(p, r1 - r0, K) for p, r0, r1 in sink):
                 for p, r0, r1 in sink:
                     ops.splitk_reduce(ws[:, r0:r1], out=p.grad.view(r1 - r0, K), accumulate=True)
@@ -183,12 +177,10 @@ def _wgrad_conv(dz: torch.Tensor, x: torch.Tensor, stride: int, relu_in: bool, b
     Cout = dz.shape[-1]
     dz2 = dz.view(-1, Cout)
     if x.dtype == torch.bfloat16 and _tn_ok(dz2, x):
-        # (split so that tiles * sk fills the 256 CUs once; the tile count depends on which kernel the shape takes)
-        sk = max(1, min(dz2.shape[0] // 512, 256 // ops.gemm_tn_conv_tiles(Cout, x.shape[1], x.shape[2], x.shape[3], stride)))
         if bias:
-            ws, cs = ops.gemm_tn(dz2, x, split_k=sk, conv=(stride, relu_in), colsum=True)
+            ws, cs = ops.gemm_tn(dz2, x, conv=(stride, relu_in), colsum=True)
             return _reduce_slabs(ws), _reduce_slabs(cs.unsqueeze(1)).reshape(-1)
-        return _reduce_slabs(ops.gemm_tn(dz2, x, split_k=sk, conv=(stride, relu_in))), None
+        return _reduce_slabs(ops.gemm_tn(dz2, x, conv=(stride, relu_in))), None
     aT, bT = _tp(dz2, x.dtype), ops.im2col_t(x, stride, relu_in, KPAD)
     sk = _split_k_x3(aT.shape[0], bT.shape[0], aT.shape[1], x.dtype)
     dW = ops.gemm(aT, bT, out_dtype=torch.float32, split_k=sk)

@@ -46,7 +46,6 @@ const UcKnobs& uc_knobs() {
         g_knobs.gemm_group_m = env_int("UC_GEMM_GROUP_M", 4);
         if (g_knobs.gemm_group_m < 1) g_knobs.gemm_group_m = 1;
         g_knobs.gemm_4wave = env_int("UC_GEMM_4WAVE", 3);
-        g_knobs.conv_dw_rows = env_int("UC_CONV_DW_ROWS", 1);
         g_knobs.attn_prio = env_int("UC_ATTN_PRIO", 0);
         g_knobs.bilinear_rows2 = env_int("UC_BILINEAR_ROWS2", 4);
         g_knobs.ln_nt = env_int("UC_LN_NT", -1);

@@ -13,7 +13,9 @@
 // 8-bank groups.  As in the NT kernel the permutation is applied to the DMA's per-lane SOURCE address.
 // Split-K over t: slice s stores its partial product to the slab C + s*I*J (plain stores; see uc_splitk_reduce).
 #include "common.h"
-#include "knobs.h"
+#include "gemm_tn_plan.h"
+
+#include <mutex>
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
@@ -63,7 +65,7 @@ __device__ __forceinline__ bf16x4_t tn_relu4(bf16x4_t v) {
     return __builtin_bit_cast(bf16x4_t, u);
 }
 
-#define TN_BN 256
+#define TN_BN UC_TN_BN
 
 // BM_ x 256 x 64 workgroup tile (BM_ = 256: 4x4 waves, BM_ = 128: 2x4 waves — for I <= 128, e.g. the 128-channel convs of the
 // DPT regressor, where a 256-row tile would be half empty); every wave owns 64 x 64 outputs.
@@ -73,6 +75,7 @@ __global__ __launch_bounds__(BM_ * 4) void gemm_tn_kernel(TnParams p) {
     constexpr int A_ROW = BM_ * 2;                   // bytes per t-row of the A tile (512 / 256); B rows are 512 B
     constexpr int A_TILE = 64 * A_ROW;
     constexpr int STAGE = A_TILE + 64 * TN_BN * 2;   // A tile then B tile
+    static_assert(2 * STAGE == uc_tn_lds_bytes(BM_), "the plan's lds_bytes is this kernel's two stages");
     constexpr int NI_A = A_TILE / 1024;              // 1-KiB DMA instructions of the A tile (32 / 16)
     constexpr int PER = (NI_A + 32) / NW;            // per wave (4 / 6)
     constexpr int RA = 1024 / A_ROW;                 // A rows per DMA instruction (2 / 4)
@@ -241,17 +244,6 @@ __global__ __launch_bounds__(BM_ * 4) void gemm_tn_kernel(TnParams p) {
     }
 }
 
-// shapes the row-walking conv weight-gradient kernel takes (everything else: the implicit-im2col kernel)
-static inline bool uc_conv_dw_rows_ok(int64_t Cout, int H, int W, int Cin, int stride) {
-    return uc_knobs().conv_dw_rows && stride == 1 && W % 64 == 0 && Cin % 128 == 0 && Cout % 128 == 0 && H > 0;
-}
-
-extern "C" int uc_gemm_tn_conv_tiles(int64_t Cout, int conv_H, int conv_W, int conv_Cin, int conv_stride) {
-    if (uc_conv_dw_rows_ok(Cout, conv_H, conv_W, conv_Cin, conv_stride)) return (int)(3 * (Cout / 128) * (conv_Cin / 128));
-    const int64_t J = 9 * (int64_t)conv_Cin;
-    return (int)(ceil_div64(Cout, Cout <= 128 ? 128 : 256) * ceil_div64(J, TN_BN));
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // Weight gradient of a 3x3 / pad 1 / stride 1 conv on maps whose width is a multiple of 64 — the DPT head's big convs — WITHOUT
 // the implicit im2col of the kernel above.  There a stage is 64 pixels x 256 im2col columns: every 16 bytes of it are located by
@@ -277,6 +269,7 @@ struct CdwParams {
 
 __global__ __launch_bounds__(512) void conv_dw_rows_kernel(CdwParams p) {
     constexpr int ROWB = 256, A_TILE = 64 * ROWB, B_ROWS = 68, STAGE = A_TILE + B_ROWS * ROWB, NST = 3;
+    static_assert(NST * STAGE == UC_TN_ROWS_LDS_BYTES, "the plan's lds_bytes is this kernel's three stages");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -433,68 +426,79 @@ __global__ __launch_bounds__(512) void conv_dw_rows_kernel(CdwParams p) {
         }
 }
 
-extern "C" int uc_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t T, int64_t I, int64_t J, int conv_B,
-                          int conv_H, int conv_W, int conv_Cin, int conv_stride, int relu_b, float* C, float* colsum_a,
-                          int colsum_atomic, int split_k, uc_stream_t stream) {
-    UC_REQUIRE(A && B && C, "uc_gemm_tn: null pointer");
-    UC_REQUIRE(T > 0 && I >= 8 && J >= 8 && I % 8 == 0 && J % 8 == 0 && lda % 8 == 0, "uc_gemm_tn: I, J and lda must be multiples of 8");
-    UC_REQUIRE(split_k >= 1 && split_k <= 1024, "uc_gemm_tn: bad split_k");
-    UC_REQUIRE(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0), "uc_gemm_tn: operands must be 16-byte aligned");
-    TnParams p;
-    p.A = (const bf16_t*)A; p.lda = lda; p.B = (const bf16_t*)B; p.ldb = ldb; p.T = T; p.I = I; p.J = J;
-    p.conv = conv_B > 0 ? 1 : 0;
-    p.cB = conv_B; p.cH = conv_H; p.cW = conv_W; p.cCin = conv_Cin; p.cStride = conv_stride; p.relu_b = relu_b ? 1 : 0;
-    p.cHo = p.cWo = 0;
-    if (p.conv) {
-        UC_REQUIRE(conv_H > 0 && conv_W > 0 && conv_Cin > 0 && conv_Cin % 8 == 0 && conv_stride > 0, "uc_gemm_tn: bad conv geometry (Cin must be a multiple of 8)");
-        p.cHo = (conv_H - 1) / conv_stride + 1;
-        p.cWo = (conv_W - 1) / conv_stride + 1;
-        UC_REQUIRE(T == (int64_t)conv_B * p.cHo * p.cWo && J == 9 * (int64_t)conv_Cin, "uc_gemm_tn: conv shape mismatch");
-        UC_REQUIRE(T < (int64_t)1 << 31, "uc_gemm_tn: too many pixels");
-        p.dWo = uc_make_fastdiv((unsigned)p.cWo); p.dHo = uc_make_fastdiv((unsigned)p.cHo); p.dCin = uc_make_fastdiv((unsigned)conv_Cin);
+// Every shape condition of a descriptor — what uc_gemm_tn_query rejects, and uc_gemm_tn before it looks at a pointer or launches.
+static int tn_check_shape(const uc_gemm_tn_desc* d) {
+    UC_REQUIRE(d, "uc_gemm_tn: null descriptor");
+    UC_REQUIRE(d->T > 0 && d->I >= 8 && d->J >= 8 && d->I % 8 == 0 && d->J % 8 == 0 && d->lda % 8 == 0, "uc_gemm_tn: I, J and lda must be multiples of 8");
+    if (d->conv_B > 0) {
+        UC_REQUIRE(d->conv_H > 0 && d->conv_W > 0 && d->conv_Cin > 0 && d->conv_Cin % 8 == 0 && d->conv_stride > 0, "uc_gemm_tn: bad conv geometry (Cin must be a multiple of 8)");
+        const int Ho = (d->conv_H - 1) / d->conv_stride + 1, Wo = (d->conv_W - 1) / d->conv_stride + 1;
+        UC_REQUIRE(d->T == (int64_t)d->conv_B * Ho * Wo && d->J == 9 * (int64_t)d->conv_Cin, "uc_gemm_tn: conv shape mismatch");
+        UC_REQUIRE(d->T < (int64_t)1 << 31, "uc_gemm_tn: too many pixels");
+        if (uc_tn_conv_rows_ok(*d))
+            UC_REQUIRE((int64_t)d->conv_B * d->conv_H * (d->conv_W / UC_TN_ROWS_SEG) < (int64_t)1 << 31, "uc_gemm_tn: too many pixels");
     } else {
-        UC_REQUIRE(ldb % 8 == 0 && ldb >= J && !relu_b, "uc_gemm_tn: ldb must be a multiple of 8");
+        UC_REQUIRE(d->ldb % 8 == 0 && d->ldb >= d->J && !d->relu_b, "uc_gemm_tn: ldb must be a multiple of 8");
     }
-    p.C = C; p.colsum = colsum_a; p.colsum_atomic = colsum_atomic ? 1 : 0; p.split_k = split_k;
+    return UC_OK;
+}
+
+extern "C" int uc_gemm_tn_query(const uc_gemm_tn_desc* d, int* tiles, int* split_k) {
+    if (const int rc = tn_check_shape(d)) return rc;
+    if (tiles) *tiles = uc_gemm_tn_plan(*d).tiles;
+    if (split_k) *split_k = uc_gemm_tn_auto_split_k(*d);
+    return UC_OK;
+}
+
+extern "C" int uc_gemm_tn(const uc_gemm_tn_desc* d, uc_stream_t stream) {
+    UC_REQUIRE(d, "uc_gemm_tn: null descriptor");
+    UC_REQUIRE(d->A && d->B && d->C, "uc_gemm_tn: null pointer");
+    if (const int rc = tn_check_shape(d)) return rc;
+    UC_REQUIRE(d->split_k >= 1 && d->split_k <= 1024, "uc_gemm_tn: bad split_k");
+    UC_REQUIRE(((uintptr_t)d->A % 16 == 0) && ((uintptr_t)d->B % 16 == 0) && ((uintptr_t)d->C % 16 == 0), "uc_gemm_tn: operands must be 16-byte aligned");
+    const GemmTnPlan plan = uc_gemm_tn_plan(*d);
+
+    static std::once_flag lds_once;   // (the launches come from two streams' threads)
+    std::call_once(lds_once, [] {
+        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, uc_tn_lds_bytes(256));
+        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, uc_tn_lds_bytes(256));
+        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, uc_tn_lds_bytes(128));
+        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, uc_tn_lds_bytes(128));
+        (void)hipFuncSetAttribute((const void*)conv_dw_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, UC_TN_ROWS_LDS_BYTES);
+    });
+
+    const dim3 grid(plan.grid), block(plan.block);
     hipStream_t st = (hipStream_t)stream;
-    if (p.conv && uc_conv_dw_rows_ok(I, conv_H, conv_W, conv_Cin, conv_stride) && lda % 8 == 0) {
-        // stride-1 convs on maps a multiple of 64 wide with whole 128-channel tiles: one kernel row per workgroup, taps as row shifts
+    if (plan.kernel == UC_TN_CONV_ROWS) {
         CdwParams c;
-        c.A = (const bf16_t*)A; c.lda = lda; c.X = (const bf16_t*)B; c.H = conv_H; c.W = conv_W; c.Cin = conv_Cin; c.relu_b = relu_b ? 1 : 0;
-        c.I = I; c.J = J; c.nseg = (int64_t)conv_B * conv_H * (conv_W / 64);
-        UC_REQUIRE(c.nseg < (int64_t)1 << 31, "uc_gemm_tn: too many pixels");
-        c.dSpr = uc_make_fastdiv((unsigned)(conv_W / 64)); c.dH = uc_make_fastdiv((unsigned)conv_H);
-        c.C = C; c.colsum = colsum_a; c.colsum_atomic = colsum_atomic ? 1 : 0; c.split_k = split_k;
-        c.tiles_i = (int)(I / 128); c.tiles_c = conv_Cin / 128;
-        constexpr int SMC = 3 * (64 * 256 + 68 * 256);
-        static bool cattr = false;
-        if (!cattr) {
-            (void)hipFuncSetAttribute((const void*)conv_dw_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMC);
-            cattr = true;
-        }
-        hipLaunchKernelGGL(conv_dw_rows_kernel, dim3((unsigned)(3 * c.tiles_i * c.tiles_c) * (unsigned)split_k), dim3(512), SMC, st, c);
+        c.A = (const bf16_t*)d->A; c.lda = d->lda; c.X = (const bf16_t*)d->B;
+        c.H = d->conv_H; c.W = d->conv_W; c.Cin = d->conv_Cin; c.relu_b = d->relu_b ? 1 : 0;
+        c.I = d->I; c.J = d->J; c.nseg = (int64_t)d->conv_B * d->conv_H * (d->conv_W / UC_TN_ROWS_SEG);
+        c.dSpr = uc_make_fastdiv((unsigned)(d->conv_W / UC_TN_ROWS_SEG)); c.dH = uc_make_fastdiv((unsigned)d->conv_H);
+        c.C = d->C; c.colsum = d->colsum_a; c.colsum_atomic = d->colsum_atomic ? 1 : 0; c.split_k = d->split_k;
+        c.tiles_i = plan.tiles_i; c.tiles_c = plan.tiles_j;
+        hipLaunchKernelGGL(conv_dw_rows_kernel, grid, block, plan.lds_bytes, st, c);
         UC_CHECK_LAUNCH("uc_gemm_tn(conv rows)");
         return UC_OK;
     }
-    const bool narrow = I <= 128;                   // half-height tile for the 128-row products (no half-empty MFMA tiles)
-    p.tiles_i = (int)ceil_div64(I, narrow ? 128 : 256);
-    p.tiles_j = (int)ceil_div64(J, TN_BN);
-    constexpr int SM256 = 2 * (64 * 256 * 2 + 64 * TN_BN * 2), SM128 = 2 * (64 * 128 * 2 + 64 * TN_BN * 2);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM256);
-        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SM256);
-        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SM128);
-        (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SM128);
-        attr_set = true;
+    TnParams p;
+    p.A = (const bf16_t*)d->A; p.lda = d->lda; p.B = (const bf16_t*)d->B; p.ldb = d->ldb; p.T = d->T; p.I = d->I; p.J = d->J;
+    p.conv = d->conv_B > 0 ? 1 : 0;
+    p.cB = d->conv_B; p.cH = d->conv_H; p.cW = d->conv_W; p.cCin = d->conv_Cin; p.cStride = d->conv_stride; p.relu_b = d->relu_b ? 1 : 0;
+    p.cHo = p.cWo = 0;
+    if (p.conv) {
+        p.cHo = (d->conv_H - 1) / d->conv_stride + 1;
+        p.cWo = (d->conv_W - 1) / d->conv_stride + 1;
+        p.dWo = uc_make_fastdiv((unsigned)p.cWo); p.dHo = uc_make_fastdiv((unsigned)p.cHo); p.dCin = uc_make_fastdiv((unsigned)d->conv_Cin);
     }
-    const dim3 grid((unsigned)p.tiles_i * p.tiles_j * (unsigned)split_k);
-    if (narrow) {
-        if (p.conv) hipLaunchKernelGGL((gemm_tn_kernel<128, true>), grid, dim3(512), SM128, st, p);
-        else hipLaunchKernelGGL((gemm_tn_kernel<128, false>), grid, dim3(512), SM128, st, p);
-    } else {
-        if (p.conv) hipLaunchKernelGGL((gemm_tn_kernel<256, true>), grid, dim3(1024), SM256, st, p);
-        else hipLaunchKernelGGL((gemm_tn_kernel<256, false>), grid, dim3(1024), SM256, st, p);
+    p.C = d->C; p.colsum = d->colsum_a; p.colsum_atomic = d->colsum_atomic ? 1 : 0; p.split_k = d->split_k;
+    p.tiles_i = plan.tiles_i; p.tiles_j = plan.tiles_j;
+    switch (plan.kernel) {
+        case UC_TN_256_DENSE: hipLaunchKernelGGL((gemm_tn_kernel<256, false>), grid, block, plan.lds_bytes, st, p); break;
+        case UC_TN_256_CONV: hipLaunchKernelGGL((gemm_tn_kernel<256, true>), grid, block, plan.lds_bytes, st, p); break;
+        case UC_TN_128_DENSE: hipLaunchKernelGGL((gemm_tn_kernel<128, false>), grid, block, plan.lds_bytes, st, p); break;
+        case UC_TN_128_CONV: hipLaunchKernelGGL((gemm_tn_kernel<128, true>), grid, block, plan.lds_bytes, st, p); break;
+        case UC_TN_CONV_ROWS: break;   // (launched above)
     }
     UC_CHECK_LAUNCH("uc_gemm_tn");
     return UC_OK;

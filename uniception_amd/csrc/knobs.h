@@ -14,7 +14,6 @@
 
 struct UcKnobs {
     int gemm_group_m;        // UC_GEMM_GROUP_M      row panels per L2-sharing tile group (default 4)
-    int conv_dw_rows;        // UC_CONV_DW_ROWS      row-walking conv weight-gradient kernel where the shape allows (default 1; 0: implicit im2col everywhere)
     int gemm_4wave;          // UC_GEMM_4WAVE        four-wave 256x256 kernel (128x128 wave tiles, asm K-loop): 0 off, 1 bf16-store family, 2 + bf16 stream, 3 all (default)
     int attn_prio;           // UC_ATTN_PRIO         eight-wave attention: static s_setprio 1 for waves 4-7 (default 0)
     int bilinear_rows2;      // UC_BILINEAR_ROWS2    output rows per work item of the upsampling form (default 4)

@@ -13,7 +13,7 @@ import contextlib
 import torch
 
 from . import _lib
-from ._lib import (AttnBwdDesc, AttnDesc, GemmDesc, UC_A_CONV3X3, UC_A_DENSE, UC_ACT_GELU_ERF, UC_ACT_NONE, UC_ACT_RELU,
+from ._lib import (AttnBwdDesc, AttnDesc, GemmDesc, GemmTnDesc, UC_A_CONV3X3, UC_A_DENSE, UC_ACT_GELU_ERF, UC_ACT_NONE, UC_ACT_RELU,
                    UC_BF16, UC_F16, UC_F32, UC_V_PACKED_T, UC_V_ROWMAJOR, UcHipError)
 
 _DT = {torch.float32: UC_F32, torch.bfloat16: UC_BF16, torch.float16: UC_F16}
@@ -837,38 +837,53 @@ def layernorm_bwd(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, eps: f
     return (dx, twin if twin is not None else dx) if bf16_twin else dx
 
 
-def gemm_tn(a: torch.Tensor, b: torch.Tensor, split_k: int = 1, conv: Optional[Tuple[int, bool]] = None,
+def _gemm_tn_desc(a: torch.Tensor, b: torch.Tensor, conv: Optional[Tuple[int, bool]]) -> GemmTnDesc:
+    "Operands and shape of a gemm_tn / gemm_tn_query call as a uc_gemm_tn_desc (outputs and split_k still unset)."
+    _need_gpu(a, b)
+    assert a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.dim() == 2 and a.stride(1) == 1
+    T, I = a.shape
+    d = GemmTnDesc(A=a.data_ptr(), lda=a.stride(0), B=b.data_ptr(), T=T, I=I)
+    if conv is None:
+        assert b.dim() == 2 and b.stride(1) == 1 and b.shape[0] == T
+        d.J, d.ldb = b.shape[1], b.stride(0)
+    else:
+        stride, relu = conv
+        assert b.dim() == 4 and b.is_contiguous()
+        d.conv_B, d.conv_H, d.conv_W, d.conv_Cin = b.shape
+        d.J, d.conv_stride, d.relu_b = 9 * b.shape[3], stride, 1 if relu else 0
+    return d
+
+
+def _gemm_tn_query(d: GemmTnDesc) -> Tuple[int, int]:
+    tiles, split_k = C.c_int(0), C.c_int(0)
+    _lib.check(_lib.load().uc_gemm_tn_query(C.byref(d), C.byref(tiles), C.byref(split_k)), "uc_gemm_tn_query")
+    return tiles.value, split_k.value
+
+
+def gemm_tn_query(a: torch.Tensor, b: torch.Tensor, conv: Optional[Tuple[int, bool]] = None) -> Tuple[int, int]:
+    "(workgroups one K-slice of gemm_tn(a, b, conv=conv) occupies, the split_k gemm_tn takes when none is given) — uc_gemm_tn_query."
+    return _gemm_tn_query(_gemm_tn_desc(a, b, conv))
+
+
+def gemm_tn(a: torch.Tensor, b: torch.Tensor, split_k: Optional[int] = None, conv: Optional[Tuple[int, bool]] = None,
             colsum: bool = False, colsum_into: Optional[torch.Tensor] = None):
     """Weight-gradient contraction over the slow axis: returns fp32 slabs [split_k, I, J] of  sum_t a[t,i] * b[t,j].
     a: [T,I] bf16 (unit column stride).  b: [T,J] bf16, or with conv=(stride, relu) the NHWC input [B,H,W,Cin] of a
     3x3/pad-1 conv whose im2col ([T, 9*Cin], T = output pixels) is formed implicitly.
+    split_k=None: the slice count the library recommends for this shape (uc_gemm_tn_query).
     colsum=True: also returns slabs [split_k, I] of sum_t a[t,i] (the bias gradient).
     colsum_into: fp32 [I] buffer that receives += sum_t a[t,i] atomically instead (e.g. the bias's gradient buffer)."""
-    _need_gpu(a, b)
-    assert a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.dim() == 2 and a.stride(1) == 1
-    T, I = a.shape
-    if conv is None:
-        assert b.dim() == 2 and b.stride(1) == 1 and b.shape[0] == T
-        J, ldb, cg, relu = b.shape[1], b.stride(0), (0, 0, 0, 0, 0), 0
-    else:
-        stride, relu = conv
-        assert b.dim() == 4 and b.is_contiguous()
-        Bc, Hc, Wc, Cin = b.shape
-        J, ldb, cg = 9 * Cin, 0, (Bc, Hc, Wc, Cin, stride)
-    out = torch.empty((split_k, I, J), dtype=torch.float32, device=a.device)
+    d = _gemm_tn_desc(a, b, conv)
+    d.split_k = _gemm_tn_query(d)[1] if split_k is None else split_k
+    out = torch.empty((d.split_k, d.I, d.J), dtype=torch.float32, device=a.device)
     if colsum_into is not None:
-        assert colsum_into.dtype == torch.float32 and colsum_into.is_contiguous() and colsum_into.numel() == I and not colsum
-        cs, atomic = colsum_into, 1
+        assert colsum_into.dtype == torch.float32 and colsum_into.is_contiguous() and colsum_into.numel() == d.I and not colsum
+        cs, d.colsum_atomic = colsum_into, 1
     else:
-        cs, atomic = (torch.empty((split_k, I), dtype=torch.float32, device=a.device) if colsum else None), 0
-    _lib.check(_lib.load().uc_gemm_tn(a.data_ptr(), a.stride(0), b.data_ptr(), ldb, T, I, J, *cg, 1 if relu else 0, out.data_ptr(),
-                                      _p(cs), atomic, split_k, _stream()), "uc_gemm_tn")
+        cs = torch.empty((d.split_k, d.I), dtype=torch.float32, device=a.device) if colsum else None
+    d.C, d.colsum_a = out.data_ptr(), _p(cs)
+    _lib.check(_lib.load().uc_gemm_tn(C.byref(d), _stream()), "uc_gemm_tn")
     return (out, cs) if colsum else out
-
-
-def gemm_tn_conv_tiles(Cout: int, H: int, W: int, Cin: int, stride: int) -> int:
-    "Workgroups one K-slice of gemm_tn(conv=...) occupies (uc_gemm_tn_conv_tiles): sizes split_k."
-    return int(_lib.load().uc_gemm_tn_conv_tiles(int(Cout), int(H), int(W), int(Cin), int(stride)))
 
 
 def splitk_reduce(ws: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
