@@ -330,18 +330,8 @@ def _norm_or_none(norm):
     return None if norm is None or isinstance(norm, nn.Identity) else norm
 
 
-def _qknorm_fwd(view4, norm):
-    """qk_norm (utils/transformer_blocks.py:196-197, 229): LayerNorm over head_dim of a [B, N, H, Dh] view of q / k, BEFORE the positional
-    encoding -> contiguous [B, N, H, Dh] in the same dtype."""
-    if not isinstance(norm, nn.LayerNorm) or norm.weight is None or norm.bias is None:
-        raise UcHipError(f"qk_norm with {type(norm).__name__} has no HIP path (nn.LayerNorm with affine parameters only)")
-    pre = view4.contiguous()
-    Dh = pre.shape[-1]
-    return ops.layernorm(pre.view(-1, Dh), norm.weight.detach().float(), norm.bias.detach().float(), norm.eps, pre.dtype).view(pre.shape)
-
-
 def _qknorm_bwd(view4, norm, dn):
-    "(d view4 [contiguous], dgamma, dbeta) of _qknorm_fwd: uc_layernorm_bwd over B N H rows of head_dim (its 64-wide kernel)."
+    "(d view4 [contiguous], dgamma, dbeta) of engine.qk_layernorm: uc_layernorm_bwd over B N H rows of head_dim (its 64-wide kernel)."
     pre = view4.contiguous()
     Dh = pre.shape[-1]
     g = norm.weight.detach().float()
@@ -557,8 +547,79 @@ def _unfold_layerscale(lin, gamma, dWf, dbf):
 
 
 # =================================================================================================================
-# pre-LN sub-layers of the transformer blocks
+# pre-LN sub-layers of the transformer blocks: the steps the four Functions share, then the Functions
 # =================================================================================================================
+def _rope_in_gemm(rope, qn, kn, dt, Dh) -> bool:
+    "Does the q / k GEMM's epilogue rotate its output (bf16 with a rope and no qk_norm)?  Else _prep_qk rotates behind the GEMM."
+    if qn is not None or kn is not None or dt != torch.bfloat16 or rope is None:
+        return False
+    if Dh != 64:
+        raise UcHipError(f"bf16 attention needs head_dim 64 (got {Dh})")
+    return True
+
+
+def _prep_qk(q4, k4, qn, kn, rope, qpos, kpos, in_gemm: bool):
+    """What lies between the q / k GEMM(s) and the attention forward, on the [B, N, H, Dh] views of the GEMM output.  qk_norm: q / k are
+    normalised over head_dim BEFORE the positional encoding — the unfused route: the GEMM output keeps the RAW q | k, and the
+    normalised, rotated copies the attention sees are returned (to be saved next to it).  Otherwise the views are rotated in place,
+    unless the GEMM's epilogue did (`in_gemm`, see _rope_in_gemm), and None is returned."""
+    if qn is None and kn is None:
+        if rope is not None and not in_gemm:
+            ops.rope_2d_(q4, qpos.contiguous(), rope.base, rope.F0)
+            ops.rope_2d_(k4, kpos.contiguous(), rope.base, rope.F0)
+        return None
+    qx = engine.qk_layernorm(q4, qn) if qn is not None else q4.contiguous()
+    kx = engine.qk_layernorm(k4, kn) if kn is not None else k4.contiguous()
+    if rope is not None:
+        ops.rope_2d_(qx, qpos.contiguous(), rope.base, rope.F0)
+        ops.rope_2d_(kx, kpos.contiguous(), rope.base, rope.F0)
+    return qx, kx
+
+
+def _attention_bwd_block(q4, k4, v4, qkn, o, do4, lse, scale, dq4, dk4, dv4, rope, qpos, kpos, dt, qn, kn, adrop):
+    """Backward of _prep_qk + attention: fills the views dq4 / dk4 / dv4 of the gradient of the q / k / v GEMM output (q4, k4, v4: views of
+    that output; qkn: _prep_qk's copies or None) and returns (dq_norm.weight, dq_norm.bias, dk_norm.weight, dk_norm.bias)."""
+    fused_rope = _bwd_rope(rope, qpos, kpos, dt)      # (bf16: the inverse rotation of dq / dk rides in the backward kernels)
+    qa, ka = qkn if qkn else (q4, k4)
+    dqa, dka = (torch.empty_like(qa), torch.empty_like(ka)) if qkn else (dq4, dk4)
+    ops.attention_bwd(qa, ka, v4, o, do4, lse, scale, out=(dqa, dka, dv4), rope=fused_rope, dropout=adrop)
+    if fused_rope is None:
+        _rope_inverse_(dqa, qpos, rope)
+        _rope_inverse_(dka, kpos, rope)
+    dqn_w = dqn_b = dkn_w = dkn_b = None
+    if qkn:
+        if qn is not None:
+            dqa, dqn_w, dqn_b = _qknorm_bwd(q4, qn, dqa)
+        if kn is not None:
+            dka, dkn_w, dkn_b = _qknorm_bwd(k4, kn, dka)
+        dq4.copy_(dqa)
+        dk4.copy_(dka)
+    return dqn_w, dqn_b, dkn_w, dkn_b
+
+
+def _out_linear_bwd(dyb, a2d, lin, gamma, has_bias, dt):
+    """(dW, db, dgamma, W^T for the data gradient) of a sub-layer's output linear (proj, fc2, w3) on the operand a2d.  gamma: the
+    LayerScale folded into it (see above) — gradient of the folded weight, unfolded into d W, d b, d gamma — or None."""
+    if gamma is None:
+        dW, db = _wgrad(dyb, a2d, dt, has_bias, sink=[(lin.weight, 0, lin.weight.shape[0])], bias_sink=[lin.bias])
+        return dW, db, None, lin_weight_t(lin, dt)
+    dW, db = _wgrad(dyb, a2d, dt, has_bias)
+    return _unfold_layerscale(lin, gamma, dW, db) + (_folded_weight_t(lin, gamma, dt),)
+
+
+def _ln_bwd_tail(x2d, ln, g, dh, dres=None, dt=None, residual: bool = True):
+    """(dx, dgamma, dbeta) of the sub-layer's LayerNorm, dgamma / dbeta None where the kernel added them into the parameters' own
+    gradient buffers (_ln_grad_targets).  residual: the residual-stream form (_ln_bwd_residual: d(x_out) = dres added in the same pass,
+    a bf16 twin of dx where the next backward wants one); False: the LayerNorm of tokens that are not this sub-layer's stream (the
+    other view's, in cross-attention) — the plain kernel call."""
+    dg, db, sunk = _ln_grad_targets(ln, g)
+    if residual:
+        dx = _ln_bwd_residual(x2d, g, dh, ln.eps, dg, db, dres, dt)
+    else:
+        dx = ops.layernorm_bwd(x2d, g, dh, ln.eps, dg, db)
+    return (dx, None, None) if sunk else (dx, dg, db)
+
+
 @_sink_aware
 class SelfAttnSubLayerFn(Function):
     """x + proj(SDPA(rope(q), rope(k), v)),  q,k,v = qkv(LN(x))   (blocks.py:105-125,154-158; transformer_blocks.py:214-260)."""
@@ -575,29 +636,10 @@ class SelfAttnSubLayerFn(Function):
         h = ops.layernorm(x2d, g, bta, ln.eps, dt)
         wq, bq = engine.lin_weights(qkv, dt)
         wp, bp = engine.lin_weights(proj, dt) if gamma is None else engine.layerscale_lin_weights(proj, gamma, dt)
-        qkn = None
-        if qn is not None or kn is not None:
-            # qk_norm: q / k are normalised over head_dim BEFORE the positional encoding — the unfused route (t keeps the RAW q | k | v;
-            # the normalised, rotated q / k the attention sees are saved next to it)
-            t = ops.gemm(h, wq, bq)
-            t5 = t.view(B, N, 3, H, Dh)
-            qx = _qknorm_fwd(t5[:, :, 0], qn) if qn is not None else t5[:, :, 0].contiguous()
-            kx = _qknorm_fwd(t5[:, :, 1], kn) if kn is not None else t5[:, :, 1].contiguous()
-            if rope is not None:
-                ops.rope_2d_(qx, pos.contiguous(), rope.base, rope.F0)
-                ops.rope_2d_(kx, pos.contiguous(), rope.base, rope.F0)
-            qkn = (qx, kx)
-        elif dt == torch.bfloat16 and rope is not None:
-            if Dh != 64:
-                raise UcHipError(f"bf16 attention needs head_dim 64 (got {Dh})")
-            t = ops.gemm(h, wq, bq, rope=engine._rope_epilogue(rope, engine._pos2d(pos), 2 * Ca))
-            t5 = t.view(B, N, 3, H, Dh)
-        else:
-            t = ops.gemm(h, wq, bq)
-            t5 = t.view(B, N, 3, H, Dh)
-            if rope is not None:
-                ops.rope_2d_(t5[:, :, 0], pos.contiguous(), rope.base, rope.F0)
-                ops.rope_2d_(t5[:, :, 1], pos.contiguous(), rope.base, rope.F0)
+        in_gemm = _rope_in_gemm(rope, qn, kn, dt, Dh)
+        t = ops.gemm(h, wq, bq, rope=engine._rope_epilogue(rope if in_gemm else None, pos, 2 * Ca))
+        t5 = t.view(B, N, 3, H, Dh)
+        qkn = _prep_qk(t5[:, :, 0], t5[:, :, 1], qn, kn, rope, pos, pos, in_gemm)
         lse = torch.empty((B, H, N), dtype=torch.float32, device=x2d.device)
         o = _attention_fwd(*(qkn if qkn is not None else (t5[:, :, 0], t5[:, :, 1])), t5[:, :, 2], scale, lse, adrop)
         if drops is not None and drops.has_out:
@@ -617,7 +659,7 @@ class SelfAttnSubLayerFn(Function):
         ln, qkv, proj, B, N, H, rope, scale, dt, has_bq, has_bp, qn, kn, has_qkn, dspec = ctx.meta
         drops, saved = _drops_restore(dspec, ctx.saved_tensors)
         x2d, g, h, t, o, lse, pos, *rest = saved
-        qx, kx = (rest[0], rest[1]) if has_qkn else (None, None)
+        qkn = rest[:2] if has_qkn else []
         rest = rest[2:] if has_qkn else rest
         gamma = rest[0] if rest else None
         M, C = x2d.shape
@@ -627,43 +669,15 @@ class SelfAttnSubLayerFn(Function):
         dyb = _as_dt(dxo, dt)
         if drops is not None and drops.has_out:
             dyb = _drop_out(dyb, drops)
-        dgamma = None
-        if gamma is None:
-            dWp, dbp = _wgrad(dyb, o.view(M, Ca), dt, has_bp, sink=[(proj.weight, 0, C)], bias_sink=[proj.bias])
-            do = ops.gemm(dyb, lin_weight_t(proj, dt))
-        else:
-            dWp, dbp = _wgrad(dyb, o.view(M, Ca), dt, has_bp)
-            dWp, dbp, dgamma = _unfold_layerscale(proj, gamma, dWp, dbp)
-            do = ops.gemm(dyb, _folded_weight_t(proj, gamma, dt))
+        dWp, dbp, dgamma, wpt = _out_linear_bwd(dyb, o.view(M, Ca), proj, gamma, has_bp, dt)
+        do = ops.gemm(dyb, wpt)
         dt3 = torch.empty_like(t)
         d5, t5 = dt3.view(B, N, 3, H, Dh), t.view(B, N, 3, H, Dh)
-        fused_rope = _bwd_rope(rope, pos, pos, dt)      # (bf16: the inverse rotation of dq / dk rides in the backward kernels)
-        dqn_w = dqn_b = dkn_w = dkn_b = None
-        if has_qkn:
-            dqx, dkx = torch.empty_like(qx), torch.empty_like(kx)
-            ops.attention_bwd(qx, kx, t5[:, :, 2], o, do.view(B, N, H, Dh), lse, scale, out=(dqx, dkx, d5[:, :, 2]), rope=fused_rope,
-                              dropout=ctx.adrop)
-            if fused_rope is None:
-                _rope_inverse_(dqx, pos, rope)
-                _rope_inverse_(dkx, pos, rope)
-            if qn is not None:
-                dqx, dqn_w, dqn_b = _qknorm_bwd(t5[:, :, 0], qn, dqx)
-            if kn is not None:
-                dkx, dkn_w, dkn_b = _qknorm_bwd(t5[:, :, 1], kn, dkx)
-            d5[:, :, 0].copy_(dqx)
-            d5[:, :, 1].copy_(dkx)
-        else:
-            ops.attention_bwd(t5[:, :, 0], t5[:, :, 1], t5[:, :, 2], o, do.view(B, N, H, Dh), lse, scale,
-                              out=(d5[:, :, 0], d5[:, :, 1], d5[:, :, 2]), rope=fused_rope, dropout=ctx.adrop)
-            if fused_rope is None:
-                _rope_inverse_(d5[:, :, 0], pos, rope)
-                _rope_inverse_(d5[:, :, 1], pos, rope)
+        dqn_w, dqn_b, dkn_w, dkn_b = _attention_bwd_block(t5[:, :, 0], t5[:, :, 1], t5[:, :, 2], qkn, o, do.view(B, N, H, Dh), lse, scale,
+                                                          d5[:, :, 0], d5[:, :, 1], d5[:, :, 2], rope, pos, pos, dt, qn, kn, ctx.adrop)
         dWq, dbq = _wgrad(dt3, h, dt, has_bq, sink=[(qkv.weight, 0, 3 * Ca)], bias_sink=[qkv.bias])
         dh = ops.gemm(dt3, lin_weight_t(qkv, dt))
-        dg, db, sunk = _ln_grad_targets(ln, g)
-        dx = _ln_bwd_residual(x2d, g, dh, ln.eps, dg, db, dxo, dt)
-        if sunk:
-            dg = db = None
+        dx, dg, db = _ln_bwd_tail(x2d, ln, g, dh, dxo, dt)
         return (dx, dg, db, dWq, dbq, dWp, dbp) + (None,) * 10 + (dgamma, dqn_w, dqn_b, dkn_w, dkn_b, None, None, None, None)
 
 
@@ -703,29 +717,11 @@ class CrossAttnSubLayerFn(Function):
         wq, bq = engine.lin_weights(projq, dt)
         wkv, bkv = engine.kv_weights(projk, projv, dt)
         wp, bp = engine.lin_weights(proj, dt) if gamma is None else engine.layerscale_lin_weights(proj, gamma, dt)
-        qkn = None
-        if qn is not None or kn is not None:     # qk_norm: the unfused route (see SelfAttnSubLayerFn)
-            q = ops.gemm(hq, wq, bq)
-            kv = ops.gemm(hy, wkv, bkv)
-            q4, k4 = q.view(B, Nq, H, Dh), kv.view(B, Nk, 2, H, Dh)[:, :, 0]
-            qx = _qknorm_fwd(q4, qn) if qn is not None else q4.contiguous()
-            kx = _qknorm_fwd(k4, kn) if kn is not None else k4.contiguous()
-            if rope is not None:
-                ops.rope_2d_(qx, qpos.contiguous(), rope.base, rope.F0)
-                ops.rope_2d_(kx, kpos.contiguous(), rope.base, rope.F0)
-            qkn = (qx, kx)
-        elif dt == torch.bfloat16 and rope is not None:
-            if Dh != 64:
-                raise UcHipError(f"bf16 attention needs head_dim 64 (got {Dh})")
-            q = ops.gemm(hq, wq, bq, rope=engine._rope_epilogue(rope, engine._pos2d(qpos), C))
-            kv = ops.gemm(hy, wkv, bkv, rope=engine._rope_epilogue(rope, engine._pos2d(kpos), C))
-        else:
-            q = ops.gemm(hq, wq, bq)
-            kv = ops.gemm(hy, wkv, bkv)
-            if rope is not None:
-                ops.rope_2d_(q.view(B, Nq, H, Dh), qpos.contiguous(), rope.base, rope.F0)
-                ops.rope_2d_(kv.view(B, Nk, 2, H, Dh)[:, :, 0], kpos.contiguous(), rope.base, rope.F0)
+        in_gemm = _rope_in_gemm(rope, qn, kn, dt, Dh)
+        q = ops.gemm(hq, wq, bq, rope=engine._rope_epilogue(rope if in_gemm else None, qpos, C))
+        kv = ops.gemm(hy, wkv, bkv, rope=engine._rope_epilogue(rope if in_gemm else None, kpos, C))
         kv5 = kv.view(B, Nk, 2, H, Dh)
+        qkn = _prep_qk(q.view(B, Nq, H, Dh), kv5[:, :, 0], qn, kn, rope, qpos, kpos, in_gemm)
         lse = torch.empty((B, H, Nq), dtype=torch.float32, device=x2d.device)
         o = _attention_fwd(*(qkn if qkn is not None else (q.view(B, Nq, H, Dh), kv5[:, :, 0])), kv5[:, :, 1], scale, lse, adrop)
         ctx.adrop = adrop
@@ -755,58 +751,24 @@ class CrossAttnSubLayerFn(Function):
         dyb = _as_dt(dxo, dt)
         if drops is not None and drops.has_out:
             dyb = _drop_out(dyb, drops)
-        dgamma = None
-        if gamma is None:
-            dWp, dbp = _wgrad(dyb, o.view(Mq, C), dt, has_bp, sink=[(proj.weight, 0, C)], bias_sink=[proj.bias])
-            do = ops.gemm(dyb, lin_weight_t(proj, dt))
-        else:       # LayerScale folded into proj: gradient of the folded weight, unfolded into d W, d b, d gamma
-            dWp, dbp = _wgrad(dyb, o.view(Mq, C), dt, has_bp)
-            dWp, dbp, dgamma = _unfold_layerscale(proj, gamma, dWp, dbp)
-            do = ops.gemm(dyb, _folded_weight_t(proj, gamma, dt))
+        dWp, dbp, dgamma, wpt = _out_linear_bwd(dyb, o.view(Mq, C), proj, gamma, has_bp, dt)
+        do = ops.gemm(dyb, wpt)
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv)
         kv5, dkv5 = kv.view(B, Nk, 2, H, Dh), dkv.view(B, Nk, 2, H, Dh)
-        fused_rope = _bwd_rope(rope, qpos, kpos, dt)
-        dqn_w = dqn_b = dkn_w = dkn_b = None
-        if qkn:
-            qx, kx = qkn
-            dqx, dkx = torch.empty_like(qx), torch.empty_like(kx)
-            ops.attention_bwd(qx, kx, kv5[:, :, 1], o, do.view(B, Nq, H, Dh), lse, scale, out=(dqx, dkx, dkv5[:, :, 1]), rope=fused_rope,
-                              dropout=ctx.adrop)
-            if fused_rope is None:
-                _rope_inverse_(dqx, qpos, rope)
-                _rope_inverse_(dkx, kpos, rope)
-            if qn is not None:
-                dqx, dqn_w, dqn_b = _qknorm_bwd(q.view(B, Nq, H, Dh), qn, dqx)
-            if kn is not None:
-                dkx, dkn_w, dkn_b = _qknorm_bwd(kv5[:, :, 0], kn, dkx)
-            dq.view(B, Nq, H, Dh).copy_(dqx)
-            dkv5[:, :, 0].copy_(dkx)
-        else:
-            ops.attention_bwd(q.view(B, Nq, H, Dh), kv5[:, :, 0], kv5[:, :, 1], o, do.view(B, Nq, H, Dh), lse, scale,
-                              out=(dq.view(B, Nq, H, Dh), dkv5[:, :, 0], dkv5[:, :, 1]), rope=fused_rope, dropout=ctx.adrop)
-            if fused_rope is None:
-                _rope_inverse_(dq.view(B, Nq, H, Dh), qpos, rope)
-                _rope_inverse_(dkv5[:, :, 0], kpos, rope)
+        dqn_w, dqn_b, dkn_w, dkn_b = _attention_bwd_block(q.view(B, Nq, H, Dh), kv5[:, :, 0], kv5[:, :, 1], qkn, o, do.view(B, Nq, H, Dh), lse,
+                                                          scale, dq.view(B, Nq, H, Dh), dkv5[:, :, 0], dkv5[:, :, 1], rope, qpos, kpos, dt,
+                                                          qn, kn, ctx.adrop)
         # query side
         dWq, dbq = _wgrad(dq, hq, dt, has_bq, sink=[(projq.weight, 0, C)], bias_sink=[projq.bias])
         dhq = ops.gemm(dq, lin_weight_t(projq, dt))
-        dg, db, sunk = _ln_grad_targets(ln, g)
-        dx = _ln_bwd_residual(x2d, g, dhq, ln.eps, dg, db, dxo, dt)
-        if sunk:
-            dg = db = None
+        dx, dg, db = _ln_bwd_tail(x2d, ln, g, dhq, dxo, dt)
         # key/value side (the other view's tokens)
         dWkv, dbkv = _wgrad(dkv, hy, dt, has_bk or has_bv, sink=[(projk.weight, 0, C), (projv.weight, C, 2 * C)],
                             bias_sink=[projk.bias, projv.bias] if (has_bk and has_bv) else None)
         dhy = ops.gemm(dkv, kv_weight_t(projk, projv, dt), out_dtype=dt if lny is not None else y2d.dtype)
-        if lny is not None:
-            dgy, dby, sunk_y = _ln_grad_targets(lny, gy)
-            dy = ops.layernorm_bwd(y2d, gy, dhy, lny.eps, dgy, dby)
-            if sunk_y:
-                dgy = dby = None
-        else:
-            dgy = dby = None
-            dy = dhy
+        # (the other view's tokens are not this sub-layer's residual stream: no d(x_out) to add, no bf16 twin of dy)
+        dy, dgy, dby = _ln_bwd_tail(y2d, lny, gy, dhy, residual=False) if lny is not None else (dhy, None, None)
         dWk, dWv = (None, None) if dWkv is None else (dWkv[:C], dWkv[C:])
         dbk = dbkv[:C] if (has_bk and dbkv is not None) else None
         dbv = dbkv[C:] if (has_bv and dbkv is not None) else None
@@ -862,14 +824,7 @@ class MlpSubLayerFn(Function):
         dyb = _as_dt(dxo, dt)
         if drops is not None and drops.has_out:
             dyb = _drop_out(dyb, drops)
-        dgamma = None
-        if gamma is None:
-            dW2, db2 = _wgrad(dyb, a, dt, has_b2, sink=[(fc2.weight, 0, fc2.weight.shape[0])], bias_sink=[fc2.bias])
-            w2t = lin_weight_t(fc2, dt)
-        else:
-            dW2, db2 = _wgrad(dyb, a, dt, has_b2)
-            dW2, db2, dgamma = _unfold_layerscale(fc2, gamma, dW2, db2)
-            w2t = _folded_weight_t(fc2, gamma, dt)
+        dW2, db2, dgamma, w2t = _out_linear_bwd(dyb, a, fc2, gamma, has_b2, dt)
         if act != "none" and dt == torch.bfloat16 and w2t.shape[1] % 64 == 0:
             du = ops.gemm(dyb, w2t, dact=(u, act))          # act'(u) applied in the data-gradient GEMM's epilogue
         else:
@@ -879,10 +834,7 @@ class MlpSubLayerFn(Function):
             du = ops.mask_scale(du, drops.mid, 0, drops.mid_scale)
         dW1, db1 = _wgrad(du, h, dt, has_b1, sink=[(fc1.weight, 0, fc1.weight.shape[0])], bias_sink=[fc1.bias])
         dh = ops.gemm(du, lin_weight_t(fc1, dt))
-        dg, db, sunk = _ln_grad_targets(ln, g)
-        dx = _ln_bwd_residual(x2d, g, dh, ln.eps, dg, db, dxo, dt)
-        if sunk:
-            dg = db = None
+        dx, dg, db = _ln_bwd_tail(x2d, ln, g, dh, dxo, dt)
         return (dx, dg, db, dW1, db1, dW2, db2) + (None,) * 5 + (dgamma, None)
 
 
@@ -916,21 +868,11 @@ class SwiGLUSubLayerFn(Function):
         ln, w12, w3, dt, has_b1, has_b2 = ctx.meta
         dxo = _c(dxo)
         dyb = _as_dt(dxo, dt)
-        dgamma = None
-        if gamma is None:
-            dW2, db2 = _wgrad(dyb, a, dt, has_b2, sink=[(w3.weight, 0, w3.weight.shape[0])], bias_sink=[w3.bias])
-            w2t = lin_weight_t(w3, dt)
-        else:
-            dW2, db2 = _wgrad(dyb, a, dt, has_b2)
-            dW2, db2, dgamma = _unfold_layerscale(w3, gamma, dW2, db2)
-            w2t = _folded_weight_t(w3, gamma, dt)
+        dW2, db2, dgamma, w2t = _out_linear_bwd(dyb, a, w3, gamma, has_b2, dt)
         dtt = ops.swiglu_bwd(ops.gemm(dyb, w2t), t)
         dW1, db1 = _wgrad(dtt, h, dt, has_b1, sink=[(w12.weight, 0, w12.weight.shape[0])], bias_sink=[w12.bias])
         dh = ops.gemm(dtt, lin_weight_t(w12, dt))
-        dg, db, sunk = _ln_grad_targets(ln, g)
-        dx = _ln_bwd_residual(x2d, g, dh, ln.eps, dg, db, dxo, dt)
-        if sunk:
-            dg = db = None
+        dx, dg, db = _ln_bwd_tail(x2d, ln, g, dh, dxo, dt)
         return (dx, dg, db, dW1, db1, dW2, db2) + (None,) * 4 + (dgamma,)
 
 

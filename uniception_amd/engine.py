@@ -621,7 +621,11 @@ def is_native_rope(rope) -> bool:
     return rope is not None and getattr(rope, "_uc_native_rope", False)
 
 
-def _rope_epilogue(rope, pos2d: torch.Tensor, cols: int):
+def _rope_epilogue(rope, pos: torch.Tensor, cols: int):
+    "rope argument of ops.gemm: the native RoPE-2D on the first `cols` output columns, or None without a rope."
+    if rope is None:
+        return None
+    pos2d = _pos2d(pos)
     table = ops.rope_table(pos2d.device, ROPE_TABLE_NPOS, rope.base, rope.F0)
     return (pos2d, table, cols)
 
@@ -630,6 +634,31 @@ def _pos2d(pos: torch.Tensor) -> torch.Tensor:
     if pos.dtype != torch.int64:
         pos = pos.long()
     return pos.reshape(-1, 2).contiguous()
+
+
+# token counts that are not multiples of 4: V row-major out of the QKV / KV GEMM + uc_vt_pack instead of the element-wise VT epilogue
+VT_PACK_ODD: bool = os.environ.get("UNICEPTION_AMD_VT_PACK_ODD", "1") != "0"
+
+
+def attention_route(dtype: torch.dtype, head_dim: int, native_rope: bool, qk_norm: bool, separate_v: bool, n_keys: int) -> str:
+    """Which pipeline an inference attention sub-layer runs (self_attention, cross_attention); plain values in, the route's name out.
+    native_rope: no positional encoding, or the native RoPE-2D (is_native_rope) — not a foreign callable.  qk_norm: the layer
+    normalises q / k over head_dim.  separate_v: the value tokens are not the key tokens.  n_keys: key tokens per sample.
+      "fp8"          attention_precision("fp8") outside autograd: ops.attention_fp8 on ops.vt_pack_fp8 of the GEMM's row-major V;
+      "vt_pack"      n_keys % 4 != 0 and VT_PACK_ODD (DINOv2: 1370 / 1369 tokens): the QKV GEMM's packed-VT epilogue would store such
+                     V tiles element by element (2-byte stores: its launches ran at 0.20-0.31 of peak) — V leaves the GEMM row-major
+                     through the plain 16-byte drain and one uc_vt_pack pass (HBM-bound, ~5 TB/s) re-lays it out;
+      "vt_epilogue"  the default: the GEMM applies RoPE to q | k and writes V in the packed VT layout itself;
+      "unfused"      everything the fused GEMM epilogues do not carry (fp32 and bf16x3 operands, a foreign rope callable, qk_norm —
+                     it runs BEFORE the positional encoding —, separate value tokens): plain GEMMs, then _unfused_attention.
+    The three fused routes need bf16 operands and head_dim 64; bf16 with another head_dim has no kernel and raises."""
+    if dtype == torch.bfloat16 and head_dim == 64 and native_rope and not qk_norm and not separate_v:
+        if _fp8_attention():
+            return "fp8"
+        return "vt_pack" if n_keys % 4 != 0 and VT_PACK_ODD else "vt_epilogue"
+    if dtype == torch.bfloat16 and head_dim != 64:
+        raise UcHipError(f"bf16 attention needs head_dim 64 (got {head_dim}); use fp32 precision for this model")
+    return "unfused"
 
 
 # ---------------------------------------------------------------------------------------------
@@ -644,25 +673,56 @@ def _folded(lin: nn.Linear, fold, dtype: torch.dtype):
     return w, b, (fold[0], cs)
 
 
-def _qk_norm(t: torch.Tensor, norm: Optional[nn.Module]) -> torch.Tensor:
+def qk_layernorm(t: torch.Tensor, norm: nn.Module) -> torch.Tensor:
     """qk_norm (utils/transformer_blocks.py:196-197, 229): LayerNorm over head_dim of q / k, [B, N, H, Dh] view -> contiguous
-    [B, N, H, Dh] in the same dtype.  Runs BEFORE the positional encoding, so these layers take the unfused route (GEMM without
-    the RoPE / VT epilogue, uc_layernorm over B.N.H rows of Dh, uc_rope2d in place, attention)."""
-    if norm is None or isinstance(norm, nn.Identity):
-        return t
+    [B, N, H, Dh] in the same dtype (uc_layernorm over B.N.H rows of Dh).  The kernel call alone: inference and the training
+    Functions (autograd) share it."""
     if not isinstance(norm, nn.LayerNorm) or norm.weight is None or norm.bias is None:
         raise UcHipError(f"qk_norm with {type(norm).__name__} has no HIP path (nn.LayerNorm with affine parameters only)")
-    if torch.is_grad_enabled() and (t.requires_grad or norm.weight.requires_grad):
-        raise UcHipError("qk_norm=True has no HIP backward: run these layers under torch.no_grad()")
     return ops.layernorm(t.contiguous(), norm.weight.detach().float(), norm.bias.detach().float(), norm.eps, t.dtype)
+
+
+def _qk_norm(t: torch.Tensor, norm: Optional[nn.Module]) -> torch.Tensor:
+    """qk_layernorm of the inference path.  It runs BEFORE the positional encoding, so these layers take the unfused route (GEMM
+    without the RoPE / VT epilogue, uc_layernorm, uc_rope2d in place, attention)."""
+    if not _has_norm(norm):
+        return t
+    if torch.is_grad_enabled() and (t.requires_grad or getattr(norm, "weight", None) is not None and norm.weight.requires_grad):
+        raise UcHipError("qk_norm=True has no HIP backward: run these layers under torch.no_grad()")
+    return qk_layernorm(t, norm)
 
 
 def _has_norm(*norms) -> bool:
     return any(n is not None and not isinstance(n, nn.Identity) for n in norms)
 
 
-# token counts that are not multiples of 4: V row-major out of the QKV / KV GEMM + uc_vt_pack instead of the element-wise VT epilogue
-VT_PACK_ODD: bool = os.environ.get("UNICEPTION_AMD_VT_PACK_ODD", "1") != "0"
+def _unfused_attention(q, k, v, q_norm, k_norm, rope, qpos, kpos, scale):
+    """The attention of the "unfused" route on row-major q, k, v [B,N,H,D] views: qk_norm, then the positional encoding and the
+    product — in one kernel where the split-operand attention carries the rotation, else uc_rope2d in place + attention."""
+    q, k = _qk_norm(q, q_norm), _qk_norm(k, k_norm)
+    o = _x3_rope_attention(rope, q, k, v, qpos, kpos, scale)
+    if o is None:
+        q, k = _apply_rope(rope, q, k, qpos, kpos)
+        o = _attention_generic(q, k, v, scale)
+    return o
+
+
+def _fused_attention(route: str, q, k, v, scale):
+    """The attention of the three fused routes (attention_route).  v: the GEMM's row-major V view ("fp8", "vt_pack"), or the packed
+    VT buffer the GEMM's epilogue filled ("vt_epilogue")."""
+    if route == "fp8":
+        return ops.attention_fp8(q, k, ops.vt_pack_fp8(v), scale)
+    return ops.attention(q, k, ops.vt_pack(v) if route == "vt_pack" else v, scale, v_packed=True)
+
+
+def _out_proj(o2d: torch.Tensor, lin: nn.Linear, wb, dtype: torch.dtype, residual: Optional[torch.Tensor], out_dtype: torch.dtype,
+              emit_ln: bool) -> torch.Tensor:
+    """The output linear of a sub-layer (proj, fc2, w3) with the residual add in its epilogue.  wb: optional prepared (W, b)
+    overriding lin's own (a LayerScale folded in).  emit_ln: the GEMM also writes the twin / statistics the next sub-layer's folded
+    LayerNorm consumes, where that fold exists for its output width."""
+    w, b = wb if wb is not None else lin_weights(lin, dtype)
+    emit = emit_ln and out_dtype in (torch.float32, torch.bfloat16) and fold_ok(dtype, w.shape[0])
+    return ops.gemm(o2d, w, b, residual=residual, out_dtype=out_dtype, emit_ln=emit)
 
 
 def self_attention(h2d: torch.Tensor, B: int, N: int, qkv: nn.Linear, proj: nn.Linear, num_heads: int, rope, pos,
@@ -673,40 +733,22 @@ def self_attention(h2d: torch.Tensor, B: int, N: int, qkv: nn.Linear, proj: nn.L
     emit_ln: the proj GEMM also writes the twin / statistics the next sub-layer's folded LayerNorm consumes.
     q_norm / k_norm: the layer's qk_norm modules (LayerNorm over head_dim, before the positional encoding)."""
     dtype = h2d.dtype
-    M, Cm = h2d.shape
+    M = h2d.shape[0]
     Cd = qkv.out_features // 3          # width of q / k / v: the model width, or `latent_attn_dim` (utils/transformer_blocks.py:178-199)
     Dh = Cd // num_heads
     wq, bq, lnq = _folded(qkv, fold, dtype)
-    wp, bp = proj_wb if proj_wb is not None else lin_weights(proj, dtype)
-    native = (rope is None or is_native_rope(rope)) and not _has_norm(q_norm, k_norm)      # (qk_norm: the unfused route below)
-    if dtype == torch.bfloat16 and Dh == 64 and native and _fp8_attention():
-        ep = _rope_epilogue(rope, _pos2d(pos), 2 * Cd) if rope is not None else None
-        t5 = ops.gemm(h2d, wq, bq, rope=ep, ln=lnq).view(B, N, 3, num_heads, Dh)
-        o = ops.attention_fp8(t5[:, :, 0], t5[:, :, 1], ops.vt_pack_fp8(t5[:, :, 2]), scale)
-    elif dtype == torch.bfloat16 and Dh == 64 and native and N % 4 != 0 and VT_PACK_ODD:
-        # token counts that are not multiples of 4 (DINOv2: 1370 / 1369 tokens): the QKV GEMM's packed-VT epilogue would store such
-        # V tiles element by element (2-byte stores: its launches ran at 0.20-0.31 of peak) — V leaves the GEMM row-major through the
-        # plain 16-byte drain and one uc_vt_pack pass (HBM-bound, ~5 TB/s) re-lays it out
-        ep = _rope_epilogue(rope, _pos2d(pos), 2 * Cd) if rope is not None else None
-        t5 = ops.gemm(h2d, wq, bq, rope=ep, ln=lnq).view(B, N, 3, num_heads, Dh)
-        o = ops.attention(t5[:, :, 0], t5[:, :, 1], ops.vt_pack(t5[:, :, 2]), scale, v_packed=True)
-    elif dtype == torch.bfloat16 and Dh == 64 and native:
-        vt = ops.vt_buffer(B, num_heads, N, h2d.device)
-        ep = _rope_epilogue(rope, _pos2d(pos), 2 * Cd) if rope is not None else None
-        qk = ops.gemm(h2d, wq, bq, rope=ep, vt=(2 * Cd, vt, N), ln=lnq)
-        qk5 = qk.view(B, N, 2, num_heads, Dh)
-        o = ops.attention(qk5[:, :, 0], qk5[:, :, 1], vt, scale, v_packed=True)
-    else:
-        if dtype == torch.bfloat16 and Dh != 64:
-            raise UcHipError(f"bf16 attention needs head_dim 64 (got {Dh}); use fp32 precision for this model")
+    route = attention_route(dtype, Dh, rope is None or is_native_rope(rope), _has_norm(q_norm, k_norm), False, N)
+    if route == "unfused":
         t = ops.gemm(h2d, wq, bq, ln=lnq).view(B, N, 3, num_heads, Dh)
-        q, k, v = _qk_norm(t[:, :, 0], q_norm), _qk_norm(t[:, :, 1], k_norm), t[:, :, 2]
-        o = _x3_rope_attention(rope, q, k, v, pos, pos, scale)
-        if o is None:
-            q, k = _apply_rope(rope, q, k, pos, pos)
-            o = _attention_generic(q, k, v, scale)
-    emit = emit_ln and out_dtype in (torch.float32, torch.bfloat16) and fold_ok(dtype, Cm)
-    return ops.gemm(o.view(M, Cd), wp, bp, residual=residual, out_dtype=out_dtype, emit_ln=emit)
+        o = _unfused_attention(t[:, :, 0], t[:, :, 1], t[:, :, 2], q_norm, k_norm, rope, pos, pos, scale)
+    elif route == "vt_epilogue":
+        vt = ops.vt_buffer(B, num_heads, N, h2d.device)
+        qk = ops.gemm(h2d, wq, bq, rope=_rope_epilogue(rope, pos, 2 * Cd), vt=(2 * Cd, vt, N), ln=lnq).view(B, N, 2, num_heads, Dh)
+        o = _fused_attention(route, qk[:, :, 0], qk[:, :, 1], vt, scale)
+    else:
+        t = ops.gemm(h2d, wq, bq, rope=_rope_epilogue(rope, pos, 2 * Cd), ln=lnq).view(B, N, 3, num_heads, Dh)
+        o = _fused_attention(route, t[:, :, 0], t[:, :, 1], t[:, :, 2], scale)
+    return _out_proj(o.view(M, Cd), proj, proj_wb, dtype, residual, out_dtype, emit_ln)
 
 
 def _apply_rope(rope, q, k, qpos, kpos):
@@ -749,14 +791,9 @@ def _pos_in_table(pos: torch.Tensor) -> bool:
 
 
 def _attention_generic(q, k, v, scale):
+    q, k, v = (t if t.stride(3) == 1 else t.contiguous() for t in (q, k, v))
     if q.dtype == torch.bfloat16:
-        q = q if q.stride(3) == 1 else q.contiguous()
-        k = k if k.stride(3) == 1 else k.contiguous()
-        v = v if v.stride(3) == 1 else v.contiguous()
         return ops.attention(q, k, ops.vt_pack(v), scale, v_packed=True)
-    q = q if q.stride(3) == 1 else q.contiguous()
-    k = k if k.stride(3) == 1 else k.contiguous()
-    v = v if v.stride(3) == 1 else v.contiguous()
     if _forced_x3 and q.shape[-1] == 64 and _x3_attention and not torch.is_grad_enabled():
         # precision("bf16x3"): the two products of the attention as three bf16 MFMA products of split operands each, fp32 softmax
         return ops.attention_x3(q, k, v, scale)
@@ -774,81 +811,45 @@ def cross_attention(hq2d: torch.Tensor, hkv2d: torch.Tensor, B: int, Nq: int, Nk
     dtype = hq2d.dtype
     Cd = hq2d.shape[1]
     Dh = Cd // num_heads
-    if hv2d is not None or _has_norm(q_norm, k_norm):
-        return _cross_attention_unfused(hq2d, hkv2d, hv2d, B, Nq, Nk, projq, projk, projv, proj, num_heads, rope, qpos, kpos, scale,
-                                        residual, out_dtype, fold_q, fold_kv, emit_ln, q_norm, k_norm, proj_wb)
+    route = attention_route(dtype, Dh, rope is None or is_native_rope(rope), _has_norm(q_norm, k_norm), hv2d is not None, Nk)
     wq, bq, lnq = _folded(projq, fold_q, dtype)
+    if route == "unfused" and (hv2d is not None or _has_norm(q_norm, k_norm)):
+        # options the fused [Wk; Wv] GEMM does not carry: q, k, v from three GEMMs (the query / key LayerNorm folds still apply)
+        if hv2d is not None and fold_kv is not None:
+            raise UcHipError("a folded key LayerNorm cannot serve separate value tokens")
+        wk, bk, lnk = _folded(projk, fold_kv, dtype)
+        q = ops.gemm(hq2d, wq, bq, ln=lnq).view(B, Nq, num_heads, Dh)
+        k = ops.gemm(hkv2d, wk, bk, ln=lnk).view(B, Nk, num_heads, Dh)
+        if hv2d is None:
+            wv, bv, lnv = _folded(projv, fold_kv, dtype)
+            v = ops.gemm(hkv2d, wv, bv, ln=lnv).view(B, Nk, num_heads, Dh)
+        else:
+            assert hv2d.shape[0] == B * Nk, "key and value must have the same number of tokens"
+            wv, bv = lin_weights(projv, dtype)
+            v = ops.gemm(hv2d, wv, bv).view(B, Nk, num_heads, Dh)
+        o = _unfused_attention(q, k, v, q_norm, k_norm, rope, qpos, kpos, scale)
+        return _out_proj(o.reshape(B * Nq, Cd), proj, proj_wb, dtype, residual, out_dtype, emit_ln)
     if fold_kv is None:
         (wkv, bkv), lnkv = kv_weights(projk, projv, dtype), None
     else:
         wkv, bkv, cskv = ln_kv_weights(projk, projv, fold_kv[1], dtype)
         lnkv = (fold_kv[0], cskv)
-    wp, bp = proj_wb if proj_wb is not None else lin_weights(proj, dtype)
-    native = rope is None or is_native_rope(rope)
-    if dtype == torch.bfloat16 and Dh == 64 and native and _fp8_attention():
-        epq = _rope_epilogue(rope, _pos2d(qpos), Cd) if rope is not None else None
-        epk = _rope_epilogue(rope, _pos2d(kpos), Cd) if rope is not None else None
-        q = ops.gemm(hq2d, wq, bq, rope=epq, ln=lnq).view(B, Nq, num_heads, Dh)
-        kv5 = ops.gemm(hkv2d, wkv, bkv, rope=epk, ln=lnkv).view(B, Nk, 2, num_heads, Dh)
-        o = ops.attention_fp8(q, kv5[:, :, 0], ops.vt_pack_fp8(kv5[:, :, 1]), scale)
-    elif dtype == torch.bfloat16 and Dh == 64 and native and Nk % 4 != 0 and VT_PACK_ODD:      # (see self_attention)
-        epq = _rope_epilogue(rope, _pos2d(qpos), Cd) if rope is not None else None
-        epk = _rope_epilogue(rope, _pos2d(kpos), Cd) if rope is not None else None
-        q = ops.gemm(hq2d, wq, bq, rope=epq, ln=lnq).view(B, Nq, num_heads, Dh)
-        kv5 = ops.gemm(hkv2d, wkv, bkv, rope=epk, ln=lnkv).view(B, Nk, 2, num_heads, Dh)
-        o = ops.attention(q, kv5[:, :, 0], ops.vt_pack(kv5[:, :, 1]), scale, v_packed=True)
-    elif dtype == torch.bfloat16 and Dh == 64 and native:
-        vt = ops.vt_buffer(B, num_heads, Nk, hq2d.device)
-        epq = _rope_epilogue(rope, _pos2d(qpos), Cd) if rope is not None else None
-        epk = _rope_epilogue(rope, _pos2d(kpos), Cd) if rope is not None else None
-        q = ops.gemm(hq2d, wq, bq, rope=epq, ln=lnq).view(B, Nq, num_heads, Dh)
-        k = ops.gemm(hkv2d, wkv, bkv, rope=epk, vt=(Cd, vt, Nk), ln=lnkv).view(B, Nk, num_heads, Dh)
-        o = ops.attention(q, k, vt, scale, v_packed=True)
-    else:
-        if dtype == torch.bfloat16 and Dh != 64:
-            raise UcHipError(f"bf16 attention needs head_dim 64 (got {Dh}); use fp32 precision for this model")
+    if route == "unfused":
         q = ops.gemm(hq2d, wq, bq, ln=lnq).view(B, Nq, num_heads, Dh)
         kv = ops.gemm(hkv2d, wkv, bkv, ln=lnkv).view(B, Nk, 2, num_heads, Dh)
-        k, v = kv[:, :, 0], kv[:, :, 1]
-        o = _x3_rope_attention(rope, q, k, v, qpos, kpos, scale)
-        if o is None:
-            q, k = _apply_rope(rope, q, k, qpos, kpos)
-            o = _attention_generic(q, k, v, scale)
-    emit = emit_ln and out_dtype in (torch.float32, torch.bfloat16) and fold_ok(dtype, Cd)
-    return ops.gemm(o.reshape(B * Nq, Cd), wp, bp, residual=residual, out_dtype=out_dtype, emit_ln=emit)
-
-
-def _cross_attention_unfused(hq2d, hk2d, hv2d, B, Nq, Nk, projq, projk, projv, proj, num_heads, rope, qpos, kpos, scale, residual,
-                             out_dtype, fold_q, fold_k, emit_ln, q_norm, k_norm, proj_wb=None):
-    """CrossAttention with options the fused pipeline does not carry: qk_norm (LayerNorm of q / k over head_dim before the positional
-    encoding) and value tokens that are not the key tokens.  q, k, v from three GEMMs (the query / key LayerNorm folds still apply),
-    uc_layernorm for the norms, uc_rope2d in place, attention on row-major V."""
-    dtype = hq2d.dtype
-    Cd = hq2d.shape[1]
-    Dh = Cd // num_heads
-    if dtype == torch.bfloat16 and Dh != 64:
-        raise UcHipError(f"bf16 attention needs head_dim 64 (got {Dh}); use fp32 precision for this model")
-    if hv2d is not None and fold_k is not None:
-        raise UcHipError("a folded key LayerNorm cannot serve separate value tokens")
-    wq, bq, lnq = _folded(projq, fold_q, dtype)
-    wk, bk, lnk = _folded(projk, fold_k, dtype)
-    q = ops.gemm(hq2d, wq, bq, ln=lnq).view(B, Nq, num_heads, Dh)
-    k = ops.gemm(hk2d, wk, bk, ln=lnk).view(B, Nk, num_heads, Dh)
-    if hv2d is None:
-        wv, bv, lnv = _folded(projv, fold_k, dtype)
-        v = ops.gemm(hk2d, wv, bv, ln=lnv).view(B, Nk, num_heads, Dh)
+        o = _unfused_attention(q, kv[:, :, 0], kv[:, :, 1], None, None, rope, qpos, kpos, scale)
+    elif route == "vt_epilogue":
+        vt = ops.vt_buffer(B, num_heads, Nk, hq2d.device)
+        epq, epk = _rope_epilogue(rope, qpos, Cd), _rope_epilogue(rope, kpos, Cd)
+        q = ops.gemm(hq2d, wq, bq, rope=epq, ln=lnq).view(B, Nq, num_heads, Dh)
+        k = ops.gemm(hkv2d, wkv, bkv, rope=epk, vt=(Cd, vt, Nk), ln=lnkv).view(B, Nk, num_heads, Dh)
+        o = _fused_attention(route, q, k, vt, scale)
     else:
-        assert hv2d.shape[0] == B * Nk, "key and value must have the same number of tokens"
-        wv, bv = lin_weights(projv, dtype)
-        v = ops.gemm(hv2d, wv, bv).view(B, Nk, num_heads, Dh)
-    q, k = _qk_norm(q, q_norm), _qk_norm(k, k_norm)
-    o = _x3_rope_attention(rope, q, k, v, qpos, kpos, scale)
-    if o is None:
-        q, k = _apply_rope(rope, q, k, qpos, kpos)
-        o = _attention_generic(q, k, v, scale)
-    wp, bp = proj_wb if proj_wb is not None else lin_weights(proj, dtype)
-    emit = emit_ln and out_dtype in (torch.float32, torch.bfloat16) and fold_ok(dtype, Cd)
-    return ops.gemm(o.reshape(B * Nq, Cd), wp, bp, residual=residual, out_dtype=out_dtype, emit_ln=emit)
+        epq, epk = _rope_epilogue(rope, qpos, Cd), _rope_epilogue(rope, kpos, Cd)
+        q = ops.gemm(hq2d, wq, bq, rope=epq, ln=lnq).view(B, Nq, num_heads, Dh)
+        kv = ops.gemm(hkv2d, wkv, bkv, rope=epk, ln=lnkv).view(B, Nk, 2, num_heads, Dh)
+        o = _fused_attention(route, q, kv[:, :, 0], kv[:, :, 1], scale)
+    return _out_proj(o.reshape(B * Nq, Cd), proj, proj_wb, dtype, residual, out_dtype, emit_ln)
 
 
 def mlp(h2d: torch.Tensor, fc1: nn.Linear, fc2: nn.Linear, act: str, residual: Optional[torch.Tensor],
@@ -857,10 +858,8 @@ def mlp(h2d: torch.Tensor, fc1: nn.Linear, fc2: nn.Linear, act: str, residual: O
     if fold is not None and act not in ("gelu", "none", None):
         raise UcHipError("the folded LayerNorm epilogue exists for GELU / no activation")
     w1, b1, ln1 = _folded(fc1, fold, h2d.dtype)
-    w2, b2 = fc2_wb if fc2_wb is not None else lin_weights(fc2, h2d.dtype)
     g = ops.gemm(h2d, w1, b1, act=act, ln=ln1)
-    emit = emit_ln and out_dtype in (torch.float32, torch.bfloat16) and fold_ok(h2d.dtype, w2.shape[0])
-    return ops.gemm(g, w2, b2, residual=residual, out_dtype=out_dtype, emit_ln=emit)
+    return _out_proj(g, fc2, fc2_wb, h2d.dtype, residual, out_dtype, emit_ln)
 
 
 def mlp_swiglu(h2d: torch.Tensor, w12: nn.Linear, w3: nn.Linear, residual: Optional[torch.Tensor], out_dtype: torch.dtype,
@@ -868,10 +867,8 @@ def mlp_swiglu(h2d: torch.Tensor, w12: nn.Linear, w3: nn.Linear, residual: Optio
     """DINOv2 giant's FFN (the hub's SwiGLUFFNFused): x1, x2 = w12(h).chunk(2); residual + w3(silu(x1) * x2).  w12 takes the folded
     LayerNorm like fc1 does, the gate is one HBM-bound pass (uc_swiglu), w3 writes the next LayerNorm's statistics (emit_ln)."""
     w1, b1, ln1 = _folded(w12, fold, h2d.dtype)
-    w2, b2 = w3_wb if w3_wb is not None else lin_weights(w3, h2d.dtype)
     g = ops.swiglu(ops.gemm(h2d, w1, b1, ln=ln1))
-    emit = emit_ln and out_dtype in (torch.float32, torch.bfloat16) and fold_ok(h2d.dtype, w2.shape[0])
-    return ops.gemm(g, w2, b2, residual=residual, out_dtype=out_dtype, emit_ln=emit)
+    return _out_proj(g, w3, w3_wb, h2d.dtype, residual, out_dtype, emit_ln)
 
 
 def act_name(act_module: nn.Module) -> str:
