@@ -57,8 +57,10 @@ const char* uc_last_error(void);
  *   15: uc_attention_fwd / uc_attention_bwd take one descriptor each (uc_attention_desc, uc_attention_bwd_desc): dtype selects bf16 or
  *       fp32, drop_p > 0 dropout; the fp32 backward and the three dropout twins are gone.
  *   16: uc_gemm_tn takes one descriptor (uc_gemm_tn_desc); uc_gemm_tn_query (tiles per K-slice and the recommended split_k of a
- *       shape, dense or conv) replaces the conv-only tile-count query of version 9. */
-#define UC_ABI_VERSION 16
+ *       shape, dense or conv) replaces the conv-only tile-count query of version 9.
+ *   17: differential attention — uc_diff_attention_desc, uc_diff_attention_fwd, uc_diff_attention_combine_bwd,
+ *       uc_diff_attention_combine_ws_bytes added (nothing existing changed). */
+#define UC_ABI_VERSION 17
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -586,6 +588,55 @@ int uc_conv1x1_to4_bwd(const void* feat, int dtype, const float* w, const float*
  * ---------------------------------------------------------------------------------- */
 /* The keep mask those kernels apply, as bytes [B, H, Nq, Nk] (1 = kept): for reference implementations and tests. */
 int uc_attention_drop_mask(void* mask, int B, int H, int Nq, int Nk, float drop_p, unsigned long long seed, uc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Differential attention (DiffAttention / DiffCrossAttention, models/utils/transformer_blocks.py:686-945; arXiv 2410.05258):
+ *   A1 = softmax(scale Q1 K1^T) V,  A2 = softmax(scale Q2 K2^T) V,  a = A1 - lambda_full A2,
+ *   O  = a / sqrt(mean_d(a^2) + rms_eps) * subln_w * out_scale            (RMSNorm over the 2 Dqk channels of V, out_scale = 1 - lambda_init)
+ * in ONE launch: per query tile both score products, two online softmaxes and two accumulators over the SAME staged V tile; only
+ * the normalised result is written (plus, for training, the four saves below).
+ * Q and K are [B, N, 2H, Dqk] views addressed by element strides (unit channel stride): head h of softmax 1 is head h, head h of
+ * softmax 2 is head H + h (the reference's chunk(2, dim=1) of the [B, 2H, N, Dqk] tensor).  V has H heads of 2 Dqk channels:
+ * row-major by strides (UC_F32) or the packed VT layout of uc_attention_fwd, [B, H, 64, roundup(Nk, 64)] (UC_BF16).
+ * O is addressed O[b*o_sb + n*o_sn + h*o_sh + d], d < 2 Dqk, in `dtype`.
+ * UC_BF16 (MFMA): Dqk == 32.  UC_F32 (verification kernel): Dqk <= 32, Dqk % 4 == 0.  Dqk == 64 (V head dim 128) is not supported.
+ * Saves for the backward (all four, or none; `training` != 0 demands them): lse1, lse2 fp32 [B, H, Nq] (natural-log LSE of the scaled
+ * scores, the convention of uc_attention_fwd) and A1, A2, the two normalised attention outputs before the combine, contiguous
+ * [B, Nq, H, 2 Dqk] in `dtype` — what uc_attention_bwd takes as O / LSE, once per softmax, with Q / K zero-padded to 2 Dqk columns.
+ * ---------------------------------------------------------------------------------- */
+typedef struct uc_diff_attention_desc {
+    int dtype;           /* UC_BF16 (packed VT, Dqk 32) or UC_F32 (row-major V, Dqk <= 32) */
+    int v_layout;        /* uc_v_layout */
+    int B, H, Nq, Nk, Dqk;
+    const void* Q;
+    const void* K;
+    const void* V;
+    void* O;
+    int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+    float scale;
+    float lambda_full;   /* exp(lq1.lk1) - exp(lq2.lk2) + lambda_init, evaluated by the host */
+    const float* subln_w; /* fp32 [2 Dqk] */
+    float rms_eps;
+    float out_scale;     /* 1 - lambda_init */
+    int training;        /* != 0: the four saves are required */
+    float* lse1;
+    float* lse2;
+    void* A1;
+    void* A2;
+} uc_diff_attention_desc;
+
+int uc_diff_attention_fwd(const uc_diff_attention_desc* desc, uc_stream_t stream);
+
+/* Backward of the combine step (everything after the two softmax(..) V products): from dY (addressed like O: dy_sb, dy_sn, dy_sh), the
+ * saved A1, A2 (contiguous [B, N, H, D], D = 2 Dqk <= 64, D % 4 == 0), lambda_full, subln_w, rms_eps and out_scale it writes
+ *   dA1, dA2 = -lambda_full dA1   (contiguous like A1; `dtype` = dtype of dY, A1, A2, dA1, dA2),
+ *   dlambda[0] = -sum dA1 . A2,  dw[d] = sum_rows dY n out_scale  (n = the normalised row), both fp32.
+ * dlambda and dw are reduced in a fixed order in two stages (per-workgroup partials in `ws`, then one workgroup adds the partials
+ * in index order): no float atomics, the same bits on every run.  ws: uc_diff_attention_combine_ws_bytes(B * N * H) bytes. */
+int64_t uc_diff_attention_combine_ws_bytes(int64_t rows);
+int uc_diff_attention_combine_bwd(const void* dY, const void* A1, const void* A2, void* dA1, void* dA2, const float* subln_w,
+                                  float* dw, float* dlambda, float* ws, int dtype, int B, int N, int H, int D, int64_t dy_sb,
+                                  int64_t dy_sn, int64_t dy_sh, float lambda_full, float rms_eps, float out_scale, uc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -74,6 +74,18 @@ class AttnBwdDesc(C.Structure):
     ]
 
 
+class DiffAttnDesc(C.Structure):
+    # field order == struct uc_diff_attention_desc in include/uc_hip.h
+    _fields_ = [
+        ("dtype", i32), ("v_layout", i32), ("B", i32), ("H", i32), ("Nq", i32), ("Nk", i32), ("Dqk", i32),
+        ("Q", vp), ("K", vp), ("V", vp), ("O", vp),
+        ("q_sb", i64), ("q_sn", i64), ("q_sh", i64), ("k_sb", i64), ("k_sn", i64), ("k_sh", i64),
+        ("v_sb", i64), ("v_sn", i64), ("v_sh", i64), ("o_sb", i64), ("o_sn", i64), ("o_sh", i64),
+        ("scale", f32), ("lambda_full", f32), ("subln_w", vp), ("rms_eps", f32), ("out_scale", f32), ("training", i32),
+        ("lse1", vp), ("lse2", vp), ("A1", vp), ("A2", vp),
+    ]
+
+
 class GemmTnDesc(C.Structure):
     # field order == struct uc_gemm_tn_desc in include/uc_hip.h
     _fields_ = [
@@ -140,12 +152,15 @@ SIGNATURES = {
     "uc_dilate_nhwc": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "uc_conv1x1_to4_bwd": [vp, i32, vp, vp, vp, vp, vp, i64, i32, i32, vp],
     "uc_attention_drop_mask": [vp, i32, i32, i32, i32, f32, u64, vp],
+    "uc_diff_attention_fwd": [C.POINTER(DiffAttnDesc), vp],
+    "uc_diff_attention_combine_ws_bytes": [i64],
+    "uc_diff_attention_combine_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, f32, f32, f32, vp],
 }
 
 _lib = None
 
 
-ABI_VERSION = 16   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 17   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

@@ -1188,3 +1188,160 @@ class Conv1x1To4Fn(Function):
 
 def conv1x1_to4(x, conv, w4, b4, relu_cell=None):
     return Conv1x1To4Fn.apply(x, conv.weight, conv.bias, w4, b4, relu_cell)
+
+
+# =================================================================================================================
+# Differential attention (reference: utils/transformer_blocks.py:686-945).  Forward: ONE fused kernel (uc_diff_attention_fwd: both
+# softmaxes over one staged V, combine, RMSNorm).  Backward: uc_diff_attention_combine_bwd (dA1, dA2, dlambda, d subln.weight; fixed-order
+# reductions), then uc_attention_bwd once per softmax on Q / K zero-padded to V's head_dim — padding leaves the scores unchanged and the
+# padded gradient columns are exactly zero — with the saved LSEs; dV is the sum of the two calls.
+# =================================================================================================================
+class Rope2dFn(Function):
+    "native RoPE-2D of a [B, N, H, D] view as a pass of its own (uc_rope2d, any D % 4 == 0); backward = the inverse rotation"
+
+    @staticmethod
+    def forward(ctx, t4, pos, base, F0):
+        out = t4.clone() if t4.is_contiguous() else t4.contiguous()
+        pos = pos.contiguous()
+        ops.rope_2d_(out, pos, base, F0)
+        ctx.pos, ctx.base, ctx.F0 = pos, base, F0
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous().clone()
+        ops.rope_2d_(g, ctx.pos, ctx.base, -ctx.F0)
+        return g, None, None, None
+
+
+def rope2d(t4, pos, rope):
+    if rope is None:
+        return t4
+    _check_rope(rope)
+    return Rope2dFn.apply(t4, pos if pos.dtype == torch.int64 else pos.long(), rope.base, rope.F0)
+
+
+class DiffAttentionFunction(Function):
+    """y [B * Nq, H * 2hd] = RMSNorm(softmax(scale q1 k1^T) v - lam softmax(scale q2 k2^T) v; w, eps) * out_scale for
+    q [B, Nq, 2H, hd], k [B, Nk, 2H, hd] (heads [0, H) feed softmax 1, [H, 2H) softmax 2), v [B, Nk, H, 2hd]; lam: 0-d fp32 tensor.
+    head_major: the result's memory order is [B, H, Nq, 2hd] (what DiffAttention.forward reshapes WITHOUT a transpose), else
+    [B, Nq, H, 2hd]."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, lam, w, scale, eps, out_scale, head_major):
+        q, k, v = (t if t.stride(3) == 1 else t.contiguous() for t in (q, k, v))
+        B, Nq, H2, hd = q.shape
+        H, D = H2 // 2, 2 * hd
+        lam_f = float(lam)
+        wf = w.detach().float().contiguous()
+        out = torch.empty((B, H, Nq, D) if head_major else (B, Nq, H, D), dtype=q.dtype, device=q.device)
+        out4 = out.permute(0, 2, 1, 3) if head_major else out
+        vk = ops.vt_pack(v) if q.dtype == torch.bfloat16 else v
+        save = any(ctx.needs_input_grad[:5])      # (autograd is off inside forward: the inputs' requires_grad is what counts)
+        res = ops.diff_attention(q, k, vk, scale, lam_f, wf, eps, out_scale, out=out4, v_packed=q.dtype == torch.bfloat16, save=save)
+        if save:
+            lse1, lse2, a1, a2 = res[1]
+            ctx.save_for_backward(q, k, v, wf, lse1, lse2, a1, a2)
+        ctx.meta = (lam_f, scale, eps, out_scale, head_major)
+        return out.view(B * Nq, H * D)
+
+    @staticmethod
+    def backward(ctx, dy):
+        q, k, v, wf, lse1, lse2, a1, a2 = ctx.saved_tensors
+        lam_f, scale, eps, out_scale, head_major = ctx.meta
+        B, Nq, H2, hd = q.shape
+        Nk, H, D = k.shape[1], H2 // 2, 2 * hd
+        dy = _c(dy)
+        if dy.dtype != q.dtype:
+            dy = ops.convert(dy, q.dtype)
+        dy4 = dy.view(B, H, Nq, D).permute(0, 2, 1, 3) if head_major else dy.view(B, Nq, H, D)
+        da1, da2, dw, dl = ops.diff_attention_combine_bwd(dy4, a1, a2, lam_f, wf, eps, out_scale)
+        dq = torch.empty_like(q, memory_format=torch.contiguous_format)
+        dk = torch.empty_like(k, memory_format=torch.contiguous_format)
+        dv = None
+        for i, (a, da, lse) in enumerate(((a1, da1, lse1), (a2, da2, lse2))):
+            qp = q.new_zeros((B, Nq, H, D))
+            kp = k.new_zeros((B, Nk, H, D))
+            qp[..., :hd].copy_(q[:, :, i * H:(i + 1) * H])
+            kp[..., :hd].copy_(k[:, :, i * H:(i + 1) * H])
+            dqp, dkp, dvi = ops.attention_bwd(qp, kp, v, a, da, lse, scale)
+            dq[:, :, i * H:(i + 1) * H].copy_(dqp[..., :hd])
+            dk[:, :, i * H:(i + 1) * H].copy_(dkp[..., :hd])
+            dv = dvi if dv is None else dv.add_(dvi)
+        return dq, dk, dv, dl.view(()), dw, None, None, None, None
+
+
+def diff_attention(q, k, v, lam, w, scale, eps, out_scale, head_major=False):
+    return DiffAttentionFunction.apply(q, k, v, lam, w, scale, eps, out_scale, head_major)
+
+
+class MaskScaleFn(Function):
+    "x * (mask ? scale : 0): nn.Dropout (one mask byte per element) or DropPath (one per `rows_per_mask` rows); its own backward"
+
+    @staticmethod
+    def forward(ctx, x2d, mask, rows_per_mask, scale):
+        ctx.save_for_backward(mask)
+        ctx.meta = (rows_per_mask, scale)
+        return ops.mask_scale(_c(x2d), mask, rows_per_mask, scale)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (mask,) = ctx.saved_tensors
+        return ops.mask_scale(_c(dy), mask, ctx.meta[0], ctx.meta[1]), None, None, None
+
+
+def _diff_out(x2d, f, gamma, drops):
+    "x + drop_path(ls(proj_drop(f))): LayerScale and the sub-layer's drops behind a differential attention's output projection"
+    if drops is not None and drops.out is not None:
+        f = MaskScaleFn.apply(f, drops.out, 0, drops.out_scale)
+    if gamma is not None:
+        f = f * gamma.to(f.dtype)
+    if drops is not None and drops.path is not None:
+        f = MaskScaleFn.apply(f, drops.path, drops.path_rows, drops.path_scale)
+    return x2d + f
+
+
+def diff_lambda(m):
+    "lambda_full of a differential attention layer (utils/transformer_blocks.py:793-795), a 0-d fp32 tensor autograd differentiates"
+    l1 = torch.exp(torch.sum(m.lambda_q1 * m.lambda_k1, dim=-1).float())
+    l2 = torch.exp(torch.sum(m.lambda_q2 * m.lambda_k2, dim=-1).float())
+    return l1 - l2 + m.lambda_init
+
+
+def diff_cross_attn_core(da, hq, hk, hv, B, Nq, Nk, rope, qpos, kpos, dt):
+    "DiffCrossAttention on already normalised operands hq [B * Nq, C], hk / hv [B * Nk, C] (dt): projections, RoPE, fused kernel, proj"
+    H, hd = da.num_heads, da.head_dim
+    q = linear(hq, da.projq.weight, da.projq.bias, da.projq, dt, dt).view(B, Nq, 2 * H, hd)
+    k = linear(hk, da.projk.weight, da.projk.bias, da.projk, dt, dt).view(B, Nk, 2 * H, hd)
+    v = linear(hv, da.projv.weight, da.projv.bias, da.projv, dt, dt).view(B, Nk, H, 2 * hd)
+    q, k = rope2d(q, qpos, rope), rope2d(k, kpos, rope)
+    return diff_attention(q, k, v, diff_lambda(da), da.subln.weight, da.scale, da.subln.eps, 1.0 - da.lambda_init)
+
+
+def diff_self_attn_core(sa, h, B, N, rope, pos, dt):
+    "DiffAttention on the normalised operand h [B * N, C] (dt)"
+    H, hd = sa.num_heads, sa.head_dim
+    C = 2 * H * hd
+    t = linear(h, sa.qkv.weight, sa.qkv.bias, sa.qkv, dt, dt).view(B, N, 3 * C)
+    q, k = t[:, :, :C].view(B, N, 2 * H, hd), t[:, :, C:2 * C].view(B, N, 2 * H, hd)
+    v = t[:, :, 2 * C:].view(B, N, H, 2 * hd)
+    q, k = rope2d(q, pos, rope), rope2d(k, pos, rope)
+    # head_major: the reference reshapes its [B, H, N, 2hd] result to [B, N, C] without transposing heads and tokens back
+    # (utils/transformer_blocks.py:796-800); the kernel writes that memory order directly
+    return diff_attention(q, k, v, diff_lambda(sa), sa.subln.weight, sa.scale, sa.subln.eps, 1.0 - sa.lambda_init, head_major=True)
+
+
+def diff_cross_attn_sublayer(x2d, y2d, ln, lny, da, B, Nq, Nk, rope, qpos, kpos, dt, gamma=None, drops=None):
+    "x + ls(proj(DiffCrossAttention core)) with the block's LayerNorms; every step a HIP Function, forward and backward"
+    hq = layer_norm(x2d, ln, dt)
+    hy = layer_norm(y2d, lny, dt) if lny is not None else convert(y2d, dt)
+    o = diff_cross_attn_core(da, hq, hy, hy, B, Nq, Nk, rope, qpos, kpos, dt)
+    f = linear(o, da.proj.weight, da.proj.bias, da.proj, dt, x2d.dtype)
+    return _diff_out(x2d, f, gamma, drops)
+
+
+def diff_self_attn_sublayer(x2d, ln, sa, B, N, rope, pos, dt, gamma=None, drops=None):
+    h = layer_norm(x2d, ln, dt)
+    o = diff_self_attn_core(sa, h, B, N, rope, pos, dt)
+    f = linear(o, sa.proj.weight, sa.proj.bias, sa.proj, dt, x2d.dtype)
+    return _diff_out(x2d, f, gamma, drops)

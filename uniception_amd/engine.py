@@ -1089,3 +1089,41 @@ def run_branches(fn0, fn1, rows: int, inputs0=(), inputs1=(), warm_key=None, own
             t.record_stream(main)
     return out0, out1
 
+
+
+# ---------------------------------------------------------------------------------------------
+# differential attention (reference: utils/transformer_blocks.py:686-945): projections through uc_gemm with the prepared-weight cache
+# under the current precision policy, RoPE-2D as a uc_rope2d pass (head_dim 32: the GEMM's RoPE epilogue is head_dim-64 only), then ONE
+# uc_diff_attention_fwd launch and the output projection.  The same HIP Functions serve inference and training (autograd.py).
+# ---------------------------------------------------------------------------------------------
+def check_diff_layer(layer: nn.Module) -> None:
+    "the options of DiffAttention / DiffCrossAttention that have no HIP form, and the geometry the fused kernel covers"
+    if _has_norm(layer.q_norm, layer.k_norm):
+        raise UcHipError("qk_norm=True inside a differential attention layer has no HIP path")
+    if layer.attn_drop.p > 0.0 and layer.training:
+        raise UcHipError("attn_drop > 0 inside a differential attention layer has no HIP path (the fused kernel drops no probabilities)")
+    rope = layer.custom_positional_encoding
+    if rope is not None and not is_native_rope(rope):
+        raise UcHipError("differential attention supports no positional encoding or the native RoPE2D, not a foreign callable")
+    hd, dt = layer.head_dim, compute_dtype()
+    if hd > 32 or hd % 4 or (dt == torch.bfloat16 and hd != 32):
+        raise UcHipError(f"differential attention with Q/K head_dim {hd} and V head_dim {2 * hd} is not supported under {dt}: the HIP "
+                         f"kernels run Q/K head_dim 32 with V head_dim 64 (fp32 also smaller multiples of 4); dim / num_heads = 128 "
+                         f"needs head_dim-128 attention, which this library does not have")
+
+
+def diff_cross_attention(layer: nn.Module, hq2d: torch.Tensor, hk2d: torch.Tensor, hv2d: torch.Tensor, B: int, Nq: int, Nk: int, qpos, kpos,
+                         dt: torch.dtype) -> torch.Tensor:
+    "DiffCrossAttention.forward on [B*N, C] operands in dt: proj(fused differential attention), [B*Nq, C] in dt"
+    from . import autograd
+    check_diff_layer(layer)
+    o = autograd.diff_cross_attn_core(layer, hq2d, hk2d, hv2d, B, Nq, Nk, layer.custom_positional_encoding, qpos, kpos, dt)
+    return autograd.linear(o, layer.proj.weight, layer.proj.bias, layer.proj, dt, dt)
+
+
+def diff_self_attention(layer: nn.Module, h2d: torch.Tensor, B: int, N: int, pos, dt: torch.dtype) -> torch.Tensor:
+    "DiffAttention.forward on a [B*N, C] operand in dt"
+    from . import autograd
+    check_diff_layer(layer)
+    o = autograd.diff_self_attn_core(layer, h2d, B, N, layer.custom_positional_encoding, pos, dt)
+    return autograd.linear(o, layer.proj.weight, layer.proj.bias, layer.proj, dt, dt)

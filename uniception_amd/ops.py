@@ -13,7 +13,7 @@ import contextlib
 import torch
 
 from . import _lib
-from ._lib import (AttnBwdDesc, AttnDesc, GemmDesc, GemmTnDesc, UC_A_CONV3X3, UC_A_DENSE, UC_ACT_GELU_ERF, UC_ACT_NONE, UC_ACT_RELU,
+from ._lib import (AttnBwdDesc, AttnDesc, DiffAttnDesc, GemmDesc, GemmTnDesc, UC_A_CONV3X3, UC_A_DENSE, UC_ACT_GELU_ERF, UC_ACT_NONE, UC_ACT_RELU,
                    UC_BF16, UC_F16, UC_F32, UC_V_PACKED_T, UC_V_ROWMAJOR, UcHipError)
 
 _DT = {torch.float32: UC_F32, torch.bfloat16: UC_BF16, torch.float16: UC_F16}
@@ -1150,3 +1150,67 @@ def conv1x1_to4_bwd(feat: torch.Tensor, w: torch.Tensor, dout: torch.Tensor, dw:
     _lib.check(_lib.load().uc_conv1x1_to4_bwd(feat.data_ptr(), _dt(feat.dtype), w.data_ptr(), dout.data_ptr(), dfeat.data_ptr(),
                                               dw.data_ptr(), db.data_ptr(), npix, Cin, 1 if relu_mask else 0, _stream()), "uc_conv1x1_to4_bwd")
     return dfeat
+
+
+# --------------------------------------------------------------------------------------------
+# differential attention (uc_diff_attention_fwd / uc_diff_attention_combine_bwd)
+def diff_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, lambda_full: float, subln_w: torch.Tensor,
+                   rms_eps: float, out_scale: float, out: Optional[torch.Tensor] = None, v_packed: bool = False, save: bool = False):
+    """q [B,Nq,2H,hd], k [B,Nk,2H,hd] strided views (unit last stride): head h of softmax 1 is head h, of softmax 2 head H + h;
+    v [B,Nk,H,2hd] (fp32, strided) or packed VT [B,H,64,Npad] (bf16, v_packed).  subln_w fp32 [2hd].
+    Returns out [B,Nq,H,2hd] (a fresh contiguous tensor, or the strided 4-D view passed as `out`) = RMSNorm(A1 - lambda A2) * out_scale;
+    with save also (lse1, lse2, A1, A2): fp32 [B,H,Nq] twice and the two attention outputs, contiguous [B,Nq,H,2hd]."""
+    _need_gpu(q, k, v, subln_w)
+    B, Nq, H2, hd = q.shape
+    Nk, H = k.shape[1], H2 // 2
+    if hd > 32 or (q.dtype == torch.bfloat16 and hd != 32) or hd % 4:
+        raise UcHipError(f"differential attention with Q/K head_dim {hd} and V head_dim {2 * hd} is not supported: the HIP kernels run "
+                         f"Q/K head_dim 32 with V head_dim 64 (fp32 also smaller multiples of 4); head_dim-128 attention does not exist "
+                         f"in this library")
+    assert H2 == 2 * H and k.shape[2] == H2 and k.shape[3] == hd and q.stride(3) == 1 and k.stride(3) == 1 and q.dtype == k.dtype == v.dtype
+    assert subln_w.dtype == torch.float32 and subln_w.is_contiguous() and subln_w.numel() == 2 * hd
+    if out is None:
+        out = torch.empty((B, Nq, H, 2 * hd), dtype=q.dtype, device=q.device)
+    assert out.shape == (B, Nq, H, 2 * hd) and out.stride(3) == 1 and out.dtype == q.dtype
+    d = DiffAttnDesc()
+    d.dtype, d.v_layout = _dt(q.dtype), UC_V_PACKED_T if v_packed else UC_V_ROWMAJOR
+    d.B, d.H, d.Nq, d.Nk, d.Dqk = B, H, Nq, Nk, hd
+    if v_packed:
+        assert v.is_contiguous() and v.shape == (B, H, 64, (Nk + 63) // 64 * 64)
+    else:
+        assert v.shape == (B, Nk, H, 2 * hd) and v.stride(3) == 1
+        d.v_sb, d.v_sn, d.v_sh = v.stride(0), v.stride(1), v.stride(2)
+    d.Q, d.K, d.V, d.O = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    d.q_sb, d.q_sn, d.q_sh = q.stride(0), q.stride(1), q.stride(2)
+    d.k_sb, d.k_sn, d.k_sh = k.stride(0), k.stride(1), k.stride(2)
+    d.o_sb, d.o_sn, d.o_sh = out.stride(0), out.stride(1), out.stride(2)
+    d.scale, d.lambda_full, d.subln_w, d.rms_eps, d.out_scale = float(scale), float(lambda_full), subln_w.data_ptr(), float(rms_eps), float(out_scale)
+    saves = None
+    if save:
+        lse1 = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+        lse2 = torch.empty_like(lse1)
+        a1 = torch.empty((B, Nq, H, 2 * hd), dtype=q.dtype, device=q.device)
+        a2 = torch.empty_like(a1)
+        d.training, d.lse1, d.lse2, d.A1, d.A2 = 1, lse1.data_ptr(), lse2.data_ptr(), a1.data_ptr(), a2.data_ptr()
+        saves = (lse1, lse2, a1, a2)
+    _lib.check(_lib.load().uc_diff_attention_fwd(C.byref(d), _stream()), "uc_diff_attention_fwd")
+    return (out, saves) if save else out
+
+
+def diff_attention_combine_bwd(dy: torch.Tensor, a1: torch.Tensor, a2: torch.Tensor, lambda_full: float, subln_w: torch.Tensor,
+                               rms_eps: float, out_scale: float):
+    """dy: [B,N,H,D] view addressed like the forward's output (unit last stride); a1, a2: the saved contiguous [B,N,H,D].
+    Returns (dA1, dA2 [B,N,H,D] contiguous, dw fp32 [D], dlambda fp32 [1]); dw and dlambda are reduced in a fixed order (bit-reproducible)."""
+    _need_gpu(dy, a1, a2, subln_w)
+    B, N, H, D = a1.shape
+    assert dy.shape == a1.shape and dy.stride(3) == 1 and a1.is_contiguous() and a2.is_contiguous() and dy.dtype == a1.dtype == a2.dtype
+    lib = _lib.load()
+    da1, da2 = torch.empty_like(a1), torch.empty_like(a2)
+    dw = torch.empty(D, dtype=torch.float32, device=a1.device)
+    dl = torch.empty(1, dtype=torch.float32, device=a1.device)
+    ws = torch.empty(lib.uc_diff_attention_combine_ws_bytes(B * N * H) // 4, dtype=torch.float32, device=a1.device)
+    _lib.check(lib.uc_diff_attention_combine_bwd(dy.data_ptr(), a1.data_ptr(), a2.data_ptr(), da1.data_ptr(), da2.data_ptr(), subln_w.data_ptr(),
+                                                 dw.data_ptr(), dl.data_ptr(), ws.data_ptr(), _dt(a1.dtype), B, N, H, D, dy.stride(0), dy.stride(1),
+                                                 dy.stride(2), float(lambda_full), float(rms_eps), float(out_scale), _stream()),
+               "uc_diff_attention_combine_bwd")
+    return da1, da2, dw, dl
