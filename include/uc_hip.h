@@ -59,8 +59,9 @@ const char* uc_last_error(void);
  *   16: uc_gemm_tn takes one descriptor (uc_gemm_tn_desc); uc_gemm_tn_query (tiles per K-slice and the recommended split_k of a
  *       shape, dense or conv) replaces the conv-only tile-count query of version 9.
  *   17: differential attention — uc_diff_attention_desc, uc_diff_attention_fwd, uc_diff_attention_combine_bwd,
- *       uc_diff_attention_combine_ws_bytes added (nothing existing changed). */
-#define UC_ABI_VERSION 17
+ *       uc_diff_attention_combine_ws_bytes added (nothing existing changed).
+ *   18: token pooling of the summary heads — uc_token_pool, uc_token_pool_ws_bytes, uc_token_pool_bwd added (nothing existing changed). */
+#define UC_ABI_VERSION 18
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -637,6 +638,25 @@ int64_t uc_diff_attention_combine_ws_bytes(int64_t rows);
 int uc_diff_attention_combine_bwd(const void* dY, const void* A1, const void* A2, void* dA1, void* dA2, const float* subln_w,
                                   float* dw, float* dlambda, float* ws, int dtype, int B, int N, int H, int D, int64_t dy_sb,
                                   int64_t dy_sn, int64_t dy_sh, float lambda_full, float rms_eps, float out_scale, uc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Token pooling (PoseHead / GlobalHead: nn.AdaptiveAvgPool2d(1) on the token matrix; prediction_heads/pose_head.py:99,144) and its adjoint.
+ *   uc_token_pool:  out[b, c] = (1 / T) sum_t x[(b T + t) ld + c]      x: [B T, C] rows of leading dim ld >= C, dtype UC_F32 | UC_BF16 |
+ *     UC_F16, 16-byte aligned with 16-byte rows (ld % 4 == 0 for fp32, ld % 8 == 0 for the 16-bit types; C itself may be anything);
+ *     out: fp32 [B, C] contiguous; fp32 accumulation.  T is cut into chunks of 64 rows, one workgroup per (chunk, 64 column groups, b)
+ *     writes its partial sum to ws (uc_token_pool_ws_bytes(B, T, C) bytes, caller-provided: the library allocates nothing) and a
+ *     second kernel adds the partials in chunk order: no float atomics, the same bits on every run.
+ *     Limits: B <= 65535, T <= 65535 * 64.
+ *   uc_token_pool_bwd:  out[(b T + t) ld_out + c] = g[b, c] / T  (* (gate[(b T + t) ld_gate + c] > 0) when gate != NULL)
+ *     g: fp32 [B, C] contiguous; gate (optional) and out: [B T, C] in `dtype` with their own leading dims, 16-byte aligned with 16-byte
+ *     rows.  With a gate it is the pooling's adjoint fused with the backward of a ReLU whose pre-activation (or output) is the gate —
+ *     the broadcast map is never stored on its own; gated-off elements are exactly +0.  gate == NULL: the plain broadcast.
+ * Every argument is checked before anything is launched (UC_ERR_BAD_ARG, message prefixed with the function name).
+ * ---------------------------------------------------------------------------------- */
+int64_t uc_token_pool_ws_bytes(int64_t B, int64_t T, int64_t C);
+int uc_token_pool(const void* x, int dtype, int64_t ld, float* out, float* ws, int64_t B, int64_t T, int64_t C, uc_stream_t stream);
+int uc_token_pool_bwd(const float* g, const void* gate, int64_t ld_gate, void* out, int64_t ld_out, int dtype, int64_t B, int64_t T,
+                      int64_t C, uc_stream_t stream);
 
 #ifdef __cplusplus
 }

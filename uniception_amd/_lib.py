@@ -155,12 +155,15 @@ SIGNATURES = {
     "uc_diff_attention_fwd": [C.POINTER(DiffAttnDesc), vp],
     "uc_diff_attention_combine_ws_bytes": [i64],
     "uc_diff_attention_combine_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, f32, f32, f32, vp],
+    "uc_token_pool_ws_bytes": [i64, i64, i64],
+    "uc_token_pool": [vp, i32, i64, vp, vp, i64, i64, i64, vp],
+    "uc_token_pool_bwd": [vp, vp, i64, vp, i64, i32, i64, i64, i64, vp],
 }
 
 _lib = None
 
 
-ABI_VERSION = 17   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 18   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

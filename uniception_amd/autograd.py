@@ -1345,3 +1345,151 @@ def diff_self_attn_sublayer(x2d, ln, sa, B, N, rope, pos, dt, gamma=None, drops=
     o = diff_self_attn_core(sa, h, B, N, rope, pos, dt)
     f = linear(o, sa.proj.weight, sa.proj.bias, sa.proj, dt, x2d.dtype)
     return _diff_out(x2d, f, gamma, drops)
+
+
+# =================================================================================================================
+# Summary heads (PoseHead / GlobalHead / MLPHead, prediction_heads/pose_head.py, global_head.py, mlp_head.py): chains of
+# 1x1 convolutions / Linear layers with a ReLU and, in the ResConvBlocks, a residual, around one mean over the tokens.
+# Every layer is ONE uc_gemm (bias + ReLU + residual in its epilogue).  The layers work on PADDED widths: a hidden width is
+# rounded up to HEAD_PAD columns (MLPHead's default 196 -> 256, a patch-14 head's 784 -> 832) by zero rows / columns in the
+# prepared weights and zero bias entries, so that the padded activations are exact zeros and every launch meets the K % 64
+# of the direct-to-LDS kernels (preact_out, the split weight-gradient kernel); the modules slice the last layer's output.
+# =================================================================================================================
+HEAD_PAD = 64
+
+
+def head_pad(n: int, granule: int = HEAD_PAD) -> int:
+    return (n + granule - 1) // granule * granule
+
+
+def _head_w2d(layers):
+    return torch.cat([l.weight.detach().reshape(l.weight.shape[0], -1) for l in layers], 0).float()
+
+
+def head_weights(layers, dt, kp: int, npad: int):
+    """(W [npad, kp] in dt, bias fp32 [npad]) of the row-concatenated `layers` (nn.Linear / 1x1 nn.Conv2d; fc_t | fc_rot come out of
+    one GEMM), zero-padded, prepared once per weight version; owned by the first layer."""
+    def build():
+        w = _head_w2d(layers)
+        wp = torch.zeros((npad, kp), dtype=dt, device=w.device)
+        wp[:w.shape[0], :w.shape[1]].copy_(w)
+        bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
+        r = 0
+        for l in layers:
+            if l.bias is not None:
+                bp[r:r + l.bias.numel()].copy_(l.bias.detach())
+            r += l.weight.shape[0]
+        return wp, bp
+    srcs = tuple(t for l in layers for t in (l.weight, l.bias))
+    return engine.prepared(layers[0], ("head", dt, kp, npad, len(layers)), srcs, build)
+
+
+def _head_weight_t(layers, dt, kp: int, npad: int):
+    def build_2d():
+        w = _head_w2d(layers)
+        wp = torch.zeros((npad, kp), dtype=torch.float32, device=w.device)
+        wp[:w.shape[0], :w.shape[1]].copy_(w)
+        return wp
+    return _w_t(layers[0], ("head", kp, npad, len(layers)), tuple(l.weight for l in layers), build_2d, dt)
+
+
+def _head_linear_fwd(x2d, residual, layers, dt, out_dtype, relu: bool, npad: int, want_gate: bool):
+    """(y [M, npad], gate | None, the operand rows in dt).  gate is what the ReLU's backward reads: the output itself, or — under
+    a residual, where the output no longer tells — the pre-activation the same launch stores (uc_gemm preact_out)."""
+    x2d = _c(x2d)
+    xb = x2d if x2d.dtype == dt else ops.convert(x2d, dt)
+    w, b = head_weights(layers, dt, xb.shape[1], npad)
+    if relu and residual is not None and want_gate:
+        gate = torch.empty((xb.shape[0], npad), dtype=out_dtype, device=xb.device)
+        return ops.gemm(xb, w, b, act="relu", residual=residual, out_dtype=out_dtype, preact_out=gate), gate, xb
+    y = ops.gemm(xb, w, b, act="relu" if relu else None, residual=residual, out_dtype=out_dtype)
+    return y, (y if relu and want_gate else None), xb
+
+
+@_sink_aware
+class HeadLinearFn(Function):
+    """y = [relu](x W^T + b) [+ residual] over padded widths, optionally followed by the mean over each sample's T rows
+    (pool = (B, T): the ResConvBlock's last convolution and the AdaptiveAvgPool2d(1) after it as one node, whose backward
+    writes the ReLU-gated broadcast with uc_token_pool_bwd instead of storing the broadcast map first)."""
+
+    @staticmethod
+    def forward(ctx, x2d, residual, layers, dt, out_dtype, relu, npad, pool, *params):
+        y, gate, xb = _head_linear_fwd(x2d, residual, layers, dt, dt if pool else out_dtype, relu, npad, True)
+        ctx.save_for_backward(xb, gate)
+        ctx.layers, ctx.dt, ctx.relu, ctx.npad, ctx.pool, ctx.x_dtype = layers, dt, relu, npad, pool, x2d.dtype
+        ctx.res_dtype = None if residual is None else residual.dtype
+        return ops.token_pool(y, *pool) if pool else y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, gate = ctx.saved_tensors
+        layers, dt, npad = ctx.layers, ctx.dt, ctx.npad
+        dy = _c(dy)
+        dres = None
+        if ctx.pool:
+            T = ctx.pool[1]
+            g = dy if dy.dtype == torch.float32 else ops.convert(dy, torch.float32)
+            du = ops.token_pool_bwd(g, T, dt, gate if ctx.relu else None)
+            if ctx.res_dtype is not None and ctx.needs_input_grad[1]:
+                dres = ops.token_pool_bwd(g, T, ctx.res_dtype)
+        else:
+            if ctx.res_dtype is not None and ctx.needs_input_grad[1]:
+                dres = dy if dy.dtype == ctx.res_dtype else ops.convert(dy, ctx.res_dtype)
+            du = dy
+            if ctx.relu:
+                du = ops.act_bwd(dy if dy.dtype == gate.dtype else ops.convert(dy, gate.dtype), gate, "relu")
+        du = _as_dt(_c(du), dt)
+        kp = xb.shape[1]
+        rows = [l.weight.shape[0] for l in layers]
+        K = layers[0].weight[0].numel()
+        sink = None
+        if sum(rows) == npad and K == kp:
+            sink, r = [], 0
+            for l, n in zip(layers, rows):
+                sink.append((l.weight, r, r + n))
+                r += n
+        dW, db = _wgrad(du, xb, dt, True, sink=sink)
+        grads, r = [], 0
+        for l, n in zip(layers, rows):
+            grads.append(None if dW is None else dW[r:r + n, :K].reshape(l.weight.shape))
+            grads.append(None if l.bias is None else db[r:r + n])
+            r += n
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.gemm(du, _head_weight_t(layers, dt, kp, npad), out_dtype=ctx.x_dtype)
+        return (dx, dres, None, None, None, None, None, None) + tuple(grads)
+
+
+def head_linear(x2d, layers, dt, out_dtype=None, relu: bool = False, residual=None, npad: Optional[int] = None, pool=None):
+    """One layer of a summary head on padded widths (see above): x2d [M, Kp] -> [M, npad] in out_dtype (default dt), or the
+    fp32 [B, npad] mean over each sample's T rows with pool = (B, T).  `layers`: one nn.Linear / 1x1 nn.Conv2d, or several
+    sharing the input (their outputs side by side).  Records a HeadLinearFn when a gradient is needed, else only launches."""
+    layers = tuple(layers)
+    N, K = sum(l.weight.shape[0] for l in layers), layers[0].weight[0].numel()
+    npad = head_pad(N) if npad is None else npad
+    if x2d.shape[1] < K or npad < N or (residual is not None and residual.shape[1] != npad):
+        raise UcHipError(f"head_linear: operand width {x2d.shape[1]} / padded output width {npad} do not fit a [{N}, {K}] layer")
+    params = tuple(t for l in layers for t in (l.weight, l.bias))
+    if grad_needed(x2d, residual, *params):
+        return HeadLinearFn.apply(x2d, residual, layers, dt, out_dtype or dt, relu, npad, pool, *params)
+    y, _, _ = _head_linear_fwd(x2d, residual, layers, dt, dt if pool else (out_dtype or dt), relu, npad, False)
+    return ops.token_pool(y, *pool) if pool else y
+
+
+@_sink_aware
+class TokenPoolFn(Function):
+    "mean over each sample's T rows (nn.AdaptiveAvgPool2d(1) on the token matrix); backward: the broadcast of uc_token_pool_bwd."
+
+    @staticmethod
+    def forward(ctx, x2d, B, T):
+        ctx.T, ctx.x_dtype = T, x2d.dtype
+        return ops.token_pool(x2d, B, T)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _c(dy)
+        return ops.token_pool_bwd(dy if dy.dtype == torch.float32 else ops.convert(dy, torch.float32), ctx.T, ctx.x_dtype), None, None
+
+
+def token_pool(x2d, B: int, T: int):
+    return TokenPoolFn.apply(x2d, B, T) if grad_needed(x2d) else ops.token_pool(x2d, B, T)

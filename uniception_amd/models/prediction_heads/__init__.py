@@ -2,3 +2,7 @@
 from .base import (AdaptorInput, AdaptorOutput, PixelTaskOutput, PredictionHeadInput, PredictionHeadLayeredInput,  # noqa: F401
                    PredictionHeadOutput, RegressionAdaptorOutput, RegressionWithConfidenceAdaptorOutput,
                    UniCeptionAdaptorBase, UniCeptionPredictionHeadBase)
+from .base import PredictionHeadTokenInput, SummaryTaskOutput  # noqa: F401,E402
+from .global_head import GlobalHead  # noqa: F401,E402
+from .mlp_head import MLPHead  # noqa: F401,E402
+from .pose_head import PoseHead, ResConvBlock  # noqa: F401,E402

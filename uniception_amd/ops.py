@@ -1214,3 +1214,34 @@ def diff_attention_combine_bwd(dy: torch.Tensor, a1: torch.Tensor, a2: torch.Ten
                                                  dy.stride(2), float(lambda_full), float(rms_eps), float(out_scale), _stream()),
                "uc_diff_attention_combine_bwd")
     return da1, da2, dw, dl
+
+
+def token_pool(x: torch.Tensor, B: int, T: int) -> torch.Tensor:
+    """x [B*T, C] (fp32 / bf16 / fp16, unit column stride, row stride >= C) -> fp32 [B, C], the mean over each sample's T rows
+    (uc_token_pool: fp32 accumulation, chunk partials added in a fixed order — bit-reproducible)."""
+    _need_gpu(x)
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[0] != B * T or B <= 0 or T <= 0:
+        raise UcHipError(f"token_pool: [B*T, C] rows with unit column stride expected (got {tuple(x.shape)}, strides {x.stride()}, B={B}, T={T})")
+    Cn = x.shape[1]
+    lib = _lib.load()
+    out = torch.empty((B, Cn), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(1, lib.uc_token_pool_ws_bytes(B, T, Cn) // 4), dtype=torch.float32, device=x.device)
+    _lib.check(lib.uc_token_pool(x.data_ptr(), _dt(x.dtype), x.stride(0), out.data_ptr(), ws.data_ptr(), B, T, Cn, _stream()), "uc_token_pool")
+    return out
+
+
+def token_pool_bwd(g: torch.Tensor, T: int, out_dtype: torch.dtype, gate: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """g fp32 [B, C] -> [B*T, C] in out_dtype: g[b] / T on each of the sample's T rows, zeroed where gate <= 0 (gate [B*T, C] in
+    out_dtype: the pre-activation or the output of the ReLU that fed the pooled sum)."""
+    _need_gpu(g, gate)
+    if g.dim() != 2 or g.dtype != torch.float32 or not g.is_contiguous() or T <= 0:
+        raise UcHipError(f"token_pool_bwd: contiguous fp32 [B, C] gradient expected (got {tuple(g.shape)}, {g.dtype})")
+    B, Cn = g.shape
+    if gate is not None and (gate.shape != (B * T, Cn) or gate.dtype != out_dtype or gate.stride(1) != 1):
+        raise UcHipError(f"token_pool_bwd: gate must be [B*T, C] in {out_dtype} with unit column stride (got {tuple(gate.shape)}, {gate.dtype})")
+    vec = 4 if out_dtype == torch.float32 else 8
+    ld = (Cn + vec - 1) // vec * vec        # 16-byte rows; the caller sees the [B*T, C] view
+    buf = torch.empty((B * T, ld), dtype=out_dtype, device=g.device)
+    _lib.check(_lib.load().uc_token_pool_bwd(g.data_ptr(), _p(gate), 0 if gate is None else gate.stride(0), buf.data_ptr(), ld, _dt(out_dtype),
+                                             B, T, Cn, _stream()), "uc_token_pool_bwd")
+    return buf if ld == Cn else buf[:, :Cn]
