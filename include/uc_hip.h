@@ -60,8 +60,10 @@ const char* uc_last_error(void);
  *       shape, dense or conv) replaces the conv-only tile-count query of version 9.
  *   17: differential attention — uc_diff_attention_desc, uc_diff_attention_fwd, uc_diff_attention_combine_bwd,
  *       uc_diff_attention_combine_ws_bytes added (nothing existing changed).
- *   18: token pooling of the summary heads — uc_token_pool, uc_token_pool_ws_bytes, uc_token_pool_bwd added (nothing existing changed). */
-#define UC_ABI_VERSION 18
+ *   18: token pooling of the summary heads — uc_token_pool, uc_token_pool_ws_bytes, uc_token_pool_bwd added (nothing existing changed).
+ *   19: the MoGe head's channels-last passes — uc_group_norm_nhwc (+ _bwd, two _ws_bytes queries), uc_replicate_pad_nhwc (+ _bwd),
+ *       uc_crop_add_nhwc, uc_crop_embed_nhwc, uc_resize_bilinear_nhwc (+ _bwd) added (nothing existing changed). */
+#define UC_ABI_VERSION 19
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -657,6 +659,56 @@ int64_t uc_token_pool_ws_bytes(int64_t B, int64_t T, int64_t C);
 int uc_token_pool(const void* x, int dtype, int64_t ld, float* out, float* ws, int64_t B, int64_t T, int64_t C, uc_stream_t stream);
 int uc_token_pool_bwd(const float* g, const void* gate, int64_t ld_gate, void* out, int64_t ld_out, int dtype, int64_t B, int64_t T,
                       int64_t C, uc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * GroupNorm on channels-last maps (MoGe head: prediction_heads/moge_conv.py:44-52, nn.GroupNorm + ReLU in front of every 3x3 convolution).
+ *   x, y: [B, H, W, C] in `dtype` (UC_F32 | UC_BF16 | UC_F16), G groups of C / G contiguous channels, (C / G) % 8 == 0, C <= 2048;
+ *   gamma, beta: fp32 [C];  mean, rstd: fp32 [B, G] (written by the forward, read by the backward).
+ *   uc_group_norm_nhwc:  y = act((x - mean) rstd gamma + beta), act = ReLU when relu != 0.  Statistics in fp32: every workgroup
+ *     takes one chunk of pixels of one sample, forms the chunk mean and the squared deviations from it (nothing cancels) and stores
+ *     (mean, M2) per (sample, chunk, group) in ws (uc_group_norm_nhwc_ws_bytes, caller-provided); a second kernel merges the chunks
+ *     in a fixed order with Chan's formula; a third applies.  No atomics: the same bits on every run.
+ *   uc_group_norm_nhwc_bwd:  with g = dy (g = 0 where gate <= 0 when gate != NULL: the forward's y under a fused ReLU),
+ *     x^ = (x - mean) rstd and m = H W C / G:
+ *       dx = rstd (g gamma - sum_group(g gamma) / m - x^ sum_group(g gamma x^) / m)          (dtype)
+ *       dgamma[c] = sum_{b,h,w} g x^,  dbeta[c] = sum_{b,h,w} g                               (fp32, overwritten)
+ *     every reduction in two fixed-order stages through ws (uc_group_norm_nhwc_bwd_ws_bytes).
+ * Every argument is checked before anything is launched (UC_ERR_BAD_ARG, message prefixed with the function name).
+ * ---------------------------------------------------------------------------------- */
+int64_t uc_group_norm_nhwc_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G);
+int uc_group_norm_nhwc(const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd, float* ws, int dtype,
+                       int B, int H, int W, int C, int G, float eps, int relu, uc_stream_t stream);
+int64_t uc_group_norm_nhwc_bwd_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G);
+int uc_group_norm_nhwc_bwd(const void* dy, const void* x, const void* gate, const float* mean, const float* rstd, const float* gamma,
+                           void* dx, float* dgamma, float* dbeta, float* ws, int dtype, int B, int H, int W, int C, int G,
+                           uc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Replicate padding by one pixel, the crop that undoes it, and their adjoints (NHWC, C % 8 == 0, any of the three dtypes).  A
+ * replicate-padded 3x3 convolution (padding_mode="replicate", moge_conv.py:47-51,170,188) is pad -> uc_gemm's zero-padded 3x3
+ * convolution on the (H + 2) x (W + 2) map -> crop: the interior of that output is the replicate-padded convolution exactly.
+ *   uc_replicate_pad_nhwc:      dst[b, y, x] = src[b, clamp(y - 1, 0, H - 1), clamp(x - 1, 0, W - 1)],  dst [B, H + 2, W + 2, C]
+ *   uc_replicate_pad_nhwc_bwd:  dx[b, y, x] = the sum of dy over the padded positions that clamp to (y, x), in a fixed order
+ *   uc_crop_add_nhwc:           dst[b, y, x] = act(src[b, y + 1, x + 1] (+ residual[b, y, x])),  src [B, H + 2, W + 2, C];
+ *                               residual may be NULL; act = ReLU when relu != 0
+ *   uc_crop_embed_nhwc:         dst [B, H + 2, W + 2, C] = dy in the interior, zeros on the ring (adjoint of the crop)
+ * H and W are always those of the UNPADDED map.
+ * ---------------------------------------------------------------------------------- */
+int uc_replicate_pad_nhwc(const void* src, void* dst, int dtype, int B, int H, int W, int C, uc_stream_t stream);
+int uc_replicate_pad_nhwc_bwd(const void* dy, void* dx, int dtype, int B, int H, int W, int C, uc_stream_t stream);
+int uc_crop_add_nhwc(const void* src, const void* residual, void* dst, int dtype, int B, int H, int W, int C, int relu, uc_stream_t stream);
+int uc_crop_embed_nhwc(const void* dy, void* dst, int dtype, int B, int H, int W, int C, uc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Bilinear resize of an NHWC map [B, Hi, Wi, C] -> [B, Ho, Wo, C] (C % 8 == 0) and its adjoint (a gather: no atomics).
+ *   align_corners == 0: PyTorch's half-pixel rule (F.interpolate(mode="bilinear", align_corners=False), moge_conv.py:222):
+ *     src = max(0, (dst + 0.5) in / out - 0.5), upper neighbour clamped to in - 1; coordinates evaluated exactly in integers.
+ *   align_corners != 0: the kernels of uc_bilinear_nhwc / uc_bilinear_nhwc_bwd without a crop, bit for bit.
+ * ---------------------------------------------------------------------------------- */
+int uc_resize_bilinear_nhwc(const void* src, void* dst, int dtype, int B, int Hi, int Wi, int C, int Ho, int Wo, int align_corners,
+                            uc_stream_t stream);
+int uc_resize_bilinear_nhwc_bwd(const void* dy, void* dx, int dtype, int B, int Hi, int Wi, int C, int Ho, int Wo, int align_corners,
+                                uc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -158,12 +158,22 @@ SIGNATURES = {
     "uc_token_pool_ws_bytes": [i64, i64, i64],
     "uc_token_pool": [vp, i32, i64, vp, vp, i64, i64, i64, vp],
     "uc_token_pool_bwd": [vp, vp, i64, vp, i64, i32, i64, i64, i64, vp],
+    "uc_group_norm_nhwc_ws_bytes": [i64, i64, i64, i64, i64],
+    "uc_group_norm_nhwc": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp],
+    "uc_group_norm_nhwc_bwd_ws_bytes": [i64, i64, i64, i64, i64],
+    "uc_group_norm_nhwc_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "uc_replicate_pad_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "uc_replicate_pad_nhwc_bwd": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "uc_crop_add_nhwc": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "uc_crop_embed_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "uc_resize_bilinear_nhwc": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "uc_resize_bilinear_nhwc_bwd": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
 }
 
 _lib = None
 
 
-ABI_VERSION = 18   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 19   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

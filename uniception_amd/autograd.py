@@ -1493,3 +1493,365 @@ class TokenPoolFn(Function):
 
 def token_pool(x2d, B: int, T: int):
     return TokenPoolFn.apply(x2d, B, T) if grad_needed(x2d) else ops.token_pool(x2d, B, T)
+
+
+# =================================================================================================================
+# MoGe convolutional head (prediction_heads/moge_conv.py) and MLPFeature (prediction_heads/mlp_feature.py).
+# GroupNorm (+ ReLU), the replicate-padded 3x3 convolution as pad -> zero-padded conv on the (H + 2) x (W + 2) map -> crop
+# (+ residual, + ReLU), the half-pixel resize, the channel-padded forms of the transposed and the 3x3 convolution (the two UV
+# channels make the channel counts 514 / 258 / 130 / 66: zero-padded to the GEMM's granule, the zero columns built into the
+# prepared weights), the sum of the 1x1 projections as one GEMM over K-concatenated operands, and the Mlp of MLPFeature.
+# =================================================================================================================
+def check_group_size(C: int, G: int, what: str = "group_norm") -> None:
+    "what uc_group_norm_nhwc would reject, said before any tensor is touched"
+    if G <= 0 or C % G != 0 or (C // G) % 8 != 0:
+        raise UcHipError(f"{what}: {C} channels in {G} groups: channels per group ({C / max(G, 1):g}) must be a multiple of 8 "
+                         "(uc_group_norm_nhwc)")
+
+
+@_sink_aware
+class GroupNormFn(Function):
+    "y = [relu](GroupNorm(x)) on an NHWC map (uc_group_norm_nhwc / uc_group_norm_nhwc_bwd)."
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gn, relu):
+        x = _c(x)
+        g, b = engine.ln_params(gn)
+        y, mean, rstd = ops.group_norm_nhwc(x, g, b, gn.num_groups, gn.eps, relu)
+        ctx.save_for_backward(x, g, mean, rstd, y if relu else torch.empty(0))
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, g, mean, rstd, y = ctx.saved_tensors
+        dx, dg, db = ops.group_norm_nhwc_bwd(_as_dt(_c(dy), x.dtype), x, mean, rstd, g, gate=y if ctx.relu else None)
+        return dx, dg, db, None, None
+
+
+def group_norm(x, gn, relu: bool):
+    check_group_size(x.shape[-1], gn.num_groups)
+    if gn.weight is None:
+        raise UcHipError("group_norm: GroupNorm(affine=False) has no HIP path")
+    return GroupNormFn.apply(x, gn.weight, gn.bias, gn, relu)
+
+
+@_sink_aware
+class ReplicatePadFn(Function):
+    @staticmethod
+    def forward(ctx, x):
+        return ops.replicate_pad_nhwc(_c(x))
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.replicate_pad_nhwc_bwd(_c(dy))
+
+
+@_sink_aware
+class CropAddFn(Function):
+    "act(padded[:, 1:-1, 1:-1] (+ residual)); the ReLU's backward gates on the output."
+
+    @staticmethod
+    def forward(ctx, xp, residual, relu):
+        y = ops.crop_add_nhwc(_c(xp), None if residual is None else _c(residual), relu)
+        ctx.save_for_backward(y if relu else torch.empty(0))
+        ctx.meta = (relu, residual is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        relu, has_res = ctx.meta
+        dy = _c(dy)
+        g = ops.act_bwd(dy, y, "relu") if relu else dy
+        return ops.crop_embed_nhwc(g), (g if has_res else None), None
+
+
+@_sink_aware
+class ResizeBilinearFn(Function):
+    @staticmethod
+    def forward(ctx, x, Ho, Wo, align_corners):
+        x = _c(x)
+        ctx.geom = (x.shape[1], x.shape[2], align_corners)
+        return ops.resize_bilinear_nhwc(x, Ho, Wo, align_corners)
+
+    @staticmethod
+    def backward(ctx, dy):
+        Hi, Wi, ac = ctx.geom
+        return ops.resize_bilinear_nhwc_bwd(_c(dy), Hi, Wi, ac), None, None, None
+
+
+def resize_bilinear(x, Ho: int, Wo: int, align_corners: bool):
+    return ResizeBilinearFn.apply(x, Ho, Wo, align_corners)
+
+
+def _conv3x3_padded_weights(conv, dt, cin_pad: int, cout_pad: int):
+    "conv3x3 weights [cout_pad, 9 * cin_pad] (K ordered (ky, kx, c)) with zero rows / columns for the padded channels; bias fp32 [cout_pad]"
+    def build():
+        w = torch.zeros((cout_pad, 3, 3, cin_pad), dtype=torch.float32, device=conv.weight.device)
+        w[:conv.out_channels, :, :, :conv.in_channels] = conv.weight.detach().float().permute(0, 2, 3, 1)
+        b = torch.zeros(cout_pad, dtype=torch.float32, device=conv.weight.device)
+        if conv.bias is not None:
+            b[:conv.out_channels] = conv.bias.detach().float()
+        return w.reshape(cout_pad, -1).to(dt).contiguous(), b
+    return engine.prepared(conv, ("c3pad", dt, cin_pad, cout_pad), (conv.weight, conv.bias), build)
+
+
+def _conv3x3_padded_rot_weight(conv, dt, cin_pad: int, cout_pad: int):
+    "data-gradient weight [cin_pad, 9 * cout_pad], K ordered (ky', kx', o) = W[o, c, 2 - ky', 2 - kx'] (see _conv3x3_rot_weight)"
+    def build():
+        w = torch.zeros((cin_pad, 3, 3, cout_pad), dtype=torch.float32, device=conv.weight.device)
+        w[:conv.in_channels, :, :, :conv.out_channels] = conv.weight.detach().float().flip(2, 3).permute(1, 2, 3, 0)
+        return w.reshape(cin_pad, -1).to(dt).contiguous()
+    return engine.prepared(conv, ("c3padrot", dt, cin_pad, cout_pad), (conv.weight,), build)
+
+
+@_sink_aware
+class Conv3x3PaddedFn(Function):
+    """Zero-padded 3x3 convolution (stride 1) of an NHWC map whose channel count was padded with zero channels to `cin_pad`, to
+    `cout_pad` output channels (zero weight rows): the output block's Conv2d(64 + 2 -> 32) and Conv2d(32 -> dim_out, 3)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, conv, cout_pad, out_dtype):
+        x = _c(x)
+        B, H, W, cin_pad = x.shape
+        w, b = _conv3x3_padded_weights(conv, x.dtype, cin_pad, cout_pad)
+        ctx.save_for_backward(x)
+        ctx.meta = (conv, cout_pad, bias is not None)
+        return ops.gemm(x, w, b, conv=(B, H, W, cin_pad, 1), out_dtype=out_dtype).view(B, H, W, cout_pad)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        conv, cout_pad, has_b = ctx.meta
+        B, H, W, cin_pad = x.shape
+        dt = x.dtype
+        dy = _c(dy)
+        dz = _as_dt(dy, dt)
+        if has_b and dy.dtype != dt:       # an fp32 cotangent (the head's last layer): the bias gradient sums it unrounded
+            dWg, db = _wgrad_conv(dz, x, 1, False)[0], _colsum(dy.view(-1, cout_pad))
+        else:
+            dWg, db = _wgrad_conv(dz, x, 1, False, has_b)
+        dW = dWg.view(cout_pad, 3, 3, cin_pad)[:conv.out_channels, :, :, :conv.in_channels].permute(0, 3, 1, 2)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.gemm(dz, _conv3x3_padded_rot_weight(conv, dt, cin_pad, cout_pad), conv=(B, H, W, cout_pad, 1)).view(B, H, W, cin_pad)
+        return dx, dW, (db[:conv.out_channels] if has_b else None), None, None, None
+
+
+@_sink_aware
+class OutConv1x1Fn(Function):
+    """The head's last 1x1 convolution (dim_out channels, zero-padded to `cpad`; fp32 output): PaddedConv1x1Fn whose bias gradient is the
+    column sum of the fp32 cotangent itself, not of its copy rounded to the operand dtype (a sum over every pixel of the image in which
+    the rounding errors of the summands do not average out against a cancelling total)."""
+
+    @staticmethod
+    def forward(ctx, x2d, weight, bias, conv, dt, cpad):
+        x2d = _c(x2d)
+        xb = x2d if x2d.dtype == dt else ops.convert(x2d, dt)
+        w, b = padded_conv1x1_weights(conv, dt, cpad)
+        ctx.save_for_backward(xb)
+        ctx.meta = (conv, dt, x2d.dtype, weight.shape, bias is not None, cpad)
+        return ops.gemm(xb, w, b, out_dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (xb,) = ctx.saved_tensors
+        conv, dt, x_dtype, wshape, has_b, cpad = ctx.meta
+        n = wshape[0]
+        dy = _c(dy)
+        dyb = _as_dt(dy, dt)
+        dW, _ = _wgrad(dyb, xb, dt)
+        db = _colsum(dy)[:n] if has_b else None
+        dx = None
+        if ctx.needs_input_grad[0]:
+            def padded32():
+                w = torch.zeros(cpad, conv.in_channels, device=conv.weight.device)
+                w[:n] = conv.weight.detach().reshape(n, -1).float()
+                return w
+            dx = ops.gemm(dyb, _w_t(conv, "c1pad", (conv.weight,), padded32, dt), out_dtype=x_dtype)
+        return dx, dW[:n].reshape(wshape), db, None, None, None
+
+
+def out_conv1x1(x, conv, dt, cpad):
+    B, H, W, Cin = x.shape
+    return OutConv1x1Fn.apply(x.reshape(-1, Cin), conv.weight, conv.bias, conv, dt, cpad).view(B, H, W, cpad)
+
+
+def check_conv3x3_replicate(conv) -> None:
+    if conv.padding_mode != "replicate":
+        raise UcHipError(f"conv3x3_replicate: padding_mode={conv.padding_mode!r} has no HIP path (supported: 'replicate')")
+    if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1:
+        raise UcHipError("conv3x3_replicate: only a dense 3x3 convolution of stride 1 has a HIP path")
+
+
+def replicate_pad(x):
+    "[B, H, W, C] -> [B, H + 2, W + 2, C], border pixels repeated; differentiable"
+    return ReplicatePadFn.apply(x)
+
+
+def conv3x3_replicate(x, conv, residual=None, relu_out: bool = False, out_dtype=None, padded: bool = False):
+    """Conv2d(k=3, padding=1, padding_mode="replicate") on an NHWC map: pad -> zero-padded convolution on the (H + 2) x (W + 2) map ->
+    crop (+ residual, + ReLU).  x may carry zero channels beyond conv.in_channels; the result has head_pad(conv.out_channels, 8)
+    channels (zero beyond the real ones).  padded: x is already the replicate-padded map (several convolutions of one map share
+    one pad pass and one adjoint)."""
+    check_conv3x3_replicate(conv)
+    cin_pad, cout_pad = x.shape[-1], head_pad(conv.out_channels, 8)
+    xp = x if padded else ReplicatePadFn.apply(x)
+    if cin_pad == conv.in_channels and cout_pad == conv.out_channels and out_dtype in (None, x.dtype):
+        yp = Conv3x3Fn.apply(xp, conv.weight, conv.bias, None, None, conv, False, None, None)
+    else:
+        yp = Conv3x3PaddedFn.apply(xp, conv.weight, conv.bias, conv, cout_pad, out_dtype)
+    return CropAddFn.apply(yp, residual, relu_out)
+
+
+def _convt_padded_weights(ct, dt, kpad: int):
+    "engine.convt_weights with the input-channel (K) axis zero-padded to kpad columns"
+    k = ct.kernel_size[0]
+
+    def build():
+        w = torch.zeros((k * k * ct.out_channels, kpad), dtype=dt, device=ct.weight.device)
+        w[:, :ct.in_channels] = ct.weight.detach().permute(2, 3, 1, 0).reshape(k * k * ct.out_channels, ct.in_channels).to(dt)
+        b = None if ct.bias is None else ct.bias.detach().float().repeat(k * k).contiguous()
+        return w, b
+    return engine.prepared(ct, ("ctpad", dt, kpad), (ct.weight, ct.bias), build)
+
+
+@_sink_aware
+class ConvTransposePaddedFn(Function):
+    "ConvTransposeFn on a map whose channel axis was zero-padded to a multiple of the dense GEMM's K granule (514 -> 576, ...)."
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, ct):
+        x = _c(x)
+        B, H, W, kpad = x.shape
+        k = ct.kernel_size[0]
+        w, b = _convt_padded_weights(ct, x.dtype, kpad)
+        x2 = x.view(-1, kpad)
+        ctx.save_for_backward(x2)
+        ctx.meta = (ct, k, (B, H, W, kpad), bias is not None)
+        return ops.convt_scatter(ops.gemm(x2, w, b), B, H, W, k, ct.out_channels)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x2,) = ctx.saved_tensors
+        ct, k, (B, H, W, kpad), has_b = ctx.meta
+        dt = x2.dtype
+        Cout, Cin = ct.out_channels, ct.in_channels
+        dyg = ops.convt_gather(_as_dt(_c(dy), dt), k)
+        dWg, dbg = _wgrad(dyg, x2, dt, has_b)
+        dW = dWg.view(k, k, Cout, kpad)[..., :Cin].permute(3, 2, 0, 1)
+        db = dbg.view(k * k, Cout).sum(0) if has_b else None
+        dx = None
+        if ctx.needs_input_grad[0]:
+            def padded32():
+                w = torch.zeros((k * k * Cout, kpad), dtype=torch.float32, device=ct.weight.device)
+                w[:, :Cin] = ct.weight.detach().permute(2, 3, 1, 0).reshape(k * k * Cout, Cin).float()
+                return w
+            dx = ops.gemm(dyg, _w_t(ct, ("ctpad", kpad), (ct.weight,), padded32, dt)).view(B, H, W, kpad)
+        return dx, dW, db, None
+
+
+def conv_transpose_padded(x, ct):
+    if ct.kernel_size != ct.stride or ct.kernel_size[0] != ct.kernel_size[1] or ct.padding != (0, 0) or ct.output_padding != (0, 0):
+        raise UcHipError("conv_transpose_padded: only ConvTranspose2d(kernel = stride, no padding) has a HIP path")
+    return ConvTransposePaddedFn.apply(x, ct.weight, ct.bias, ct)
+
+
+def _cat_k_weights(layers, dt):
+    "(W [N, sum K_i] in dt, sum of the biases fp32) of 1x1 convolutions whose outputs are added: one GEMM over K-concatenated operands"
+    def build():
+        w = torch.cat([l.weight.detach().reshape(l.weight.shape[0], -1).float() for l in layers], 1).to(dt).contiguous()
+        bs = [l.bias.detach().float() for l in layers if l.bias is not None]
+        return w, (torch.stack(bs, 0).sum(0).contiguous() if bs else None)
+    return engine.prepared(layers[0], ("catk", dt, len(layers)), tuple(t for l in layers for t in (l.weight, l.bias)), build)
+
+
+@_sink_aware
+class SumLinearFn(Function):
+    "sum_i (x_i W_i^T + b_i) as one GEMM: x2d = [x_0 | x_1 | ...] (K-concatenated rows), params = weights then biases."
+
+    @staticmethod
+    def forward(ctx, x2d, layers, dt, *params):
+        x2d = _c(x2d)
+        xb = x2d if x2d.dtype == dt else ops.convert(x2d, dt)
+        w, b = _cat_k_weights(layers, dt)
+        ctx.save_for_backward(xb)
+        ctx.meta = (layers, dt, x2d.dtype)
+        return ops.gemm(xb, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (xb,) = ctx.saved_tensors
+        layers, dt, x_dtype = ctx.meta
+        dyb = _as_dt(_c(dy), dt)
+        has_b = any(l.bias is not None for l in layers)
+        dW, db = _wgrad(dyb, xb, dt, has_b)
+        dws, k0 = [], 0
+        for l in layers:
+            k1 = k0 + l.weight[0].numel()
+            dws.append(dW[:, k0:k1].reshape(l.weight.shape))
+            k0 = k1
+        dx = None
+        if ctx.needs_input_grad[0]:
+            wT = _w_t(layers[0], ("catk", len(layers)), tuple(l.weight for l in layers),
+                      lambda: torch.cat([l.weight.detach().reshape(l.weight.shape[0], -1).float() for l in layers], 1).contiguous(), dt)
+            dx = ops.gemm(dyb, wT, out_dtype=x_dtype)
+        return (dx, None, None, *dws, *[(db if l.bias is not None else None) for l in layers])
+
+
+def sum_linear(x2d, layers, dt):
+    layers = tuple(layers)
+    return SumLinearFn.apply(x2d, layers, dt, *[l.weight for l in layers], *[l.bias for l in layers])
+
+
+@_sink_aware
+class MlpFn(Function):
+    "fc2(act(fc1(x))) on token rows: MlpSubLayerFn without the LayerNorm and the residual (MLPFeature's Mlp, mlp_feature.py:57-63)."
+
+    @staticmethod
+    def forward(ctx, x2d, w1_, b1_, w2_, b2_, fc1, fc2, act, dt, drops=None):
+        x2d = _c(x2d)
+        h = x2d if x2d.dtype == dt else ops.convert(x2d, dt)
+        w1, b1 = engine.lin_weights(fc1, dt)
+        w2, b2 = engine.lin_weights(fc2, dt)
+        if act != "none" and (dt == torch.float32 or (dt == torch.bfloat16 and h.shape[1] % 64 == 0)):
+            u = torch.empty((h.shape[0], w1.shape[0]), dtype=dt, device=h.device)
+            a = ops.gemm(h, w1, b1, act=act, preact_out=u)
+        elif act != "none" and any(ctx.needs_input_grad):      # K off the direct-to-LDS granule: the pre-activation from its own launch
+            u = ops.gemm(h, w1, b1)
+            a = ops.gemm(h, w1, b1, act=act)
+        else:
+            u = a = ops.gemm(h, w1, b1, act=act)
+        if drops is not None and drops.mid is not None:
+            a = ops.mask_scale(a, drops.mid, 0, drops.mid_scale)
+        out = ops.gemm(a, w2, b2)
+        if drops is not None and drops.has_out:
+            out = _drop_out(out, drops)
+        masks, dspec = _drops_saved(drops)
+        ctx.save_for_backward(h, u, a, *masks)
+        ctx.meta = (fc1, fc2, act, dt, x2d.dtype, b1_ is not None, b2_ is not None, dspec)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        fc1, fc2, act, dt, x_dtype, has_b1, has_b2, dspec = ctx.meta
+        drops, (h, u, a) = _drops_restore(dspec, ctx.saved_tensors)
+        dyb = _as_dt(_c(dy), dt)
+        if drops is not None and drops.has_out:
+            dyb = _drop_out(dyb, drops)
+        dW2, db2, _, w2t = _out_linear_bwd(dyb, a, fc2, None, has_b2, dt)
+        if act != "none" and dt == torch.bfloat16 and w2t.shape[1] % 64 == 0:
+            du = ops.gemm(dyb, w2t, dact=(u, act))          # act'(u) applied in the data-gradient GEMM's epilogue
+        else:
+            da = ops.gemm(dyb, w2t)
+            du = ops.act_bwd(da, u, act) if act != "none" else da
+        if drops is not None and drops.mid is not None:
+            du = ops.mask_scale(du, drops.mid, 0, drops.mid_scale)
+        dW1, db1 = _wgrad(du, h, dt, has_b1, sink=[(fc1.weight, 0, fc1.weight.shape[0])], bias_sink=[fc1.bias])
+        dx = ops.gemm(du, lin_weight_t(fc1, dt), out_dtype=x_dtype) if ctx.needs_input_grad[0] else None
+        return (dx, dW1, db1, dW2, db2) + (None,) * 5
+
+
+def mlp(x2d, fc1, fc2, act, dt, drops=None):
+    return MlpFn.apply(x2d, fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc1, fc2, act, dt, drops)

@@ -6,3 +6,5 @@ from .base import PredictionHeadTokenInput, SummaryTaskOutput  # noqa: F401,E402
 from .global_head import GlobalHead  # noqa: F401,E402
 from .mlp_head import MLPHead  # noqa: F401,E402
 from .pose_head import PoseHead, ResConvBlock  # noqa: F401,E402
+from .mlp_feature import MLPFeature  # noqa: F401,E402
+from .moge_conv import MoGeConvFeature, ResidualConvBlock, normalized_view_plane_uv  # noqa: F401,E402

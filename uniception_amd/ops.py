@@ -1245,3 +1245,106 @@ def token_pool_bwd(g: torch.Tensor, T: int, out_dtype: torch.dtype, gate: Option
     _lib.check(_lib.load().uc_token_pool_bwd(g.data_ptr(), _p(gate), 0 if gate is None else gate.stride(0), buf.data_ptr(), ld, _dt(out_dtype),
                                              B, T, Cn, _stream()), "uc_token_pool_bwd")
     return buf if ld == Cn else buf[:, :Cn]
+
+
+# =================================================================================================================
+# MoGe head: GroupNorm, replicate pad / crop, half-pixel resize on NHWC maps
+# =================================================================================================================
+def _nhwc4(x: torch.Tensor):
+    _need_gpu(x)
+    assert x.is_contiguous() and x.dim() == 4
+    return x.shape
+
+
+def group_norm_nhwc(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, G: int, eps: float, relu: bool = False):
+    """(y, mean [B,G] fp32, rstd [B,G] fp32) of GroupNorm(G) on NHWC x, y = act((x - mean) rstd gamma + beta) in x's dtype
+    (uc_group_norm_nhwc: fp32 statistics from per-chunk (mean, M2) merged in a fixed order — bit-reproducible)."""
+    B, H, W, Cn = _nhwc4(x)
+    _need_gpu(gamma, beta)
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.is_contiguous() and beta.is_contiguous()
+    assert gamma.numel() == Cn and beta.numel() == Cn
+    lib = _lib.load()
+    y = torch.empty_like(x)
+    mean = torch.empty((B, G), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((B, G), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(1, lib.uc_group_norm_nhwc_ws_bytes(B, H, W, Cn, G) // 4), dtype=torch.float32, device=x.device)
+    _lib.check(lib.uc_group_norm_nhwc(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                      ws.data_ptr(), _dt(x.dtype), B, H, W, Cn, G, float(eps), 1 if relu else 0, _stream()), "uc_group_norm_nhwc")
+    return y, mean, rstd
+
+
+def group_norm_nhwc_bwd(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor,
+                        gate: Optional[torch.Tensor] = None):
+    """(dx in x's dtype, dgamma fp32 [C], dbeta fp32 [C]); gate: the forward's output under a fused ReLU (gradient 0 where gate <= 0)."""
+    B, H, W, Cn = _nhwc4(x)
+    _need_gpu(dy, gate, gamma)
+    assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous()
+    assert gate is None or (gate.shape == x.shape and gate.dtype == x.dtype and gate.is_contiguous())
+    assert mean.dtype == torch.float32 and rstd.dtype == torch.float32 and mean.is_contiguous() and rstd.is_contiguous() and mean.shape == rstd.shape
+    assert gamma.dtype == torch.float32 and gamma.is_contiguous() and gamma.numel() == Cn
+    G = mean.shape[1]
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    dg = torch.empty(Cn, dtype=torch.float32, device=x.device)
+    db = torch.empty(Cn, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(1, lib.uc_group_norm_nhwc_bwd_ws_bytes(B, H, W, Cn, G) // 4), dtype=torch.float32, device=x.device)
+    _lib.check(lib.uc_group_norm_nhwc_bwd(dy.data_ptr(), x.data_ptr(), _p(gate), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+                                          dx.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), _dt(x.dtype), B, H, W, Cn, G, _stream()),
+               "uc_group_norm_nhwc_bwd")
+    return dx, dg, db
+
+
+def replicate_pad_nhwc(x: torch.Tensor) -> torch.Tensor:
+    "[B,H,W,C] -> [B,H+2,W+2,C], the border pixels repeated (F.pad(mode='replicate') by one pixel)."
+    B, H, W, Cn = _nhwc4(x)
+    y = torch.empty((B, H + 2, W + 2, Cn), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.load().uc_replicate_pad_nhwc(x.data_ptr(), y.data_ptr(), _dt(x.dtype), B, H, W, Cn, _stream()), "uc_replicate_pad_nhwc")
+    return y
+
+
+def replicate_pad_nhwc_bwd(dy: torch.Tensor) -> torch.Tensor:
+    "adjoint of replicate_pad_nhwc: dy [B,H+2,W+2,C] -> dx [B,H,W,C]"
+    B, Hp, Wp, Cn = _nhwc4(dy)
+    dx = torch.empty((B, Hp - 2, Wp - 2, Cn), dtype=dy.dtype, device=dy.device)
+    _lib.check(_lib.load().uc_replicate_pad_nhwc_bwd(dy.data_ptr(), dx.data_ptr(), _dt(dy.dtype), B, Hp - 2, Wp - 2, Cn, _stream()),
+               "uc_replicate_pad_nhwc_bwd")
+    return dx
+
+
+def crop_add_nhwc(x: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+    "act(x[:, 1:-1, 1:-1] (+ residual)) of a padded map x [B,H+2,W+2,C] -> [B,H,W,C]"
+    B, Hp, Wp, Cn = _nhwc4(x)
+    H, W = Hp - 2, Wp - 2
+    if residual is not None:
+        _need_gpu(residual)
+        assert residual.shape == (B, H, W, Cn) and residual.dtype == x.dtype and residual.is_contiguous()
+    y = torch.empty((B, H, W, Cn), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.load().uc_crop_add_nhwc(x.data_ptr(), _p(residual), y.data_ptr(), _dt(x.dtype), B, H, W, Cn, 1 if relu else 0, _stream()),
+               "uc_crop_add_nhwc")
+    return y
+
+
+def crop_embed_nhwc(dy: torch.Tensor) -> torch.Tensor:
+    "adjoint of the crop: dy [B,H,W,C] -> [B,H+2,W+2,C] with a ring of zeros"
+    B, H, W, Cn = _nhwc4(dy)
+    y = torch.empty((B, H + 2, W + 2, Cn), dtype=dy.dtype, device=dy.device)
+    _lib.check(_lib.load().uc_crop_embed_nhwc(dy.data_ptr(), y.data_ptr(), _dt(dy.dtype), B, H, W, Cn, _stream()), "uc_crop_embed_nhwc")
+    return y
+
+
+def resize_bilinear_nhwc(x: torch.Tensor, Ho: int, Wo: int, align_corners: bool) -> torch.Tensor:
+    "bilinear resize of NHWC x to (Ho, Wo): PyTorch's half-pixel rule (align_corners=False) or uc_bilinear_nhwc's (True)"
+    B, Hi, Wi, Cn = _nhwc4(x)
+    y = torch.empty((B, Ho, Wo, Cn), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.load().uc_resize_bilinear_nhwc(x.data_ptr(), y.data_ptr(), _dt(x.dtype), B, Hi, Wi, Cn, Ho, Wo, 1 if align_corners else 0,
+                                                   _stream()), "uc_resize_bilinear_nhwc")
+    return y
+
+
+def resize_bilinear_nhwc_bwd(dy: torch.Tensor, Hi: int, Wi: int, align_corners: bool) -> torch.Tensor:
+    "adjoint of resize_bilinear_nhwc: dy [B,Ho,Wo,C] -> dx [B,Hi,Wi,C]"
+    B, Ho, Wo, Cn = _nhwc4(dy)
+    dx = torch.empty((B, Hi, Wi, Cn), dtype=dy.dtype, device=dy.device)
+    _lib.check(_lib.load().uc_resize_bilinear_nhwc_bwd(dy.data_ptr(), dx.data_ptr(), _dt(dy.dtype), B, Hi, Wi, Cn, Ho, Wo,
+                                                       1 if align_corners else 0, _stream()), "uc_resize_bilinear_nhwc_bwd")
+    return dx
