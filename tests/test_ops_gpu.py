@@ -1009,14 +1009,30 @@ def test_gemm_four_wave_kernel_is_bitwise_the_sixteen_wave_kernel(gpu, K):
             assert torch.equal(s2.stats(1e-6), s7.stats(1e-6))
 
 
-@pytest.mark.parametrize("B,H,Nq,Nk", [(2, 3, 1024, 1024), (1, 2, 1369, 1369), (2, 1, 300, 37), (1, 2, 256, 64), (3, 2, 512, 700), (1, 1, 260, 4096)])
-def test_attention_role_split_kernel_is_bitwise_the_dma_kernel(gpu, B, H, Nq, Nk):
+@pytest.fixture(scope="module")
+def attn_plan(tmp_path_factory):
+    from tests import attention_routes
+    return attention_routes.build_driver(tmp_path_factory.mktemp("attention_plan_ops"))
+
+
+_DMA8_WITNESS = "dma8_witness"      # tests/attention_routes.py: the smallest launch that takes the eight-wave kernels (sized by the CU count)
+
+
+@pytest.mark.parametrize("B,H,Nq,Nk", [(2, 3, 1024, 1024), (1, 2, 1369, 1369), (2, 1, 300, 37), (1, 2, 256, 64), (3, 2, 512, 700), (1, 1, 260, 4096),
+                                       pytest.param(0, 0, 0, 0, id=_DMA8_WITNESS)])
+def test_attention_role_split_kernel_is_bitwise_the_dma_kernel(gpu, attn_plan, B, H, Nq, Nk):
     """attn_bf16_rs_kernel (tuning knob attn_role_split): the eight-wave forward cut into matrix / vector segments that the two halves
     of a workgroup run one segment apart.  Same MFMAs on the same operands in the same order, same softmax arithmetic: the outputs
     and the log-sum-exp must equal the one-barrier-per-tile kernel's to the bit — one and many key tiles, ragged key / query counts,
-    and a spiked key that takes the rescale branch in a late tile."""
+    and a spiked key that takes the rescale branch in a late tile.  Which kernels were compared is asked of the plan for every shape
+    (the descriptor each launch passed, the device's CUs, the live knobs): the small shapes take the four-wave kernel under either knob
+    value; the witness shape must have compared rs8 with dma8."""
+    from tests import attention_routes as AR
     from uniception_amd import ops
     D = 64
+    witness = B == 0
+    if witness:
+        B, H, Nq, Nk = AR.shape_for(AR.WITNESSES["dma8"], torch.cuda.get_device_properties(gpu).multi_processor_count)
     g = torch.Generator().manual_seed(1000 + Nq + Nk)
     q = (torch.randn(B, Nq, H, D, generator=g) * 1.5).bfloat16()
     k = (torch.randn(B, Nk, H, D, generator=g) * 1.5).bfloat16()
@@ -1024,10 +1040,15 @@ def test_attention_role_split_kernel_is_bitwise_the_dma_kernel(gpu, B, H, Nq, Nk
     if Nk > 200:
         k[0, Nk - 7, 0] = q[0, 17, 0] * 6
     vt = ops.vt_pack(v.to(gpu))
-    outs = {}
+    outs, kernels = {}, {}
     for rs in (0, 1):
-        with ops.tuning("attn_role_split", rs):
+        with ops.tuning("attn_role_split", rs), AR.spy("uc_attention_fwd", AR.FWD_FIELDS) as cap:
             lse = torch.empty(B, H, Nq, device=gpu)
             outs[rs] = (ops.attention(q.to(gpu), k.to(gpu), vt, D ** -0.5, v_packed=True, lse=lse), lse)
+            assert len(cap) == 1
+            kernels[rs] = AR.route_of("fwd", attn_plan([{**cap[0], **AR.live_knobs(ops)}])[0])
+    print(f"role split 0 / 1 at {(B, H, Nq, Nk)}: {kernels[0]} against {kernels[1]}")
+    if witness:
+        assert kernels == {0: "dma8", 1: "rs8"}, kernels
     assert rel_l2(outs[1][0].cpu().float(), sdpa_ref(q, k, v, D ** -0.5)) < 8e-3
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
