@@ -209,3 +209,52 @@ def test_attention_descriptors_are_checked_before_any_launch():
     assert status != 0 and "unsupported dtype" in msg, msg
     d = _lib.AttnDesc(dtype=_lib.UC_F32, B=1, H=1, Nq=8, Nk=8, D=32, Q=4096, K=4096, V=4096, O=4096, scale=1.0, drop_p=-0.5)
     assert lib.uc_attention_fwd(C.byref(d), None) != 0 and lib.uc_last_error().decode().startswith("uc_attention_fwd: drop_p")
+
+
+def test_single_dtype_entry_points_reject_other_dtype_codes_before_any_launch():
+    """Every streaming entry point that takes ONE storage dtype rejects a code outside its set with UC_ERR_BAD_ARG and
+    '<fn>: unsupported dtype <d> (...)' before it launches anything: shapes are valid, the pointers are never dereferenced.  The table
+    is written out per entry point: which of them take fp16 (UC_F16 = 2) is part of the ABI, not of the dispatch macro.  Decided
+    entirely on the host, so it is skipped where a GPU is visible (a dispatch that wrongly accepted a code would launch on these
+    pointers)."""
+    import torch
+    from uniception_amd import _lib
+
+    if torch.cuda.is_available():
+        pytest.skip("GPU present: a wrongly accepted code would launch on invalid pointers")
+    lib = _lib.load()
+    P = 4096                    # 16-byte aligned, never dereferenced
+    D = "DTYPE"
+    F32_BF16, WITH_F16 = (2, 3, -1), (3, -1)
+    table = [
+        ("uc_patch_gather", F32_BF16, (P, P, D, 2, 3, 8, 8, 4, None)),                  # 16-byte pixel quads
+        ("uc_patch_gather", F32_BF16, (P, P, D, 2, 3, 6, 10, 2, None)),                 # any patch size
+        ("uc_bilinear_nhwc", WITH_F16, (P, P, D, 2, 3, 5, 16, 6, 10, 6, 10, None)),     # x2 upsampling (the several-rows form's range)
+        ("uc_bilinear_nhwc", WITH_F16, (P, P, D, 2, 6, 10, 16, 3, 5, 3, 5, None)),      # downsampling
+        ("uc_convt_scatter", WITH_F16, (P, P, D, 2, 3, 5, 2, 16, None)),
+        ("uc_pixel_shuffle", WITH_F16, (P, D, P, 2, 3, 5, 2, 16, None)),
+        ("uc_conv1x1_to4", WITH_F16, (P, D, P, P, P, 30, 16, None)),                    # aligned bias: the cooperative form's range
+        ("uc_conv1x1_to4", WITH_F16, (P, D, P, P + 4, P, 30, 16, None)),
+        ("uc_bilinear_nhwc_bwd", F32_BF16, (P, P, D, 2, 3, 5, 16, 6, 10, 6, 10, None)),
+        ("uc_convt_gather", F32_BF16, (P, P, D, 2, 3, 5, 2, 16, None)),
+        ("uc_im2col_t", F32_BF16, (P, P, D, 2, 3, 5, 16, 1, 0, 30, None)),
+        ("uc_dilate_nhwc", F32_BF16, (P, P, D, 2, 3, 5, 6, 10, 16, 2, None)),
+        ("uc_conv1x1_to4_bwd", F32_BF16, (P, D, P, P, P, P, P, 30, 16, 0, None)),
+        ("uc_colsum", F32_BF16, (P, D, 30, 16, 16, P, None)),
+        ("uc_act_bwd", F32_BF16, (P, P, P, D, _lib.UC_ACT_RELU, 480, None)),
+        ("uc_swiglu", F32_BF16, (P, P, D, 30, 16, None)),
+        ("uc_swiglu_bwd", F32_BF16, (P, P, P, D, 30, 16, None)),
+        ("uc_pixel_unshuffle", F32_BF16, (P, P, D, 2, 3, 5, 2, 16, None)),
+        ("uc_token_pool", WITH_F16, (P, D, 16, P, P, 2, 15, 16, None)),
+        ("uc_token_pool_bwd", WITH_F16, (P, P, 16, P, 16, D, 2, 15, 16, None)),
+    ]
+    converted = {"uc_patch_gather", "uc_bilinear_nhwc", "uc_convt_scatter", "uc_pixel_shuffle", "uc_conv1x1_to4", "uc_bilinear_nhwc_bwd",
+                 "uc_convt_gather", "uc_im2col_t", "uc_dilate_nhwc", "uc_conv1x1_to4_bwd", "uc_colsum", "uc_act_bwd", "uc_swiglu",
+                 "uc_swiglu_bwd", "uc_pixel_unshuffle", "uc_token_pool", "uc_token_pool_bwd"}
+    assert {name for name, _, _ in table} == converted
+    for name, rejected, args in table:
+        assert len(args) == len(_lib.SIGNATURES[name]) and args.count(D) == 1, name
+        for code in rejected:
+            status = getattr(lib, name)(*[code if a is D else a for a in args])
+            msg = lib.uc_last_error().decode()
+            assert status != 0 and msg.startswith(name + ":") and f"unsupported dtype {code} " in msg, (name, code, status, msg)

@@ -863,6 +863,18 @@ def test_bilinear(gpu, dtype, geom):
     assert rel_l2(got, ref) < (2e-6 if dtype == torch.float32 else 4e-3)
 
 
+@pytest.mark.parametrize("Ho,Wo", [(6, 10), (4, 7)])      # x2: the four-rows kernel (vertical scale <= 1/2); scale 2/3: the one-row kernel
+def test_bilinear_fp16(gpu, Ho, Wo):
+    """fp16 maps (the heads' default operand type).  Loads are exact and the arithmetic is fp32, so against the float64 interpolation
+    of the fp16 inputs only the one output rounding remains: 2^-11 relative per element, hence rel-L2 < 5e-4."""
+    from uniception_amd import ops
+    x = torch.randn(2, 16, 3, 5, generator=torch.Generator().manual_seed(13)).half()
+    ref = F.interpolate(x.double(), size=(Ho, Wo), mode="bilinear", align_corners=True)
+    out = ops.bilinear_nhwc(x.permute(0, 2, 3, 1).contiguous().to(gpu), Ho, Wo)
+    assert out.dtype == torch.float16 and out.shape == (2, Ho, Wo, 16)
+    assert rel_l2(out.cpu().double().permute(0, 3, 1, 2), ref) < 5e-4
+
+
 def test_bilinear_scale2_matches_scale_factor(gpu):
     """scale_factor=2, align_corners=True (dpt_block.py:251-253) == size=(2H,2W)."""
     from uniception_amd import ops
@@ -890,6 +902,14 @@ def test_convtranspose_as_gemm_plus_scatter(gpu, k):
     assert rel_l2(out.cpu().permute(0, 3, 1, 2), ref) < 3e-6
 
 
+def test_convt_scatter_fp16_is_the_pixel_permutation(gpu):
+    from uniception_amd import ops
+    B, h, w, k, Cout = 2, 3, 5, 2, 16
+    rows = torch.randn(B * h * w, k * k * Cout, generator=torch.Generator().manual_seed(14)).half()
+    ref = rows.view(B, h, w, k, k, Cout).permute(0, 1, 3, 2, 4, 5).reshape(B, k * h, k * w, Cout)      # [b, i*k + u, j*k + v, o]
+    assert torch.equal(ops.convt_scatter(rows.to(gpu), B, h, w, k, Cout).cpu(), ref)
+
+
 def test_pixel_shuffle(gpu):
     from uniception_amd import ops
     B, h, w, P, Cout = 2, 3, 5, 4, 4
@@ -898,6 +918,16 @@ def test_pixel_shuffle(gpu):
     src = y.permute(0, 2, 3, 1).reshape(B * h * w, Cout * P * P).contiguous()
     out = ops.pixel_shuffle(src.to(gpu), B, h, w, P, Cout)
     assert torch.equal(out.cpu(), ref)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_pixel_shuffle_16bit_rows(gpu, dtype):
+    from uniception_amd import ops
+    B, h, w, P, Cout = 2, 3, 5, 2, 16
+    y = torch.randn(B, Cout * P * P, h, w, generator=torch.Generator().manual_seed(15)).to(dtype)
+    src = y.permute(0, 2, 3, 1).reshape(B * h * w, Cout * P * P).contiguous()
+    out = ops.pixel_shuffle(src.to(gpu), B, h, w, P, Cout)
+    assert out.dtype == torch.float32 and torch.equal(out.cpu(), F.pixel_shuffle(y.float(), P))
 
 
 def test_pointmap_adaptor(gpu):
@@ -923,6 +953,18 @@ def test_conv1x1_to4(gpu, dtype, Cin):
     from uniception_amd import ops
     g = torch.Generator().manual_seed(16 + Cin)
     f = torch.randn(2, 37, 29, Cin, generator=g).to(dtype)
+    w = torch.randn(4, Cin, generator=g) / 11
+    b = torch.randn(4, generator=g)
+    ref = f.float() @ w.t() + b
+    out = ops.conv1x1_to4(f.to(gpu), w.to(gpu), b.to(gpu))
+    assert rel_l2(out.cpu(), ref) < 3e-6
+
+
+@pytest.mark.parametrize("Cin", [16, 24])   # 16: lane-cooperative kernel; 24: one-thread-per-pixel fallback
+def test_conv1x1_to4_fp16(gpu, Cin):
+    from uniception_amd import ops
+    g = torch.Generator().manual_seed(16 + Cin)
+    f = torch.randn(2, 3, 5, Cin, generator=g).half()
     w = torch.randn(4, Cin, generator=g) / 11
     b = torch.randn(4, generator=g)
     ref = f.float() @ w.t() + b

@@ -92,6 +92,23 @@ def test_token_pool_bwd_is_the_gated_broadcast(gpu, dtype, gated, B, T, C, ld):
         assert worst <= 2.0 ** -8
 
 
+def test_token_pool_and_its_backward_fp16(gpu):
+    """fp16 rows (the heads' default operand type) at B 2, T 15, C 16: two column groups.  Forward: the bound of the other dtypes
+    (the float64 mean of the stored values).  Backward: one rounding of the exact quotient, 2^-11 relative, or half a subnormal
+    step (2^-25) below fp16's normal range; gated-off elements exactly 0."""
+    from uniception_amd import ops
+    B, T, C = 2, 15, 16
+    x = _rows(B, T, C, 24, torch.float16, 131, gpu)
+    assert rel_l2(ops.token_pool(x, B, T).cpu(), x.double().view(B, T, C).mean(1).cpu()) < 1e-6
+    g = torch.randn(B, C, generator=torch.Generator().manual_seed(22)).to(gpu)
+    gate = _rows(B, T, C, 24, torch.float16, 315, gpu, mean=0.0)
+    gate[::3, ::2] = 0.0
+    out = ops.token_pool_bwd(g, T, torch.float16, gate)
+    exact = torch.where(gate > 0, (g.double() / T).view(B, 1, C).expand(B, T, C).reshape(B * T, C), torch.zeros((), dtype=torch.float64, device=gpu))
+    assert out.dtype == torch.float16 and bool((out[~(gate > 0)] == 0).all())
+    assert bool(((out.double() - exact).abs() <= torch.clamp(exact.abs() * 2.0 ** -11, min=2.0 ** -25)).all())
+
+
 def _model(name, gpu):
     kind, kw, _ = CASES[name]
     model = getattr(importlib.import_module(f"uniception_amd.models.prediction_heads.{MODULE_OF[kind]}"), kind)(**kw)

@@ -112,6 +112,14 @@ def test_pixel_unshuffle_is_inverse_of_pixel_shuffle(gpu, P, Cout, h, w):
 
 
 # ------------------------------------------------------------------------------------------
+def test_pixel_unshuffle_bf16_rows(gpu):
+    from uniception_amd import ops
+    B, h, w, P, Cout = 2, 3, 5, 2, 16
+    gimg = torch.randn(B, Cout, P * h, P * w, generator=torch.Generator().manual_seed(2))
+    ref = F.pixel_unshuffle(gimg, P).permute(0, 2, 3, 1).reshape(B * h * w, Cout * P * P)       # columns c*P*P + u*P + v
+    assert torch.equal(ops.pixel_unshuffle(gimg.to(gpu), P, torch.bfloat16).cpu(), ref.bfloat16())
+
+
 def _adaptor_loss_ref(x, gt, alpha):
     """x [B,4,H,W]; the adaptor of adaptors.py:337-342,1080-1083 followed by the confidence-weighted regression loss."""
     xyz = x[:, :3].permute(0, 2, 3, 1)
@@ -346,6 +354,15 @@ def test_dilate_nhwc(gpu):
     src = torch.randn(2, 3, 4, 8, generator=g)
     out = ops.dilate_nhwc(src.to(gpu), 5, 7, 2).cpu()
     ref = torch.zeros(2, 5, 7, 8)
+    ref[:, ::2, ::2] = src
+    assert torch.equal(out, ref)
+
+
+def test_dilate_nhwc_bf16(gpu):
+    from uniception_amd import ops
+    src = torch.randn(2, 3, 5, 16, generator=torch.Generator().manual_seed(1)).bfloat16()
+    out = ops.dilate_nhwc(src.to(gpu), 6, 10, 2).cpu()
+    ref = torch.zeros(2, 6, 10, 16, dtype=torch.bfloat16)
     ref[:, ::2, ::2] = src
     assert torch.equal(out, ref)
 

@@ -2,39 +2,7 @@
 // inverse pixel scatter of ConvTranspose2d(k=s), the transposed im2col that feeds the 3x3 weight-gradient GEMM, the
 // zero-stuffing that turns a stride-2 conv's data gradient into a stride-1 one, and the backward of the 4-channel head conv.
 // All NHWC; 8 channels (16 B bf16) per lane where the channel axis is contiguous.
-#include "common.h"
-
-struct V8b { float v[8]; };
-template <typename Tag> __device__ __forceinline__ V8b ld8(const typename Tag::storage* p);
-template <> __device__ __forceinline__ V8b ld8<F32Tag>(const float* p) {
-    V8b r;
-    const float4_t a = *reinterpret_cast<const float4_t*>(p);
-    const float4_t b = *reinterpret_cast<const float4_t*>(p + 4);
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w; r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-template <> __device__ __forceinline__ V8b ld8<BF16Tag>(const bf16_t* p) {
-    V8b r;
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    r.v[0] = __uint_as_float(u.x << 16); r.v[1] = __uint_as_float(u.x & 0xffff0000u);
-    r.v[2] = __uint_as_float(u.y << 16); r.v[3] = __uint_as_float(u.y & 0xffff0000u);
-    r.v[4] = __uint_as_float(u.z << 16); r.v[5] = __uint_as_float(u.z & 0xffff0000u);
-    r.v[6] = __uint_as_float(u.w << 16); r.v[7] = __uint_as_float(u.w & 0xffff0000u);
-    return r;
-}
-template <typename Tag> __device__ __forceinline__ void st8(typename Tag::storage* p, const V8b& r);
-template <> __device__ __forceinline__ void st8<F32Tag>(float* p, const V8b& r) {
-    *reinterpret_cast<float4_t*>(p) = (float4_t){r.v[0], r.v[1], r.v[2], r.v[3]};
-    *reinterpret_cast<float4_t*>(p + 4) = (float4_t){r.v[4], r.v[5], r.v[6], r.v[7]};
-}
-template <> __device__ __forceinline__ void st8<BF16Tag>(bf16_t* p, const V8b& r) {
-    uint4 u;
-    u.x = pack_bf16x2(r.v[0], r.v[1]); u.y = pack_bf16x2(r.v[2], r.v[3]);
-    u.z = pack_bf16x2(r.v[4], r.v[5]); u.w = pack_bf16x2(r.v[6], r.v[7]);
-    *reinterpret_cast<uint4*>(p) = u;
-}
-
-#define DB_GRID(n_items) ((unsigned)min((int64_t)65536 * 4, ceil_div64((n_items), 256)))
+#include "vec_access.h"
 
 // =================================================================================================================
 // bilinear backward (exact adjoint of bilinear_kernel in elementwise.hip, including its index clamps): gather form, one
@@ -59,7 +27,7 @@ __global__ void bilinear_bwd_kernel(const typename Tag::storage* __restrict__ dy
         int ylo, yhi, xlo, xhi;
         tap_range(yi, sy, ch, ylo, yhi);
         tap_range(xi, sx, cw, xlo, xhi);
-        V8b acc;
+        Vec8 acc;
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc.v[e] = 0.f;
         const typename Tag::storage* base = dy + (int64_t)b * ch * cw * C + c8 * 8;
@@ -75,13 +43,13 @@ __global__ void bilinear_bwd_kernel(const typename Tag::storage* __restrict__ dy
                 const float lx = fx - (float)x0;
                 const float wx = (x0 == xi ? 1.f - lx : 0.f) + (x1 == xi ? lx : 0.f);
                 if (wx == 0.f) continue;
-                const V8b g = ld8<Tag>(base + ((int64_t)oy * cw + ox) * C);
+                const Vec8 g = vec_load8<Tag>(base + ((int64_t)oy * cw + ox) * C);
                 const float w = wy * wx;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc.v[e] = fmaf(w, g.v[e], acc.v[e]);
             }
         }
-        st8<Tag>(dx + it * 8, acc);
+        vec_store8<Tag>(dx + it * 8, acc);
     }
 }
 
@@ -94,11 +62,8 @@ extern "C" int uc_bilinear_nhwc_bwd(const void* dy, void* dx, int dtype, int B, 
     const float sx = Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f;
     const int64_t items = (int64_t)B * Hi * Wi * (C / 8);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_F32)
-        hipLaunchKernelGGL((bilinear_bwd_kernel<F32Tag>), dim3(DB_GRID(items)), dim3(256), 0, st, (const float*)dy, (float*)dx, B, Hi, Wi, C, crop_h, crop_w, sy, sx, items);
-    else if (dtype == UC_BF16)
-        hipLaunchKernelGGL((bilinear_bwd_kernel<BF16Tag>), dim3(DB_GRID(items)), dim3(256), 0, st, (const bf16_t*)dy, (bf16_t*)dx, B, Hi, Wi, C, crop_h, crop_w, sy, sx, items);
-    else { uc_set_error("uc_bilinear_nhwc_bwd: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH("uc_bilinear_nhwc_bwd", dtype,
+                hipLaunchKernelGGL((bilinear_bwd_kernel<Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, (const Tag::storage*)dy, (Tag::storage*)dx, B, Hi, Wi, C, crop_h, crop_w, sy, sx, items));
     UC_CHECK_LAUNCH("uc_bilinear_nhwc_bwd");
     return UC_OK;
 }
@@ -118,7 +83,7 @@ __global__ void convt_gather_kernel(const typename Tag::storage* __restrict__ sr
         const int b = (int)(r / (k * h));
         const int i = Y / k, u = Y % k, j = X / k, v = X % k;
         const int64_t drow = ((int64_t)b * h + i) * w + j;
-        st8<Tag>(dst + drow * ((int64_t)k * k * Cout) + (int64_t)(u * k + v) * Cout + c8 * 8, ld8<Tag>(src + it * 8));
+        vec_store8<Tag>(dst + drow * ((int64_t)k * k * Cout) + (int64_t)(u * k + v) * Cout + c8 * 8, vec_load8<Tag>(src + it * 8));
     }
 }
 
@@ -126,9 +91,8 @@ extern "C" int uc_convt_gather(const void* src, void* dst, int dtype, int B, int
     UC_REQUIRE(src && dst && B > 0 && h > 0 && w > 0 && k > 0 && Cout > 0 && Cout % 8 == 0, "uc_convt_gather: bad argument (Cout must be a multiple of 8)");
     const int64_t items = (int64_t)B * h * k * w * k * (Cout / 8);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_F32) hipLaunchKernelGGL((convt_gather_kernel<F32Tag>), dim3(DB_GRID(items)), dim3(256), 0, st, (const float*)src, (float*)dst, B, h, w, k, Cout, items);
-    else if (dtype == UC_BF16) hipLaunchKernelGGL((convt_gather_kernel<BF16Tag>), dim3(DB_GRID(items)), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, B, h, w, k, Cout, items);
-    else { uc_set_error("uc_convt_gather: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH("uc_convt_gather", dtype,
+                hipLaunchKernelGGL((convt_gather_kernel<Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, (const Tag::storage*)src, (Tag::storage*)dst, B, h, w, k, Cout, items));
     UC_CHECK_LAUNCH("uc_convt_gather");
     return UC_OK;
 }
@@ -181,9 +145,8 @@ extern "C" int uc_im2col_t(const void* x, void* dst, int dtype, int B, int H, in
     UC_REQUIRE(ld >= npix && ld < npix + 64, "uc_im2col_t: ld must be in [npix, npix+64)");
     dim3 grid((unsigned)ceil_div64(ld, 64), (unsigned)((Cin + 63) / 64), 9);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_F32) hipLaunchKernelGGL((im2col_t_kernel<F32Tag>), grid, dim3(256), 0, st, (const float*)x, (float*)dst, B, H, W, Cin, stride, Ho, Wo, relu, npix, ld);
-    else if (dtype == UC_BF16) hipLaunchKernelGGL((im2col_t_kernel<BF16Tag>), grid, dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)dst, B, H, W, Cin, stride, Ho, Wo, relu, npix, ld);
-    else { uc_set_error("uc_im2col_t: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH("uc_im2col_t", dtype,
+                hipLaunchKernelGGL((im2col_t_kernel<Tag>), grid, dim3(256), 0, st, (const Tag::storage*)x, (Tag::storage*)dst, B, H, W, Cin, stride, Ho, Wo, relu, npix, ld));
     UC_CHECK_LAUNCH("uc_im2col_t");
     return UC_OK;
 }
@@ -201,12 +164,12 @@ __global__ void dilate_kernel(const typename Tag::storage* __restrict__ src, typ
         const int X = (int)(r % W); r /= W;
         const int Y = (int)(r % H);
         const int b = (int)(r / H);
-        V8b v;
+        Vec8 v;
 #pragma unroll
         for (int e = 0; e < 8; ++e) v.v[e] = 0.f;
         if (Y % s == 0 && X % s == 0 && Y / s < h && X / s < w)
-            v = ld8<Tag>(src + ((((int64_t)b * h + Y / s) * w + X / s) * C) + c8 * 8);
-        st8<Tag>(dst + it * 8, v);
+            v = vec_load8<Tag>(src + ((((int64_t)b * h + Y / s) * w + X / s) * C) + c8 * 8);
+        vec_store8<Tag>(dst + it * 8, v);
     }
 }
 
@@ -216,9 +179,8 @@ extern "C" int uc_dilate_nhwc(const void* src, void* dst, int dtype, int B, int 
     UC_REQUIRE((h - 1) * stride < H && (w - 1) * stride < W, "uc_dilate_nhwc: source does not fit the dilated grid");
     const int64_t items = (int64_t)B * H * W * (C / 8);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_F32) hipLaunchKernelGGL((dilate_kernel<F32Tag>), dim3(DB_GRID(items)), dim3(256), 0, st, (const float*)src, (float*)dst, B, h, w, H, W, C, stride, items);
-    else if (dtype == UC_BF16) hipLaunchKernelGGL((dilate_kernel<BF16Tag>), dim3(DB_GRID(items)), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, B, h, w, H, W, C, stride, items);
-    else { uc_set_error("uc_dilate_nhwc: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH("uc_dilate_nhwc", dtype,
+                hipLaunchKernelGGL((dilate_kernel<Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, (const Tag::storage*)src, (Tag::storage*)dst, B, h, w, H, W, C, stride, items));
     UC_CHECK_LAUNCH("uc_dilate_nhwc");
     return UC_OK;
 }
@@ -249,15 +211,15 @@ __global__ __launch_bounds__(256) void conv1x1_to4_bwd_kernel(const typename Tag
         for (int64_t p = (int64_t)blockIdx.x * lanes + pl; p < npix; p += (int64_t)gridDim.x * lanes) {
             const float4_t g = *reinterpret_cast<const float4_t*>(dout + p * 4);
             const float gv[4] = {g.x, g.y, g.z, g.w};
-            const V8b f = ld8<Tag>(feat + p * Cin + chunk * 8);
-            V8b d;
+            const Vec8 f = vec_load8<Tag>(feat + p * Cin + chunk * 8);
+            Vec8 d;
 #pragma unroll
             for (int e = 0; e < 8; ++e) d.v[e] = gv[0] * wr[0][e] + gv[1] * wr[1][e] + gv[2] * wr[2][e] + gv[3] * wr[3][e];
             if (relu_mask) {      // feat is the OUTPUT of a ReLU: its backward rides here (the stand-alone mask pass re-read both maps)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) d.v[e] = f.v[e] > 0.f ? d.v[e] : 0.f;
             }
-            st8<Tag>(dfeat + p * Cin + chunk * 8, d);
+            vec_store8<Tag>(dfeat + p * Cin + chunk * 8, d);
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
 #pragma unroll
@@ -300,9 +262,8 @@ extern "C" int uc_conv1x1_to4_bwd(const void* feat, int dtype, const float* w, c
     const int lanes = 256 / (Cin / 8);
     const unsigned grid = (unsigned)min((int64_t)2048, ceil_div64(npix, lanes));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_F32) hipLaunchKernelGGL((conv1x1_to4_bwd_kernel<F32Tag>), dim3(grid), dim3(256), 0, st, (const float*)feat, w, dout, (float*)dfeat, dw, db, npix, Cin, relu_mask);
-    else if (dtype == UC_BF16) hipLaunchKernelGGL((conv1x1_to4_bwd_kernel<BF16Tag>), dim3(grid), dim3(256), 0, st, (const bf16_t*)feat, w, dout, (bf16_t*)dfeat, dw, db, npix, Cin, relu_mask);
-    else { uc_set_error("uc_conv1x1_to4_bwd: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH("uc_conv1x1_to4_bwd", dtype,
+                hipLaunchKernelGGL((conv1x1_to4_bwd_kernel<Tag>), dim3(grid), dim3(256), 0, st, (const Tag::storage*)feat, w, dout, (Tag::storage*)dfeat, dw, db, npix, Cin, relu_mask));
     UC_CHECK_LAUNCH("uc_conv1x1_to4_bwd");
     return UC_OK;
 }

@@ -3,75 +3,9 @@
 // behind ConvTranspose2d(k=s) / pixel_shuffle, the pointmap+confidence adaptor and the 1x1 head conv.
 // All are single-pass streaming kernels; channel-last (NHWC) tensors are moved 8 elements per lane
 // (16 B bf16 / 2x16 B fp32).
-#include "common.h"
+#include "vec_access.h"
 #include <type_traits>
 #include "knobs.h"
-
-// ---- generic 8-element vector load/store with fp32 math in between --------------------------
-struct V8 { float v[8]; };
-
-template <typename Tag>
-__device__ __forceinline__ V8 load8(const typename Tag::storage* p);
-template <>
-__device__ __forceinline__ V8 load8<F32Tag>(const float* p) {
-    V8 r;
-    const float4_t a = *reinterpret_cast<const float4_t*>(p);
-    const float4_t b = *reinterpret_cast<const float4_t*>(p + 4);
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-template <>
-__device__ __forceinline__ V8 load8<BF16Tag>(const bf16_t* p) {
-    V8 r;
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    r.v[0] = __uint_as_float(u.x << 16); r.v[1] = __uint_as_float(u.x & 0xffff0000u);
-    r.v[2] = __uint_as_float(u.y << 16); r.v[3] = __uint_as_float(u.y & 0xffff0000u);
-    r.v[4] = __uint_as_float(u.z << 16); r.v[5] = __uint_as_float(u.z & 0xffff0000u);
-    r.v[6] = __uint_as_float(u.w << 16); r.v[7] = __uint_as_float(u.w & 0xffff0000u);
-    return r;
-}
-typedef _Float16 uc_half2_t __attribute__((ext_vector_type(2)));
-typedef float uc_float2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_f16x2(float lo, float hi) {       // round-to-nearest-even, like torch's Half
-    const uc_float2_t v = {uc_sat_f16(lo), uc_sat_f16(hi)};          // (saturating: see common.h)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, uc_half2_t));
-}
-__device__ __forceinline__ void unpack_f16x2(unsigned u, float& lo, float& hi) {
-    const uc_float2_t v = __builtin_convertvector(__builtin_bit_cast(uc_half2_t, u), uc_float2_t);
-    lo = v.x; hi = v.y;
-}
-template <>
-__device__ __forceinline__ V8 load8<F16Tag>(const unsigned short* p) {
-    V8 r;
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    unpack_f16x2(u.x, r.v[0], r.v[1]); unpack_f16x2(u.y, r.v[2], r.v[3]);
-    unpack_f16x2(u.z, r.v[4], r.v[5]); unpack_f16x2(u.w, r.v[6], r.v[7]);
-    return r;
-}
-template <typename Tag>
-__device__ __forceinline__ void store8(typename Tag::storage* p, const V8& r);
-template <>
-__device__ __forceinline__ void store8<F16Tag>(unsigned short* p, const V8& r) {
-    uint4 u;
-    u.x = pack_f16x2(r.v[0], r.v[1]); u.y = pack_f16x2(r.v[2], r.v[3]);
-    u.z = pack_f16x2(r.v[4], r.v[5]); u.w = pack_f16x2(r.v[6], r.v[7]);
-    *reinterpret_cast<uint4*>(p) = u;
-}
-template <>
-__device__ __forceinline__ void store8<F32Tag>(float* p, const V8& r) {
-    *reinterpret_cast<float4_t*>(p) = (float4_t){r.v[0], r.v[1], r.v[2], r.v[3]};
-    *reinterpret_cast<float4_t*>(p + 4) = (float4_t){r.v[4], r.v[5], r.v[6], r.v[7]};
-}
-template <>
-__device__ __forceinline__ void store8<BF16Tag>(bf16_t* p, const V8& r) {
-    uint4 u;
-    u.x = pack_bf16x2(r.v[0], r.v[1]); u.y = pack_bf16x2(r.v[2], r.v[3]);
-    u.z = pack_bf16x2(r.v[4], r.v[5]); u.w = pack_bf16x2(r.v[6], r.v[7]);
-    *reinterpret_cast<uint4*>(p) = u;
-}
-
-#define EW_GRID(n_items) ((unsigned)min((int64_t)65536 * 4, ceil_div64((n_items), 256)))
 
 // =======================================================================================
 // patch gather: img fp32 NCHW -> cols [B*h*w, Cin*P*P], columns (c,u,v).  One work item = 4 pixels of a patch row.
@@ -118,23 +52,18 @@ extern "C" int uc_patch_gather(const float* img, void* cols, int out_dtype, int 
                                uc_stream_t stream) {
     UC_REQUIRE(img && cols, "uc_patch_gather: null pointer");
     UC_REQUIRE(B > 0 && Cin > 0 && P > 0 && H % P == 0 && W % P == 0, "uc_patch_gather: H,W must be multiples of the patch size");
-    UC_REQUIRE(out_dtype == UC_F32 || out_dtype == UC_BF16, "uc_patch_gather: bad out_dtype %d", out_dtype);
     hipStream_t st = (hipStream_t)stream;
     const bool quad = (P % 4 == 0) && (W % 4 == 0) && ((uintptr_t)img % 16 == 0);   // 16-byte pixel quads
     if (!quad) {
         const int64_t n = (int64_t)B * Cin * H * W;
-        if (out_dtype == UC_F32)
-            hipLaunchKernelGGL((patch_gather_scalar_kernel<F32Tag>), dim3(EW_GRID(n)), dim3(256), 0, st, img, (float*)cols, B, Cin, H, W, P, n);
-        else
-            hipLaunchKernelGGL((patch_gather_scalar_kernel<BF16Tag>), dim3(EW_GRID(n)), dim3(256), 0, st, img, (bf16_t*)cols, B, Cin, H, W, P, n);
+        UC_DISPATCH("uc_patch_gather", out_dtype,
+                    hipLaunchKernelGGL((patch_gather_scalar_kernel<Tag>), dim3(EW_GRID(n)), dim3(256), 0, st, img, (Tag::storage*)cols, B, Cin, H, W, P, n));
         UC_CHECK_LAUNCH("uc_patch_gather");
         return UC_OK;
     }
     const int64_t items = (int64_t)B * Cin * H * W / 4;
-    if (out_dtype == UC_F32)
-        hipLaunchKernelGGL((patch_gather_kernel<F32Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, img, (float*)cols, B, Cin, H, W, P, items);
-    else
-        hipLaunchKernelGGL((patch_gather_kernel<BF16Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, img, (bf16_t*)cols, B, Cin, H, W, P, items);
+    UC_DISPATCH("uc_patch_gather", out_dtype,
+                hipLaunchKernelGGL((patch_gather_kernel<Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, img, (Tag::storage*)cols, B, Cin, H, W, P, items));
     UC_CHECK_LAUNCH("uc_patch_gather");
     return UC_OK;
 }
@@ -346,15 +275,15 @@ __global__ void bilinear_kernel(const typename Tag::storage* __restrict__ src, t
     const float ly = fy - (float)y0, lx = fx - (float)x0;
     const float hy = 1.f - ly, hx = 1.f - lx;
     const typename Tag::storage* base = src + (int64_t)b * Hi * Wi * C + c8 * 8;
-    const V8 p00 = load8<Tag>(base + ((int64_t)y0 * Wi + x0) * C);
-    const V8 p01 = load8<Tag>(base + ((int64_t)y0 * Wi + x1) * C);
-    const V8 p10 = load8<Tag>(base + ((int64_t)y1 * Wi + x0) * C);
-    const V8 p11 = load8<Tag>(base + ((int64_t)y1 * Wi + x1) * C);
-    V8 o;
+    const Vec8 p00 = vec_load8<Tag>(base + ((int64_t)y0 * Wi + x0) * C);
+    const Vec8 p01 = vec_load8<Tag>(base + ((int64_t)y0 * Wi + x1) * C);
+    const Vec8 p10 = vec_load8<Tag>(base + ((int64_t)y1 * Wi + x0) * C);
+    const Vec8 p11 = vec_load8<Tag>(base + ((int64_t)y1 * Wi + x1) * C);
+    Vec8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e)
         o.v[e] = hy * (hx * p00.v[e] + lx * p01.v[e]) + ly * (hx * p10.v[e] + lx * p11.v[e]);
-    store8<Tag>(dst + (((int64_t)b * ch + oy) * cw) * C + (int64_t)t * 8, o);
+    vec_store8<Tag>(dst + (((int64_t)b * ch + oy) * cw) * C + (int64_t)t * 8, o);
 }
 
 // R output rows per work item (upsampling: vertical scale <= 1/2, so rows oy .. oy + R - 1 read at most the R/2 + 2 input rows
@@ -379,7 +308,7 @@ __global__ void bilinear_rows_kernel(const typename Tag::storage* __restrict__ s
 #pragma unroll
     for (int i = 0; i < RIN; ++i) {
         const int64_t y = min(ya + i, Hi - 1);
-        const V8 p0 = load8<Tag>(base + (y * Wi + x0) * C), p1 = load8<Tag>(base + (y * Wi + x1) * C);
+        const Vec8 p0 = vec_load8<Tag>(base + (y * Wi + x0) * C), p1 = vec_load8<Tag>(base + (y * Wi + x1) * C);
 #pragma unroll
         for (int e = 0; e < 8; ++e) h[i][e] = hx * p0.v[e] + lx * p1.v[e];
     }
@@ -390,7 +319,7 @@ __global__ void bilinear_rows_kernel(const typename Tag::storage* __restrict__ s
         const int y0 = (int)fy;
         const float ly = fy - (float)y0, hy = 1.f - ly;
         const int rel = y0 - ya;                   // 0 .. RIN - 2
-        V8 o;
+        Vec8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float top = h[0][e], bot = h[1][e];
@@ -398,7 +327,7 @@ __global__ void bilinear_rows_kernel(const typename Tag::storage* __restrict__ s
             for (int i = 1; i < RIN - 1; ++i) { top = rel == i ? h[i][e] : top; bot = rel == i ? h[i + 1][e] : bot; }
             o.v[e] = hy * top + ly * bot;
         }
-        store8<Tag>(dst + (((int64_t)b * ch + oy + k) * cw) * C + (int64_t)t * 8, o);
+        vec_store8<Tag>(dst + (((int64_t)b * ch + oy + k) * cw) * C + (int64_t)t * 8, o);
     }
 }
 
@@ -415,27 +344,20 @@ extern "C" int uc_bilinear_nhwc(const void* src, void* dst, int dtype, int B, in
     const int rows2 = uc_knobs().bilinear_rows2;   // rows per work item of the upsampling form: 4 (default), 2, 0 = one-row kernel
     // (bf16 only: the fp32 kernels are the verification path — its gradient fixtures sit on ReLU boundaries of the tiny test models,
     // where a 1e-7 change of the forward's rounding flips a mask and moves a small gradient tensor by 1e-3)
-    if (rows2 && dtype == UC_F16 && sy <= 0.5f) {
-        const dim3 gr(grid.x, (unsigned)((crop_h + 3) / 4), (unsigned)B);
-        hipLaunchKernelGGL((bilinear_rows_kernel<F16Tag, 4>), gr, dim3(256), 0, st, (const unsigned short*)src, (unsigned short*)dst, B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx);
+    // Instantiated for (bf16, 4 or 2 rows) and (fp16, 4 rows): these (dtype, rows) pairs are the specification, not a dtype dispatch.
+    if (rows2 && sy <= 0.5f && (dtype == UC_BF16 || dtype == UC_F16)) {
+#define UC_BL_ROWS(TAG, R)                                                                                                           \
+    hipLaunchKernelGGL((bilinear_rows_kernel<TAG, R>), dim3(grid.x, (unsigned)((crop_h + R - 1) / R), (unsigned)B), dim3(256), 0, st, \
+                       (const TAG::storage*)src, (TAG::storage*)dst, B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx)
+        if (dtype == UC_F16) UC_BL_ROWS(F16Tag, 4);
+        else if (rows2 == 4) UC_BL_ROWS(BF16Tag, 4);
+        else UC_BL_ROWS(BF16Tag, 2);
+#undef UC_BL_ROWS
         UC_CHECK_LAUNCH("uc_bilinear_nhwc");
         return UC_OK;
     }
-    if (rows2 && dtype == UC_BF16 && sy <= 0.5f) {
-        const int R = rows2 == 4 ? 4 : 2;
-        const dim3 gr(grid.x, (unsigned)((crop_h + R - 1) / R), (unsigned)B);
-        if (R == 4) hipLaunchKernelGGL((bilinear_rows_kernel<BF16Tag, 4>), gr, dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx);
-        else hipLaunchKernelGGL((bilinear_rows_kernel<BF16Tag, 2>), gr, dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx);
-        UC_CHECK_LAUNCH("uc_bilinear_nhwc");
-        return UC_OK;
-    }
-    if (dtype == UC_F32)
-        hipLaunchKernelGGL((bilinear_kernel<F32Tag>), grid, dim3(256), 0, st, (const float*)src, (float*)dst, B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx);
-    else if (dtype == UC_BF16)
-        hipLaunchKernelGGL((bilinear_kernel<BF16Tag>), grid, dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx);
-    else if (dtype == UC_F16)
-        hipLaunchKernelGGL((bilinear_kernel<F16Tag>), grid, dim3(256), 0, st, (const unsigned short*)src, (unsigned short*)dst, B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx);
-    else { uc_set_error("uc_bilinear_nhwc: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH_F16("uc_bilinear_nhwc", dtype,
+                    hipLaunchKernelGGL((bilinear_kernel<Tag>), grid, dim3(256), 0, st, (const Tag::storage*)src, (Tag::storage*)dst, B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx));
     UC_CHECK_LAUNCH("uc_bilinear_nhwc");
     return UC_OK;
 }
@@ -456,8 +378,8 @@ __global__ void convt_scatter_kernel(const typename Tag::storage* __restrict__ s
         const int b = (int)(r / (k * h));
         const int i = Y / k, u = Y % k, j = X / k, v = X % k;
         const int64_t srow = ((int64_t)b * h + i) * w + j;
-        const V8 x = load8<Tag>(src + srow * ((int64_t)k * k * Cout) + (int64_t)(u * k + v) * Cout + c8 * 8);
-        store8<Tag>(dst + it * 8, x);
+        const Vec8 x = vec_load8<Tag>(src + srow * ((int64_t)k * k * Cout) + (int64_t)(u * k + v) * Cout + c8 * 8);
+        vec_store8<Tag>(dst + it * 8, x);
     }
 }
 
@@ -467,13 +389,8 @@ extern "C" int uc_convt_scatter(const void* src, void* dst, int dtype, int B, in
     UC_REQUIRE(B > 0 && h > 0 && w > 0 && k > 0 && Cout > 0 && Cout % 8 == 0, "uc_convt_scatter: bad shape (Cout must be a multiple of 8)");
     const int64_t items = (int64_t)B * h * w * k * k * (Cout / 8);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_F32)
-        hipLaunchKernelGGL((convt_scatter_kernel<F32Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, (const float*)src, (float*)dst, B, h, w, k, Cout, items);
-    else if (dtype == UC_BF16)
-        hipLaunchKernelGGL((convt_scatter_kernel<BF16Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, B, h, w, k, Cout, items);
-    else if (dtype == UC_F16)
-        hipLaunchKernelGGL((convt_scatter_kernel<F16Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, (const unsigned short*)src, (unsigned short*)dst, B, h, w, k, Cout, items);
-    else { uc_set_error("uc_convt_scatter: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH_F16("uc_convt_scatter", dtype,
+                    hipLaunchKernelGGL((convt_scatter_kernel<Tag>), dim3(EW_GRID(items)), dim3(256), 0, st, (const Tag::storage*)src, (Tag::storage*)dst, B, h, w, k, Cout, items));
     UC_CHECK_LAUNCH("uc_convt_scatter");
     return UC_OK;
 }
@@ -502,13 +419,8 @@ extern "C" int uc_pixel_shuffle(const void* src, int src_dtype, float* dst, int 
     UC_REQUIRE(src && dst && B > 0 && h > 0 && w > 0 && P > 0 && Cout > 0, "uc_pixel_shuffle: bad argument");
     const int64_t n = (int64_t)B * Cout * P * h * P * w;
     hipStream_t st = (hipStream_t)stream;
-    if (src_dtype == UC_F32)
-        hipLaunchKernelGGL((pixel_shuffle_kernel<F32Tag>), dim3(EW_GRID(n)), dim3(256), 0, st, (const float*)src, dst, B, h, w, P, Cout, n);
-    else if (src_dtype == UC_BF16)
-        hipLaunchKernelGGL((pixel_shuffle_kernel<BF16Tag>), dim3(EW_GRID(n)), dim3(256), 0, st, (const bf16_t*)src, dst, B, h, w, P, Cout, n);
-    else if (src_dtype == UC_F16)
-        hipLaunchKernelGGL((pixel_shuffle_kernel<F16Tag>), dim3(EW_GRID(n)), dim3(256), 0, st, (const unsigned short*)src, dst, B, h, w, P, Cout, n);
-    else { uc_set_error("uc_pixel_shuffle: bad dtype %d", src_dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH_F16("uc_pixel_shuffle", src_dtype,
+                    hipLaunchKernelGGL((pixel_shuffle_kernel<Tag>), dim3(EW_GRID(n)), dim3(256), 0, st, (const Tag::storage*)src, dst, B, h, w, P, Cout, n));
     UC_CHECK_LAUNCH("uc_pixel_shuffle");
     return UC_OK;
 }
@@ -557,7 +469,7 @@ __global__ __launch_bounds__(256) void conv1x1_to4_kernel(const typename Tag::st
         float a0 = bias[0], a1 = bias[1], a2 = bias[2], a3 = bias[3];
         const typename Tag::storage* f = feat + pix * Cin;
         for (int c = 0; c < Cin; c += 8) {
-            const V8 x = load8<Tag>(f + c);
+            const Vec8 x = vec_load8<Tag>(f + c);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 a0 = fmaf(x.v[e], ws[0][c + e], a0);
@@ -587,7 +499,7 @@ __global__ __launch_bounds__(256) void conv1x1_to4_coop_kernel(const typename Ta
         for (int e = 0; e < 8; ++e) wr[o][e] = w[o * Cin + chunk * 8 + e];
     const float4_t b4 = *reinterpret_cast<const float4_t*>(bias);
     for (int64_t pix = (int64_t)blockIdx.x * PPB + pl; pix < npix; pix += (int64_t)gridDim.x * PPB) {
-        const V8 x = load8<Tag>(feat + pix * Cin + chunk * 8);
+        const Vec8 x = vec_load8<Tag>(feat + pix * Cin + chunk * 8);
         float a[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -628,19 +540,11 @@ extern "C" int uc_conv1x1_to4(const void* feat, int dtype, const float* w, const
     UC_REQUIRE(feat && w && b && out && npix > 0, "uc_conv1x1_to4: bad argument");
     UC_REQUIRE(Cin > 0 && Cin <= 256 && Cin % 8 == 0, "uc_conv1x1_to4: Cin must be a multiple of 8 and <= 256 (got %d)", Cin);
     hipStream_t st = (hipStream_t)stream;
-    if (((uintptr_t)b % 16 == 0) && ((dtype == UC_F32 && launch_conv1x1_to4_coop<F32Tag>(feat, w, b, out, npix, Cin, st)) ||
-                                      (dtype == UC_BF16 && launch_conv1x1_to4_coop<BF16Tag>(feat, w, b, out, npix, Cin, st)) ||
-                                      (dtype == UC_F16 && launch_conv1x1_to4_coop<F16Tag>(feat, w, b, out, npix, Cin, st)))) {
-        UC_CHECK_LAUNCH("uc_conv1x1_to4");
-        return UC_OK;
-    }
-    if (dtype == UC_F32)
-        hipLaunchKernelGGL((conv1x1_to4_kernel<F32Tag>), dim3(EW_GRID(npix)), dim3(256), 0, st, (const float*)feat, w, b, out, npix, Cin);
-    else if (dtype == UC_BF16)
-        hipLaunchKernelGGL((conv1x1_to4_kernel<BF16Tag>), dim3(EW_GRID(npix)), dim3(256), 0, st, (const bf16_t*)feat, w, b, out, npix, Cin);
-    else if (dtype == UC_F16)
-        hipLaunchKernelGGL((conv1x1_to4_kernel<F16Tag>), dim3(EW_GRID(npix)), dim3(256), 0, st, (const unsigned short*)feat, w, b, out, npix, Cin);
-    else { uc_set_error("uc_conv1x1_to4: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    bool coop = false;          // the coalesced form: a 16-byte aligned bias and Cin = 8 * 2^k
+    if ((uintptr_t)b % 16 == 0) UC_DISPATCH_F16("uc_conv1x1_to4", dtype, coop = launch_conv1x1_to4_coop<Tag>(feat, w, b, out, npix, Cin, st));
+    if (!coop)
+        UC_DISPATCH_F16("uc_conv1x1_to4", dtype,
+                        hipLaunchKernelGGL((conv1x1_to4_kernel<Tag>), dim3(EW_GRID(npix)), dim3(256), 0, st, (const Tag::storage*)feat, w, b, out, npix, Cin));
     UC_CHECK_LAUNCH("uc_conv1x1_to4");
     return UC_OK;
 }

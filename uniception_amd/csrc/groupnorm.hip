@@ -1,7 +1,7 @@
 // GroupNorm on channels-last maps (the ResidualConvBlocks of the MoGe head: nn.GroupNorm + ReLU in front of every 3x3 convolution)
 // and its backward.  x [B, H, W, C], G groups of C / G contiguous channels, (C / G) % 8 == 0.
 //
-// Work item = 8 consecutive channels of one pixel (nhwc_vec.h).  A workgroup of 256 threads is laid out as `rows` pixels x C / 8
+// Work item = 8 consecutive channels of one pixel (vec_access.h).  A workgroup of 256 threads is laid out as `rows` pixels x C / 8
 // channel vectors (rows = 256 / (C / 8)), so consecutive lanes read consecutive 16-byte pieces: a wave load covers whole pixel rows.
 // One workgroup takes one CHUNK of rows * GN_VECS pixels of one sample — B x G alone would be a handful of workgroups.
 //
@@ -14,7 +14,7 @@
 //     kernel adds the chunks in a fixed order (four interleaved chains, combined in chain order) and forms the two group sums
 //     sum g gamma and sum g gamma x^ from the per-channel sums (they are gamma-weighted sums of those); a third adds the samples for
 //     dgamma / dbeta; the fourth writes dx.  Fixed order everywhere: two calls give the same bits.
-#include "nhwc_vec.h"
+#include "vec_access.h"
 
 #define GN_THREADS 256
 #define GN_VECS 8            // 8-channel vectors per thread and chunk (64 values in registers)
@@ -70,13 +70,13 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_partial_kernel(const type
     const int p0 = chunk * gm.chunk_pix;
     const int npix = min(gm.chunk_pix, gm.HW - p0);
     const typename Tag::storage* base = x + ((b * gm.HW + p0) * (int64_t)gm.C) + c8 * 8;
-    NV8 v[GN_VECS];
+    Vec8 v[GN_VECS];
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < GN_VECS; ++j) {
         const int p = j * rows + r;
         if (active && p < npix) {
-            v[j] = nv_ld8<Tag>(base + (int64_t)p * gm.C);
+            v[j] = vec_load8<Tag>(base + (int64_t)p * gm.C);
 #pragma unroll
             for (int e = 0; e < 8; ++e) s += v[j].v[e];
         } else {
@@ -157,15 +157,15 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const typename Tag::stora
     const int c8 = (int)((it - b * per_sample) % gm.C8);
     const int sg = (int)b * gm.G + c8 / gm.cg8;
     const float mu = mean[sg], rs = rstd[sg];
-    const NV8 ga = nv_ld8<F32Tag>(gamma + c8 * 8), be = nv_ld8<F32Tag>(beta + c8 * 8);
-    const NV8 v = nv_ld8<Tag>(x + it * 8);
-    NV8 o;
+    const Vec8 ga = vec_load8<F32Tag>(gamma + c8 * 8), be = vec_load8<F32Tag>(beta + c8 * 8);
+    const Vec8 v = vec_load8<Tag>(x + it * 8);
+    Vec8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const float t = fmaf((v.v[e] - mu) * rs, ga.v[e], be.v[e]);
         o.v[e] = RELU ? fmaxf(t, 0.f) : t;
     }
-    nv_st8<Tag>(y + it * 8, o);
+    vec_store8<Tag>(y + it * 8, o);
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------------
@@ -197,10 +197,10 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_partial_kernel(const typena
             const int p = j * rows + r;
             if (p < npix) {
                 const int64_t o = off + (int64_t)p * gm.C;
-                NV8 g = nv_ld8<Tag>(dy + o);
-                const NV8 xv = nv_ld8<Tag>(x + o);
+                Vec8 g = vec_load8<Tag>(dy + o);
+                const Vec8 xv = vec_load8<Tag>(x + o);
                 if (GATE) {
-                    const NV8 yv = nv_ld8<Tag>(gate + o);
+                    const Vec8 yv = vec_load8<Tag>(gate + o);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) g.v[e] = yv.v[e] > 0.f ? g.v[e] : 0.f;
                 }
@@ -290,26 +290,26 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const typename Tag::s
     const int sg = (int)b * gm.G + c8 / gm.cg8;
     const float mu = mean[sg], rs = rstd[sg];
     const float s1 = S[sg * 2] * inv_m, s2 = S[sg * 2 + 1] * inv_m;
-    const NV8 ga = nv_ld8<F32Tag>(gamma + c8 * 8);
-    NV8 g = nv_ld8<Tag>(dy + it * 8);
-    const NV8 xv = nv_ld8<Tag>(x + it * 8);
+    const Vec8 ga = vec_load8<F32Tag>(gamma + c8 * 8);
+    Vec8 g = vec_load8<Tag>(dy + it * 8);
+    const Vec8 xv = vec_load8<Tag>(x + it * 8);
     if (GATE) {
-        const NV8 yv = nv_ld8<Tag>(gate + it * 8);
+        const Vec8 yv = vec_load8<Tag>(gate + it * 8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) g.v[e] = yv.v[e] > 0.f ? g.v[e] : 0.f;
     }
-    NV8 o;
+    Vec8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const float xh = (xv.v[e] - mu) * rs;
         o.v[e] = rs * ((g.v[e] * ga.v[e] - s1) - xh * s2);
     }
-    nv_st8<Tag>(dx + it * 8, o);
+    vec_store8<Tag>(dx + it * 8, o);
 }
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------------
 static int gn_check_shape(const char* fn, int dtype, int B, int H, int W, int C, int G) {
-    UC_REQUIRE(nv_dtype_ok(dtype), "%s: unsupported dtype %d (UC_F32, UC_BF16 or UC_F16)", fn, dtype);
+    UC_REQUIRE_DTYPE(fn, dtype, true);
     UC_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && G > 0, "%s: bad shape B=%d H=%d W=%d C=%d G=%d", fn, B, H, W, C, G);
     UC_REQUIRE(C % G == 0, "%s: C (%d) is not a multiple of G (%d)", fn, C, G);
     UC_REQUIRE((C / G) % 8 == 0, "%s: channels per group (%d) must be a multiple of 8", fn, C / G);
@@ -338,17 +338,17 @@ extern "C" int uc_group_norm_nhwc(const void* x, void* y, const float* gamma, co
     const GnGeom gm = gn_geom(H, W, C, G);
     hipStream_t st = (hipStream_t)stream;
     const dim3 pgrid((unsigned)gm.nchunk, (unsigned)B);
-    NV_DISPATCH(dtype, hipLaunchKernelGGL(gn_stats_partial_kernel<Tag>, pgrid, dim3(GN_THREADS), 0, st, (const T*)x, (float2*)ws, gm));
+    UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL(gn_stats_partial_kernel<Tag>, pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)x, (float2*)ws, gm));
     UC_CHECK_LAUNCH(fn);
     hipLaunchKernelGGL(gn_stats_finalize_kernel, dim3((unsigned)(B * G)), dim3(64), 0, st, (const float2*)ws, mean, rstd, gm, eps);
     UC_CHECK_LAUNCH(fn);
     const int64_t per_sample = (int64_t)gm.HW * gm.C8, items = per_sample * B;
     const dim3 agrid((unsigned)((items + 255) / 256));
     if (relu)
-        NV_DISPATCH(dtype, hipLaunchKernelGGL((gn_apply_kernel<Tag, true>), agrid, dim3(256), 0, st, (const T*)x, (T*)y, gamma, beta,
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_apply_kernel<Tag, true>), agrid, dim3(256), 0, st, (const Tag::storage*)x, (Tag::storage*)y, gamma, beta,
                                               (const float*)mean, (const float*)rstd, items, per_sample, gm));
     else
-        NV_DISPATCH(dtype, hipLaunchKernelGGL((gn_apply_kernel<Tag, false>), agrid, dim3(256), 0, st, (const T*)x, (T*)y, gamma, beta,
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_apply_kernel<Tag, false>), agrid, dim3(256), 0, st, (const Tag::storage*)x, (Tag::storage*)y, gamma, beta,
                                               (const float*)mean, (const float*)rstd, items, per_sample, gm));
     UC_CHECK_LAUNCH(fn);
     return UC_OK;
@@ -377,11 +377,11 @@ extern "C" int uc_group_norm_nhwc_bwd(const void* dy, const void* x, const void*
     float* S = pc + (int64_t)B * 2 * C;
     const dim3 pgrid((unsigned)gm.nchunk, (unsigned)B);
     if (gate)
-        NV_DISPATCH(dtype, hipLaunchKernelGGL((gn_bwd_partial_kernel<Tag, true>), pgrid, dim3(GN_THREADS), 0, st, (const T*)dy, (const T*)x,
-                                              (const T*)gate, mean, rstd, part, gm));
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_partial_kernel<Tag, true>), pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
+                                              (const Tag::storage*)gate, mean, rstd, part, gm));
     else
-        NV_DISPATCH(dtype, hipLaunchKernelGGL((gn_bwd_partial_kernel<Tag, false>), pgrid, dim3(GN_THREADS), 0, st, (const T*)dy, (const T*)x,
-                                              (const T*)nullptr, mean, rstd, part, gm));
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_partial_kernel<Tag, false>), pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
+                                              (const Tag::storage*)nullptr, mean, rstd, part, gm));
     UC_CHECK_LAUNCH(fn);
     hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)part, gamma, pc, S, gm);
     UC_CHECK_LAUNCH(fn);
@@ -391,11 +391,11 @@ extern "C" int uc_group_norm_nhwc_bwd(const void* dy, const void* x, const void*
     const dim3 agrid((unsigned)((items + 255) / 256));
     const float inv_m = (float)(1.0 / ((double)gm.HW * (double)(gm.cg8 * 8)));
     if (gate)
-        NV_DISPATCH(dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<Tag, true>), agrid, dim3(256), 0, st, (const T*)dy, (const T*)x, (const T*)gate,
-                                              mean, rstd, gamma, (const float*)S, (T*)dx, items, per_sample, inv_m, gm));
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<Tag, true>), agrid, dim3(256), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x, (const Tag::storage*)gate,
+                                              mean, rstd, gamma, (const float*)S, (Tag::storage*)dx, items, per_sample, inv_m, gm));
     else
-        NV_DISPATCH(dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<Tag, false>), agrid, dim3(256), 0, st, (const T*)dy, (const T*)x,
-                                              (const T*)nullptr, mean, rstd, gamma, (const float*)S, (T*)dx, items, per_sample, inv_m, gm));
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<Tag, false>), agrid, dim3(256), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
+                                              (const Tag::storage*)nullptr, mean, rstd, gamma, (const float*)S, (Tag::storage*)dx, items, per_sample, inv_m, gm));
     UC_CHECK_LAUNCH(fn);
     return UC_OK;
 }

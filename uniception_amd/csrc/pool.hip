@@ -7,7 +7,7 @@
 //             atomics: the same bits on every run.
 //   backward: out[b T + t, c] = g[b, c] / T, times (gate[b T + t, c] > 0) when a gate is given (the ReLU of the last res_conv3 under
 //             the residual sum) — the broadcast map is never stored on its own.
-#include "common.h"
+#include "vec_access.h"
 
 #define POOL_CHUNK 64   // rows of T per workgroup of the first stage
 #define POOL_WAVES 4
@@ -137,7 +137,7 @@ extern "C" int uc_token_pool(const void* x, int dtype, int64_t ld, float* out, f
                              uc_stream_t stream) {
     const char* fn = "uc_token_pool";
     UC_REQUIRE(x && out && ws, "%s: null pointer", fn);
-    UC_REQUIRE(dtype == UC_F32 || dtype == UC_BF16 || dtype == UC_F16, "%s: unsupported dtype %d (UC_F32, UC_BF16 or UC_F16)", fn, dtype);
+    UC_REQUIRE_DTYPE(fn, dtype, true);
     UC_REQUIRE(B > 0 && T > 0 && C > 0, "%s: bad shape B=%lld T=%lld C=%lld", fn, (long long)B, (long long)T, (long long)C);
     UC_REQUIRE(ld >= C, "%s: ld (%lld) < C (%lld)", fn, (long long)ld, (long long)C);
     const int V = pool_vec(dtype);
@@ -150,12 +150,7 @@ extern "C" int uc_token_pool(const void* x, int dtype, int64_t ld, float* out, f
                "%s: grid limit exceeded (B <= 65535, T <= %d, C < 2^31, B * C < 2^39)", fn, 65535 * POOL_CHUNK);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)colblocks, (unsigned)nchunk, (unsigned)B), block(64 * POOL_WAVES);
-    if (dtype == UC_F32)
-        hipLaunchKernelGGL(token_pool_partial_kernel<F32Tag>, grid, block, 0, st, (const float*)x, ld, ws, (int)T, (int)C, (int)nchunk);
-    else if (dtype == UC_BF16)
-        hipLaunchKernelGGL(token_pool_partial_kernel<BF16Tag>, grid, block, 0, st, (const bf16_t*)x, ld, ws, (int)T, (int)C, (int)nchunk);
-    else
-        hipLaunchKernelGGL(token_pool_partial_kernel<F16Tag>, grid, block, 0, st, (const unsigned short*)x, ld, ws, (int)T, (int)C, (int)nchunk);
+    UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL(token_pool_partial_kernel<Tag>, grid, block, 0, st, (const Tag::storage*)x, ld, ws, (int)T, (int)C, (int)nchunk));
     UC_CHECK_LAUNCH(fn);
     hipLaunchKernelGGL(token_pool_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)ws, out, total, (int)T,
                        (int)C, (int)nchunk);
@@ -167,7 +162,7 @@ extern "C" int uc_token_pool_bwd(const float* g, const void* gate, int64_t ld_ga
                                  int64_t T, int64_t C, uc_stream_t stream) {
     const char* fn = "uc_token_pool_bwd";
     UC_REQUIRE(g && out, "%s: null pointer", fn);
-    UC_REQUIRE(dtype == UC_F32 || dtype == UC_BF16 || dtype == UC_F16, "%s: unsupported dtype %d (UC_F32, UC_BF16 or UC_F16)", fn, dtype);
+    UC_REQUIRE_DTYPE(fn, dtype, true);
     UC_REQUIRE(B > 0 && T > 0 && C > 0, "%s: bad shape B=%lld T=%lld C=%lld", fn, (long long)B, (long long)T, (long long)C);
     UC_REQUIRE(ld_out >= C, "%s: ld_out (%lld) < C (%lld)", fn, (long long)ld_out, (long long)C);
     UC_REQUIRE(!gate || ld_gate >= C, "%s: ld_gate (%lld) < C (%lld)", fn, (long long)ld_gate, (long long)C);
@@ -181,15 +176,8 @@ extern "C" int uc_token_pool_bwd(const float* g, const void* gate, int64_t ld_ga
     const int64_t total = B * T * ngroups;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (dtype == UC_F32)
-        hipLaunchKernelGGL(token_pool_bwd_kernel<F32Tag>, grid, block, 0, st, g, (const float*)gate, ld_gate, (float*)out, ld_out, total, (int)T,
-                           (int)C, (int)ngroups);
-    else if (dtype == UC_BF16)
-        hipLaunchKernelGGL(token_pool_bwd_kernel<BF16Tag>, grid, block, 0, st, g, (const bf16_t*)gate, ld_gate, (bf16_t*)out, ld_out, total, (int)T,
-                           (int)C, (int)ngroups);
-    else
-        hipLaunchKernelGGL(token_pool_bwd_kernel<F16Tag>, grid, block, 0, st, g, (const unsigned short*)gate, ld_gate, (unsigned short*)out, ld_out,
-                           total, (int)T, (int)C, (int)ngroups);
+    UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL(token_pool_bwd_kernel<Tag>, grid, block, 0, st, g, (const Tag::storage*)gate, ld_gate, (Tag::storage*)out, ld_out, total,
+                                                  (int)T, (int)C, (int)ngroups));
     UC_CHECK_LAUNCH(fn);
     return UC_OK;
 }

@@ -2,7 +2,7 @@
 // Both are HBM-bound streaming kernels: one pass over the data, 16-byte accesses per lane where
 // the layout allows, trig hoisted out of the per-head loop (the reference recomputes nothing per
 // head either: kernels.cu:47-50 computes cos/sin once per (token, channel) and loops over heads).
-#include "common.h"
+#include "vec_access.h"
 #include "knobs.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -127,36 +127,6 @@ extern "C" int uc_rope_table(float* table, int npos, int Q, float base, float F0
 // ---------------------------------------------------------------------------------------
 #define LN_MAXV 8
 
-template <typename TI>
-__device__ __forceinline__ float4_t ln_load4(const typename TI::storage* p);
-template <>
-__device__ __forceinline__ float4_t ln_load4<F32Tag>(const float* p) {
-    return *reinterpret_cast<const float4_t*>(p);
-}
-template <>
-__device__ __forceinline__ float4_t ln_load4<BF16Tag>(const bf16_t* p) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p);
-    float4_t v;
-    v.x = __uint_as_float(r.x << 16);
-    v.y = __uint_as_float(r.x & 0xffff0000u);
-    v.z = __uint_as_float(r.y << 16);
-    v.w = __uint_as_float(r.y & 0xffff0000u);
-    return v;
-}
-template <typename TO>
-__device__ __forceinline__ void ln_store4(typename TO::storage* p, float4_t v);
-template <>
-__device__ __forceinline__ void ln_store4<F32Tag>(float* p, float4_t v) {
-    *reinterpret_cast<float4_t*>(p) = v;
-}
-template <>
-__device__ __forceinline__ void ln_store4<BF16Tag>(bf16_t* p, float4_t v) {
-    uint2 r;
-    r.x = pack_bf16x2(v.x, v.y);
-    r.y = pack_bf16x2(v.z, v.w);
-    *reinterpret_cast<uint2*>(p) = r;
-}
-
 // Exact-width variant: C == NV*256, no per-chunk predicates, so all NV 16-byte loads of a row are issued back to back
 // (the predicated generic kernel below serialises them behind exec-mask branches: 2.8 TB/s vs 7+ TB/s cache-hot).
 template <typename TI, typename TO, int NV, bool NT = false>
@@ -176,7 +146,7 @@ __global__ __launch_bounds__(256) void layernorm_exact_kernel(const typename TI:
         // NT: an fp32 residual stream larger than half the Infinity Cache is read once here and once by the next residual
         // epilogue, two GEMMs later — streaming it leaves the caches to the GEMM operands
         if constexpr (NT && std::is_same<TI, F32Tag>::value) v[i] = __builtin_nontemporal_load(reinterpret_cast<const float4_t*>(xr + (i * 64 + lane) * 4));
-        else v[i] = ln_load4<TI>(xr + (i * 64 + lane) * 4);
+        else v[i] = vec_load4<TI>(xr + (i * 64 + lane) * 4);
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -202,8 +172,8 @@ __global__ __launch_bounds__(256) void layernorm_exact_kernel(const typename TI:
         o.y = (v[i].y - mean) * rstd * g[i].y + bb[i].y;
         o.z = (v[i].z - mean) * rstd * g[i].z + bb[i].z;
         o.w = (v[i].w - mean) * rstd * g[i].w + bb[i].w;
-        ln_store4<TO>(yr + (i * 64 + lane) * 4, o);
-        if (twin) ln_store4<BF16Tag>(twin + row * C + (i * 64 + lane) * 4, o);   // bf16 copy for the consumers that take bf16 operands
+        vec_store4<TO>(yr + (i * 64 + lane) * 4, o);
+        if (twin) vec_store4<BF16Tag>(twin + row * C + (i * 64 + lane) * 4, o);   // bf16 copy for the consumers that take bf16 operands
     }
 }
 
@@ -223,7 +193,7 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const typename TI::s
     for (int i = 0; i < LN_MAXV; ++i) {
         const int c = (i * 64 + lane) * 4;
         if (c < C) {
-            v[i] = ln_load4<TI>(xr + c);
+            v[i] = vec_load4<TI>(xr + c);
             s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
         }
     }
@@ -250,8 +220,8 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const typename TI::s
             o.y = (v[i].y - mean) * rstd * g.y + bb.y;
             o.z = (v[i].z - mean) * rstd * g.z + bb.z;
             o.w = (v[i].w - mean) * rstd * g.w + bb.w;
-            ln_store4<TO>(yr + c, o);
-            if (twin) ln_store4<BF16Tag>(twin + row * C + c, o);
+            vec_store4<TO>(yr + c, o);
+            if (twin) vec_store4<BF16Tag>(twin + row * C + c, o);
         }
     }
 }

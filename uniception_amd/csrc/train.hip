@@ -3,7 +3,7 @@
 // contiguous dimension), fused adaptor+loss forward/backward, pixel un-shuffle, AdamW.
 // The reference has no hand-written backward (it is PyTorch autograd over the modules); each kernel cites the forward
 // expression it differentiates in include/uc_hip.h.
-#include "common.h"
+#include "vec_access.h"
 #include <algorithm>
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -11,28 +11,6 @@
 // distributed grid-stride so each wave also accumulates its share of dgamma/dbeta in registers and issues ONE atomic
 // per column at the end.
 // ---------------------------------------------------------------------------------------------------------------
-template <typename TD>
-__device__ __forceinline__ float4_t tr_load4(const typename TD::storage* p);
-template <>
-__device__ __forceinline__ float4_t tr_load4<F32Tag>(const float* p) { return *reinterpret_cast<const float4_t*>(p); }
-template <>
-__device__ __forceinline__ float4_t tr_load4<BF16Tag>(const bf16_t* p) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p);
-    float4_t v;
-    v.x = __uint_as_float(r.x << 16); v.y = __uint_as_float(r.x & 0xffff0000u);
-    v.z = __uint_as_float(r.y << 16); v.w = __uint_as_float(r.y & 0xffff0000u);
-    return v;
-}
-
-template <typename TX>
-__device__ __forceinline__ void tr_store4(typename TX::storage* p, float4_t o);
-template <>
-__device__ __forceinline__ void tr_store4<F32Tag>(float* p, float4_t o) { *reinterpret_cast<float4_t*>(p) = o; }
-template <>
-__device__ __forceinline__ void tr_store4<BF16Tag>(bf16_t* p, float4_t o) {
-    *reinterpret_cast<uint2*>(p) = (uint2){pack_bf16x2(o.x, o.y), pack_bf16x2(o.z, o.w)};
-}
-
 // a lane's four values as they lie in memory (kept packed while in flight)
 template <typename T> struct TrRaw;
 template <> struct TrRaw<F32Tag> {
@@ -41,9 +19,7 @@ template <> struct TrRaw<F32Tag> {
 };
 template <> struct TrRaw<BF16Tag> {
     typedef uint2 type;
-    static __device__ __forceinline__ float4_t unpack(uint2 r) {
-        return (float4_t){__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
-    }
+    static __device__ __forceinline__ float4_t unpack(uint2 r) { return unpack_bf16x4(r); }
 };
 
 __device__ __forceinline__ void wave_sum2(float& a, float& b) {
@@ -133,7 +109,7 @@ __global__ __launch_bounds__(512) void layernorm_bwd_kernel(const typename TX::s
             o.z = rstd * (d[i].z - s1 - v[i].z * s2);
             o.w = rstd * (d[i].w - s1 - v[i].w * s2);
             if (dres) { o.x += rs[i].x; o.y += rs[i].y; o.z += rs[i].z; o.w += rs[i].w; }
-            tr_store4<TX>(dx + row * C + (i * 64 + lane) * 4, o);
+            vec_store4<TX>(dx + row * C + (i * 64 + lane) * 4, o);
             if (dx_b) {   // bf16 twin of dx: the operand the previous sub-layer's backward GEMMs will want
                 uint2 pk;
                 pk.x = pack_bf16x2(o.x, o.y);
@@ -179,7 +155,7 @@ __global__ __launch_bounds__(256) void layernorm64_bwd_kernel(const typename TX:
         const int64_t row = r0 + rg;
         const bool ok = row < rows;
         float4_t v = {0.f, 0.f, 0.f, 0.f}, d = {0.f, 0.f, 0.f, 0.f};
-        if (ok) { v = tr_load4<TX>(x + row * 64 + 4 * sub); d = tr_load4<TD>(dy + row * 64 + 4 * sub); }
+        if (ok) { v = vec_load4<TX>(x + row * 64 + 4 * sub); d = vec_load4<TD>(dy + row * 64 + 4 * sub); }
         const float mean = row16_sum((v.x + v.y) + (v.z + v.w)) * (1.0f / 64.0f);
         v.x -= mean; v.y -= mean; v.z -= mean; v.w -= mean;
         const float rstd = rsqrtf(row16_sum((v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w)) * (1.0f / 64.0f) + eps);
@@ -193,7 +169,7 @@ __global__ __launch_bounds__(256) void layernorm64_bwd_kernel(const typename TX:
             float4_t o;
             o.x = rstd * (d.x - s1 - v.x * s2); o.y = rstd * (d.y - s1 - v.y * s2);
             o.z = rstd * (d.z - s1 - v.z * s2); o.w = rstd * (d.w - s1 - v.w * s2);
-            tr_store4<TX>(dx + row * 64 + 4 * sub, o);
+            vec_store4<TX>(dx + row * 64 + 4 * sub, o);
         }
     }
 #pragma unroll
@@ -321,13 +297,13 @@ __global__ __launch_bounds__(256) void colsum_kernel(const typename Tag::storage
     if (c0 + 3 < N && (ld % 4 == 0)) {
         int64_t r = r0 + rl;
         for (; r + 12 < r1; r += 16) {   // 4 independent loads in flight
-            const float4_t v0 = tr_load4<Tag>(src + r * ld + c0), v1 = tr_load4<Tag>(src + (r + 4) * ld + c0);
-            const float4_t v2 = tr_load4<Tag>(src + (r + 8) * ld + c0), v3 = tr_load4<Tag>(src + (r + 12) * ld + c0);
+            const float4_t v0 = vec_load4<Tag>(src + r * ld + c0), v1 = vec_load4<Tag>(src + (r + 4) * ld + c0);
+            const float4_t v2 = vec_load4<Tag>(src + (r + 8) * ld + c0), v3 = vec_load4<Tag>(src + (r + 12) * ld + c0);
             a[0] += (v0.x + v1.x) + (v2.x + v3.x); a[1] += (v0.y + v1.y) + (v2.y + v3.y);
             a[2] += (v0.z + v1.z) + (v2.z + v3.z); a[3] += (v0.w + v1.w) + (v2.w + v3.w);
         }
         for (; r < r1; r += 4) {
-            const float4_t v = tr_load4<Tag>(src + r * ld + c0);
+            const float4_t v = vec_load4<Tag>(src + r * ld + c0);
             a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
         }
     } else {
@@ -358,9 +334,7 @@ extern "C" int uc_colsum(const void* src, int dtype, int64_t M, int64_t N, int64
     dim3 grid(gx, (unsigned)min(max_slabs, ceil_div64(M, 64)));
     const int64_t rpb = ceil_div64(M, grid.y);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_F32) hipLaunchKernelGGL((colsum_kernel<F32Tag>), grid, dim3(256), 0, st, (const float*)src, M, N, ld, out, rpb);
-    else if (dtype == UC_BF16) hipLaunchKernelGGL((colsum_kernel<BF16Tag>), grid, dim3(256), 0, st, (const bf16_t*)src, M, N, ld, out, rpb);
-    else { uc_set_error("uc_colsum: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH("uc_colsum", dtype, hipLaunchKernelGGL((colsum_kernel<Tag>), grid, dim3(256), 0, st, (const Tag::storage*)src, M, N, ld, out, rpb));
     UC_CHECK_LAUNCH("uc_colsum");
     return UC_OK;
 }
@@ -414,11 +388,9 @@ extern "C" int uc_act_bwd(const void* dg, const void* u, void* du, int dtype, in
     UC_REQUIRE(dg && u && du && n >= 0, "uc_act_bwd: bad argument");
     UC_REQUIRE(act == UC_ACT_GELU_ERF || act == UC_ACT_RELU, "uc_act_bwd: bad act %d", act);
     if (n == 0) return UC_OK;
-    const unsigned grid = (unsigned)min((int64_t)65536 * 4, ceil_div64(n, 256));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UC_F32) hipLaunchKernelGGL((act_bwd_kernel<F32Tag>), dim3(grid), dim3(256), 0, st, (const float*)dg, (const float*)u, (float*)du, act, n);
-    else if (dtype == UC_BF16) hipLaunchKernelGGL((act_bwd_kernel<BF16Tag>), dim3(grid), dim3(256), 0, st, (const bf16_t*)dg, (const bf16_t*)u, (bf16_t*)du, act, n);
-    else { uc_set_error("uc_act_bwd: bad dtype %d", dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH("uc_act_bwd", dtype,
+                hipLaunchKernelGGL((act_bwd_kernel<Tag>), dim3(EW_GRID(n)), dim3(256), 0, st, (const Tag::storage*)dg, (const Tag::storage*)u, (Tag::storage*)du, act, n));
     UC_CHECK_LAUNCH("uc_act_bwd");
     return UC_OK;
 }
@@ -434,7 +406,7 @@ __global__ __launch_bounds__(256) void mask_scale_kernel(const typename TX::stor
                                                          const typename TO::storage* __restrict__ residual, typename TO::storage* __restrict__ out,
                                                          int64_t n4, int cols4, int64_t rows_per_mask, float scale) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        float4_t v = tr_load4<TX>(x + i * 4);
+        float4_t v = vec_load4<TX>(x + i * 4);
         float4_t m;
         if (rows_per_mask > 0) {
             const float k = mask[(i / cols4) / rows_per_mask] ? scale : 0.f;
@@ -445,10 +417,10 @@ __global__ __launch_bounds__(256) void mask_scale_kernel(const typename TX::stor
         }
         v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
         if (residual) {
-            const float4_t r = tr_load4<TO>(residual + i * 4);
+            const float4_t r = vec_load4<TO>(residual + i * 4);
             v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
         }
-        tr_store4<TO>(out + i * 4, v);
+        vec_store4<TO>(out + i * 4, v);
     }
 }
 
@@ -522,13 +494,9 @@ static int swiglu_launch(const void* t, const void* dg, void* out, int dtype, in
     for (int64_t m0 = 0; m0 < M; m0 += rows_per) {
         const int64_t mc = std::min(rows_per, M - m0);
         const unsigned grid = (unsigned)std::min<int64_t>((int64_t)uc_num_cus() * 16, ceil_div64(mc * (H / 8), 256));
-        const size_t es = dtype == UC_F32 ? 4 : 2;
-        const char* tp = (const char*)t + (size_t)m0 * 2 * H * es;
-        const char* gp = dg ? (const char*)dg + (size_t)m0 * H * es : nullptr;
-        char* op = (char*)out + (size_t)m0 * (BWD ? 2 : 1) * H * es;
-        if (dtype == UC_F32) hipLaunchKernelGGL((swiglu_kernel<F32Tag, BWD>), dim3(grid), dim3(256), 0, st, (const float*)tp, (const float*)gp, (float*)op, mc, (int)H, d);
-        else if (dtype == UC_BF16) hipLaunchKernelGGL((swiglu_kernel<BF16Tag, BWD>), dim3(grid), dim3(256), 0, st, (const bf16_t*)tp, (const bf16_t*)gp, (bf16_t*)op, mc, (int)H, d);
-        else { uc_set_error("%s: bad dtype %d", who, dtype); return UC_ERR_BAD_ARG; }
+        UC_DISPATCH(who, dtype,
+                    hipLaunchKernelGGL((swiglu_kernel<Tag, BWD>), dim3(grid), dim3(256), 0, st, (const Tag::storage*)t + m0 * 2 * H,
+                                       dg ? (const Tag::storage*)dg + m0 * H : nullptr, (Tag::storage*)out + m0 * (BWD ? 2 : 1) * H, mc, (int)H, d));
     }
     return UC_OK;
 }
@@ -735,11 +703,9 @@ __global__ void pixel_unshuffle_kernel(const float* __restrict__ src, typename T
 extern "C" int uc_pixel_unshuffle(const float* src, void* dst, int dst_dtype, int B, int h, int w, int P, int Cout, uc_stream_t stream) {
     UC_REQUIRE(src && dst && B > 0 && h > 0 && w > 0 && P > 0 && Cout > 0, "uc_pixel_unshuffle: bad argument");
     const int64_t n = (int64_t)B * h * w * Cout * P * P;
-    const unsigned grid = (unsigned)min((int64_t)65536 * 4, ceil_div64(n, 256));
     hipStream_t st = (hipStream_t)stream;
-    if (dst_dtype == UC_F32) hipLaunchKernelGGL((pixel_unshuffle_kernel<F32Tag>), dim3(grid), dim3(256), 0, st, src, (float*)dst, B, h, w, P, Cout, n);
-    else if (dst_dtype == UC_BF16) hipLaunchKernelGGL((pixel_unshuffle_kernel<BF16Tag>), dim3(grid), dim3(256), 0, st, src, (bf16_t*)dst, B, h, w, P, Cout, n);
-    else { uc_set_error("uc_pixel_unshuffle: bad dtype %d", dst_dtype); return UC_ERR_BAD_ARG; }
+    UC_DISPATCH("uc_pixel_unshuffle", dst_dtype,
+                hipLaunchKernelGGL((pixel_unshuffle_kernel<Tag>), dim3(EW_GRID(n)), dim3(256), 0, st, src, (Tag::storage*)dst, B, h, w, P, Cout, n));
     UC_CHECK_LAUNCH("uc_pixel_unshuffle");
     return UC_OK;
 }
