@@ -866,19 +866,31 @@ def gemm_tn_query(a: torch.Tensor, b: torch.Tensor, conv: Optional[Tuple[int, bo
 
 
 def gemm_tn(a: torch.Tensor, b: torch.Tensor, split_k: Optional[int] = None, conv: Optional[Tuple[int, bool]] = None,
-            colsum: bool = False, colsum_into: Optional[torch.Tensor] = None):
+            colsum: bool = False, colsum_into: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+            colsum_out: Optional[torch.Tensor] = None):
     """Weight-gradient contraction over the slow axis: returns fp32 slabs [split_k, I, J] of  sum_t a[t,i] * b[t,j].
     a: [T,I] bf16 (unit column stride).  b: [T,J] bf16, or with conv=(stride, relu) the NHWC input [B,H,W,Cin] of a
     3x3/pad-1 conv whose im2col ([T, 9*Cin], T = output pixels) is formed implicitly.
     split_k=None: the slice count the library recommends for this shape (uc_gemm_tn_query).
     colsum=True: also returns slabs [split_k, I] of sum_t a[t,i] (the bias gradient).
-    colsum_into: fp32 [I] buffer that receives += sum_t a[t,i] atomically instead (e.g. the bias's gradient buffer)."""
+    colsum_into: fp32 [I] buffer that receives += sum_t a[t,i] atomically instead (e.g. the bias's gradient buffer).
+    out / colsum_out: caller-provided contiguous fp32 [split_k, I, J] / [split_k, I] (with colsum=True) to write the slabs to, e.g.
+    the front of a larger buffer; allocated here when omitted."""
     d = _gemm_tn_desc(a, b, conv)
     d.split_k = _gemm_tn_query(d)[1] if split_k is None else split_k
-    out = torch.empty((d.split_k, d.I, d.J), dtype=torch.float32, device=a.device)
+    if out is None:
+        out = torch.empty((d.split_k, d.I, d.J), dtype=torch.float32, device=a.device)
+    else:
+        _need_gpu(out)
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (d.split_k, d.I, d.J)
+    assert colsum_out is None or colsum, "colsum_out goes with colsum=True"
     if colsum_into is not None:
         assert colsum_into.dtype == torch.float32 and colsum_into.is_contiguous() and colsum_into.numel() == d.I and not colsum
         cs, d.colsum_atomic = colsum_into, 1
+    elif colsum_out is not None:
+        _need_gpu(colsum_out)
+        assert colsum_out.dtype == torch.float32 and colsum_out.is_contiguous() and tuple(colsum_out.shape) == (d.split_k, d.I)
+        cs = colsum_out
     else:
         cs = torch.empty((d.split_k, d.I), dtype=torch.float32, device=a.device) if colsum else None
     d.C, d.colsum_a = out.data_ptr(), _p(cs)
