@@ -61,7 +61,7 @@ the wrapper really passed goes to the same driver on the GPU, so a change of rou
 No witness needs more than REF_BUDGET_FLOP of fp64 work (4 * T * I * J: reference and S).
 
 OPERANDS (`make_operands`): seeded bf16, O(1), normal numbers only (magnitudes >= 2^-6).  Under relu_b the image holds negative values,
-exact +0.0 and exact -0.0 (tn_relu4 is an int16 max: -0.0 = 0x8000 must come out as zero).  Every operand lives inside NaN: A is a view
+exact +0.0 and exact -0.0 (relu_bf16x4 is an int16 max: -0.0 = 0x8000 must come out as zero).  Every operand lives inside NaN: A is a view
 [:T, a_off : a_off + I] of a NaN-filled [T + 8, lda] buffer, dense B likewise, the conv image is images 1 .. B of a NaN-filled
 [B + 2, H, W, Cin] buffer.  A kernel that multiplies anything it should have replaced by zero, and stores it, produces a NaN.
 

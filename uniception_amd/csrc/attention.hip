@@ -13,13 +13,11 @@
 //   (double-buffered, XOR-swizzled 128-byte rows, one barrier per tile).
 //
 // attn_f32_kernel — verification mode: one thread per query row, fp32 FMA chains, expf.
-#include "common.h"
+#include "mma_tile.h"
 #include "knobs.h"
 #include "attention_p64.h"
 #include "attention_plan.h"
 #include <stdlib.h>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 struct AttnParams {
     const void* Q;
@@ -38,14 +36,6 @@ struct AttnParams {
 
 #define KV_TILE 64
 #define ATT_TILE_BYTES (KV_TILE * 128)  // 64 rows x 128 B
-
-__device__ __forceinline__ int att_swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-// key offset inside a 16-key group for VT position pp (inverse of uc_vt_perm)
-__device__ __forceinline__ int vt_key_of_pos(int pp) {
-    const int hi = pp >> 3, j = pp & 7;
-    return (j & 3) + 8 * (j >> 2) + 4 * hi;
-}
 
 // the body of attn_bf16_kernel for the 128 queries from q0w of (batch b, head h): also what attn_bf16_fixup_kernel recomputes a
 // flagged block of the persistent kernel with (attention_p64.h)
@@ -111,7 +101,7 @@ __device__ __forceinline__ void attn_bf16_body(const AttnParams& p, const int b,
         rv1 = load_v((k0_), sr + 32);       \
     } while (0)
     // loop-invariant LDS byte offsets: rows r and r+32 share the swizzle key, so one offset + an immediate serves both
-    const int w_off = att_swz(sr, cc);
+    const int w_off = tile_swz(sr, cc);
 #define ATT_STAGE_WRITE(buf_)                                                          \
     do {                                                                               \
         char* sk_ = smem + (buf_) * 2 * ATT_TILE_BYTES + w_off;                        \
@@ -122,7 +112,7 @@ __device__ __forceinline__ void attn_bf16_body(const AttnParams& p, const int b,
     } while (0)
     int r_off[4];   // fragment read offsets: row l31 (+32 via immediate), chunk 2*st+hi, st = 0..3 (K and VT tiles alike)
 #pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = att_swz(l31, 2 * st + hi);
+    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
 
     float16_t o[2];   // O^T accumulators: d-block x (16 regs): d = 32*db + (r&3) + 8*(r>>2) + 4*hi, q = l31
     o[0] = (float16_t)(0.f);
@@ -298,25 +288,6 @@ __global__ __launch_bounds__(256) void attn_bf16_fixup_kernel(AttnParams p) {
 // of 4 waves per SIMD.  Descriptors: K rows / VT rows of this (batch, head); the per-lane byte offsets are loop
 // invariant, the tile advance is a wave-uniform soffset.
 // ---------------------------------------------------------------------------------------
-typedef unsigned att_uint4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void att_dma16(unsigned voff, att_uint4_t srd, unsigned soff, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 4\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(lds_byte_addr), "s"(soff)
-        : "memory");
-}
-__device__ __forceinline__ att_uint4_t att_make_srd(const void* base) {
-    const unsigned long long pa = (unsigned long long)base;
-    return (att_uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pa),
-                         (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pa >> 32) & 0xffffu)), 0xffffff00u, 0x00020000u};
-}
-
 // What bounds it (round 2, tools/scratch/probe_attn_anatomy.py and its SQ counters, B = 64, H = 16, N = 1024): the costs of the exp2
 // work and of the PV products are ADDITIVE (-18 % without the exps, -20 % without the PV MFMAs, -2 % without the per-tile
 // barrier; static priorities or a start stagger per workgroup slot: nothing).  SQ_ACTIVE_INST_VALU — which includes a matrix
@@ -338,23 +309,12 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_bf16_dma_kernel(AttnParams p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hi = lane >> 5;
     const int l31 = lane & 31;
-    // 1-D grid.  Workgroup w runs on XCD w % 8 (round-robin dispatch): the nq query tiles that share one (batch, head)'s
-    // K/VT rows are given ids that differ by multiples of 8, so that they meet in ONE XCD's L2 instead of pulling the
-    // same K/VT through all eight.
+    // 1-D grid: the nq query tiles that share one (batch, head)'s K/VT rows meet in one XCD's L2 (xcd_tile_order)
     constexpr int QT = 32 * NW;                 // queries per workgroup
     const int nq = (p.Nq + QT - 1) / QT;
     const int nbh = p.B * p.H;
     int qt, bh;
-    {
-        const int w = blockIdx.x;
-        const int per_group = 8 * nq;
-        const int grp = (int)uc_div((unsigned)w, p.dGroup), within = w - grp * per_group;
-        if ((grp + 1) * 8 <= nbh) { bh = grp * 8 + (within & 7); qt = within >> 3; }
-        else {   // last, partial group: plain order
-            const int rem = w - (nbh >> 3) * 8 * nq, rb = (int)uc_div((unsigned)rem, p.dNq);
-            bh = (nbh >> 3) * 8 + rb; qt = rem - rb * nq;
-        }
-    }
+    xcd_tile_order((int)blockIdx.x, nq, nbh, p.dGroup, p.dNq, qt, bh);
     const int b = (int)uc_div((unsigned)bh, p.dH), h = bh - b * p.H;
     const int q0 = qt * QT + wave * 32;
     if constexpr (DBG & 8) {    // experiment: static priority by (approximate) workgroup slot on the CU
@@ -378,10 +338,10 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_bf16_dma_kernel(AttnParams p)
 
     // ---- DMA assignment: a tile is 8 instructions of 8 rows x 128 B; wave w issues instructions PW*w .. PW*w + PW - 1 of both tiles ----
     constexpr int PW = 8 / NW;                  // 2 (four waves) or 1 (eight waves)
-    att_uint4_t srd_k = att_make_srd(Kb);
+    uint4_t srd_k = make_srd(Kb);
     srd_k.z = (unsigned)__builtin_amdgcn_readfirstlane((int)((((int64_t)p.Nk - 1) * p.k_sn + 64) * 2));   // key rows >= Nk read as zeros
-    const att_uint4_t srd_v = att_make_srd(VTb);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)smem;
+    const uint4_t srd_v = make_srd(VTb);
+    const unsigned lds0 = lds_addr(smem);
     unsigned voff_k[PW], voff_v[PW];
 #pragma unroll
     for (int i = 0; i < PW; ++i) {
@@ -395,8 +355,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_bf16_dma_kernel(AttnParams p)
         const unsigned dst = lds0 + (unsigned)(buf * 2 * ATT_TILE_BYTES + wave * (PW * 1024));
 #pragma unroll
         for (int i = 0; i < PW; ++i) {
-            att_dma16(voff_k[i], srd_k, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + i * 1024));
-            att_dma16(voff_v[i], srd_v, (unsigned)t * (KV_TILE * 2), __builtin_amdgcn_readfirstlane(dst + ATT_TILE_BYTES + i * 1024));
+            dma16_buf_to_lds(voff_k[i], srd_k, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + i * 1024));
+            dma16_buf_to_lds(voff_v[i], srd_v, (unsigned)t * (KV_TILE * 2), __builtin_amdgcn_readfirstlane(dst + ATT_TILE_BYTES + i * 1024));
         }
     };
 
@@ -406,19 +366,19 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_bf16_dma_kernel(AttnParams p)
     {
         const unsigned long long qa = (unsigned long long)(Qb + (int64_t)q0 * p.q_sn);
         const int64_t q_rows = min((int64_t)32, (int64_t)p.Nq - q0);
-        att_uint4_t srd_q = att_make_srd((const void*)qa);
+        uint4_t srd_q = make_srd((const void*)qa);
         srd_q.z = (unsigned)__builtin_amdgcn_readfirstlane((int)(q_rows > 0 ? ((q_rows - 1) * p.q_sn + 64) * 2 : 0));
         const unsigned dstq = lds0 + (unsigned)(2 * ATT_TILE_BYTES + wave * 4096);     // waves 4..7 land behind the second stage
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int rr = i * 8 + (lane >> 3);
             const int cch = (lane & 7) ^ ((rr >> 1) & 7);
-            att_dma16((unsigned)(((int64_t)rr * p.q_sn + cch * 8) * 2), srd_q, 0u, __builtin_amdgcn_readfirstlane(dstq + i * 1024));
+            dma16_buf_to_lds((unsigned)(((int64_t)rr * p.q_sn + cch * 8) * 2), srd_q, 0u, __builtin_amdgcn_readfirstlane(dstq + i * 1024));
         }
     }
     int r_off[4];   // fragment read offsets: row l31 (+32 via immediate), chunk 2*st+hi, st = 0..3 (K and VT tiles alike)
 #pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = att_swz(l31, 2 * st + hi);
+    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
 
     issue_tile(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -573,16 +533,7 @@ __global__ __launch_bounds__(512, 4) void attn_bf16_rs_kernel(AttnParams p) {
     const int nq = (p.Nq + QT - 1) / QT;
     const int nbh = p.B * p.H;
     int qt, bh;
-    {
-        const int w = blockIdx.x;
-        const int per_group = 8 * nq;
-        const int grp = (int)uc_div((unsigned)w, p.dGroup), within = w - grp * per_group;
-        if ((grp + 1) * 8 <= nbh) { bh = grp * 8 + (within & 7); qt = within >> 3; }
-        else {
-            const int rem = w - (nbh >> 3) * 8 * nq, rb = (int)uc_div((unsigned)rem, p.dNq);
-            bh = (nbh >> 3) * 8 + rb; qt = rem - rb * nq;
-        }
-    }
+    xcd_tile_order((int)blockIdx.x, nq, nbh, p.dGroup, p.dNq, qt, bh);
     const int b = (int)uc_div((unsigned)bh, p.dH), h = bh - b * p.H;
     const int q0 = qt * QT + wave * 32;
 
@@ -591,10 +542,10 @@ __global__ __launch_bounds__(512, 4) void attn_bf16_rs_kernel(AttnParams p) {
     const bf16_t* VTb = (const bf16_t*)p.V + ((int64_t)b * p.H + h) * 64 * (int64_t)p.npad;
 
     // DMA: a tile is 8 instructions of 8 rows x 128 B; wave w issues instruction w of the K tile and of the VT tile
-    att_uint4_t srd_k = att_make_srd(Kb);
+    uint4_t srd_k = make_srd(Kb);
     srd_k.z = (unsigned)__builtin_amdgcn_readfirstlane((int)((((int64_t)p.Nk - 1) * p.k_sn + 64) * 2));   // key rows >= Nk read as zeros
-    const att_uint4_t srd_v = att_make_srd(VTb);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)smem;
+    const uint4_t srd_v = make_srd(VTb);
+    const unsigned lds0 = lds_addr(smem);
     unsigned voff_k, voff_v;
     {
         const int rr = wave * 8 + (lane >> 3);
@@ -604,28 +555,28 @@ __global__ __launch_bounds__(512, 4) void attn_bf16_rs_kernel(AttnParams p) {
     }
     const unsigned kstep = (unsigned)(KV_TILE * p.k_sn * 2);
     auto issue_k = [&](int t) {
-        att_dma16(voff_k, srd_k, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * 2 * ATT_TILE_BYTES + wave * 1024)));
+        dma16_buf_to_lds(voff_k, srd_k, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * 2 * ATT_TILE_BYTES + wave * 1024)));
     };
     auto issue_v = [&](int t) {
-        att_dma16(voff_v, srd_v, (unsigned)t * (KV_TILE * 2),
+        dma16_buf_to_lds(voff_v, srd_v, (unsigned)t * (KV_TILE * 2),
                   __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * 2 * ATT_TILE_BYTES + ATT_TILE_BYTES + wave * 1024)));
     };
     {   // Q rows of this wave into the second stage (waves 0-3) / the third region (waves 4-7)
         const unsigned long long qa = (unsigned long long)(Qb + (int64_t)q0 * p.q_sn);
         const int64_t q_rows = min((int64_t)32, (int64_t)p.Nq - q0);
-        att_uint4_t srd_q = att_make_srd((const void*)qa);
+        uint4_t srd_q = make_srd((const void*)qa);
         srd_q.z = (unsigned)__builtin_amdgcn_readfirstlane((int)(q_rows > 0 ? ((q_rows - 1) * p.q_sn + 64) * 2 : 0));
         const unsigned dstq = lds0 + (unsigned)(2 * ATT_TILE_BYTES + wave * 4096);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int rr = i * 8 + (lane >> 3);
             const int cch = (lane & 7) ^ ((rr >> 1) & 7);
-            att_dma16((unsigned)(((int64_t)rr * p.q_sn + cch * 8) * 2), srd_q, 0u, __builtin_amdgcn_readfirstlane(dstq + i * 1024));
+            dma16_buf_to_lds((unsigned)(((int64_t)rr * p.q_sn + cch * 8) * 2), srd_q, 0u, __builtin_amdgcn_readfirstlane(dstq + i * 1024));
         }
     }
     int r_off[4];
 #pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = att_swz(l31, 2 * st + hi);
+    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
 
     issue_k(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

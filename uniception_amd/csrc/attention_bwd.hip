@@ -17,15 +17,10 @@
 // no packed transposes, no permutation pass.
 // LDS tiles are 64 rows x 128 B with the (row>>1)&7 chunk swizzle (conflict-free ds_read_b128; the transposing reads see
 // 2-way conflicts between rows r and r+2, which the MFMA/VALU work hides), single-buffered, 2-3 workgroups per CU.
-#include "common.h"
+#include "mma_tile.h"
 #include "knobs.h"
 #include "attention_plan.h"
 #include <math.h>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* ab_lds_ptr_t;
-typedef __attribute__((address_space(3))) bf16x4_t* ab_lds_v4_t;
 
 struct AttnBwdParams {
     const bf16_t *Q, *K, *V, *O, *dO;
@@ -49,8 +44,6 @@ struct AttnBwdParams {
 
 #define TB (64 * 128)   // bytes of one 64-row tile
 
-__device__ __forceinline__ int bswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
 // Transposed MFMA A operand out of a row-major [64 rows][64 channels] swizzled tile: for the 32-channel block `cb` the lane
 // (channel = 32 cb + (lane & 31), k half = lane >> 5) receives rows  slab16*16 + 4*(lane>>5) + {0,1,2,3, 8,9,10,11}.
 __device__ __forceinline__ bf16x8_t tr_operand(const char* tile, int slab16, int cb, int lane) {
@@ -60,29 +53,15 @@ __device__ __forceinline__ bf16x8_t tr_operand(const char* tile, int slab16, int
     const int chunk = (d0 >> 3) + (piece >> 1);
     const int row0 = slab16 * 16 + 4 * (lane >> 5) + (jj >> 2);
     const int row1 = row0 + 8;
-    const char* a0 = tile + row0 * 128 + ((chunk ^ ((row0 >> 1) & 7)) << 4) + ((piece & 1) << 3);
-    const char* a1 = tile + row1 * 128 + ((chunk ^ ((row1 >> 1) & 7)) << 4) + ((piece & 1) << 3);
-    const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((ab_lds_v4_t)(ab_lds_ptr_t)a0);
-    const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((ab_lds_v4_t)(ab_lds_ptr_t)a1);
+    const char* a0 = tile + row0 * 128 + tile_swz_chunk(row0, chunk) + ((piece & 1) << 3);
+    const char* a1 = tile + row1 * 128 + tile_swz_chunk(row1, chunk) + ((piece & 1) << 3);
+    const bf16x4_t lo = lds_read_tr16(a0), hi = lds_read_tr16(a1);
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-// Asynchronous global -> LDS copy of one [64 rows][64 bf16] tile in the swizzled image (global_load_lds_dwordx4, 1 KiB per
+// Asynchronous global -> LDS copy of one [64 rows][64 bf16] tile in the swizzled image (dma16_to_lds, 1 KiB per
 // wave-instruction: lane -> row 8 n + (lane >> 3), physical chunk lane & 7 <- logical chunk (lane & 7) ^ ((row >> 1) & 7)).
 // Wave w issues instructions 2w and 2w+1; rows beyond n_rows re-read the last valid row (their scores are masked).
-__device__ __forceinline__ void ab_dma16(const void* gsrc, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_byte_addr)
-        : "memory");
-}
-
 __device__ __forceinline__ void dma_tile(const bf16_t* base, int64_t row_stride, int row0, int n_rows, unsigned lds_tile, int wave,
                                          int lane) {
 #pragma unroll
@@ -92,7 +71,7 @@ __device__ __forceinline__ void dma_tile(const bf16_t* base, int64_t row_stride,
         int row = row0 + rr;
         if (row >= n_rows) row = n_rows - 1;
         const int c = (lane & 7) ^ ((rr >> 1) & 7);
-        ab_dma16(base + (int64_t)row * row_stride + c * 8, __builtin_amdgcn_readfirstlane(lds_tile + (unsigned)(n * 1024)));
+        dma16_to_lds(base + (int64_t)row * row_stride + c * 8, __builtin_amdgcn_readfirstlane(lds_tile + (unsigned)(n * 1024)));
     }
 }
 
@@ -127,15 +106,6 @@ __device__ __forceinline__ void ab_rope_inverse(float16_t (&g)[2], const int64_t
 // =================================================================================================================
 // dQ
 // =================================================================================================================
-// 1-D grid -> (tile, batch*head): workgroup w runs on XCD w % 8 (round-robin dispatch), so the nt tiles that share one
-// (batch, head)'s operands get ids that differ by multiples of 8 and meet in ONE XCD's L2 (see attn_bf16_dma_kernel)
-__device__ __forceinline__ void ab_xcd_order(int w, int nt, int nbh, int& tile, int& bh) {
-    const int per_group = 8 * nt;
-    const int grp = w / per_group, within = w - grp * per_group;
-    if ((grp + 1) * 8 <= nbh) { bh = grp * 8 + (within & 7); tile = within >> 3; }
-    else { const int rem = w - (nbh / 8) * 8 * nt; bh = (nbh / 8) * 8 + rem / nt; tile = rem % nt; }
-}
-
 // DROP (attention dropout, uc_attention_bwd with drop_p > 0): the forward computed O = P' V with P' = P o mask / (1 - p).  dV = P'^T dO;
 // dP' = dO V^T; dP = dP' o mask / (1 - p); dS = P o (dP - delta) with delta = rowsum(dP o P) = rowsum(dP' o P') = rowsum(dO o O) as
 // without dropout.  The accumulator chain that starts at -delta holds dP' - delta: dS = P ((acc + delta) m - delta), m = mask / (1 - p).
@@ -146,7 +116,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnBwdParams p) {
     const int lane = tid & 63, wave = tid >> 6;
     const int hi = lane >> 5, l31 = lane & 31;
     int tile_, bh_;
-    ab_xcd_order((int)blockIdx.x, (p.Nq + 127) / 128, p.B * p.H, tile_, bh_);
+    xcd_tile_order((int)blockIdx.x, (p.Nq + 127) / 128, p.B * p.H, tile_, bh_);
     const int b = bh_ / p.H, h = bh_ - b * p.H;
     const int q0 = tile_ * 128 + wave * 32;
     int q = q0 + l31;
@@ -212,8 +182,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(AttnBwdParams p) {
 
     int r_off[4];
 #pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = bswz(l31, 2 * st + hi);
-    const unsigned lds0 = (unsigned)(size_t)(ab_lds_ptr_t)smem_all;
+    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
+    const unsigned lds0 = lds_addr(smem_all);
 
     const int nt = (p.Nk + 63) / 64;
     dma_tile(Kb, p.k_sn, 0, p.Nk, lds0, wave, lane);
@@ -296,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
     const int lane = tid & 63, wave = tid >> 6;
     const int hi = lane >> 5, l31 = lane & 31;
     int tile_, bh_;
-    ab_xcd_order((int)blockIdx.x, (p.Nk + 127) / 128, p.B * p.H, tile_, bh_);
+    xcd_tile_order((int)blockIdx.x, (p.Nk + 127) / 128, p.B * p.H, tile_, bh_);
     const int b = bh_ / p.H, h = bh_ - b * p.H;
     const int key0 = tile_ * 128 + wave * 32;
     int key = key0 + l31;
@@ -337,8 +307,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
 
     int r_off[4];
 #pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = bswz(l31, 2 * st + hi);
-    const unsigned lds0 = (unsigned)(size_t)(ab_lds_ptr_t)smem_all;
+    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
+    const unsigned lds0 = lds_addr(smem_all);
 
     const int nt = (p.Nq + 63) / 64;
     auto stage_aux = [&](int stage, int q0) {   // per-query scalars of the tile: plain loads, 64 threads

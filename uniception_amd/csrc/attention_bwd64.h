@@ -25,6 +25,7 @@
 // Key rows beyond Nk read as zeros and are not stored; waves wholly beyond Nk compute along (barriers) and store nothing.
 // Needs Nq > 64 (two query tiles: the lookahead of two tiles then stays inside the next item).
 #pragma once
+#include "mma_tile.h"
 #include "attention_p64.h"
 
 #define B64_TILE 8192
@@ -34,15 +35,15 @@
 #define B64_BOUNCE_OFF (B64_STAGE_OFF + 4 * 2 * B64_TILE)      // per wave: 8 KiB for the read-out (whole 128-byte rows per store)
 #define B64_LDS_BYTES (B64_BOUNCE_OFF + 4 * B64_TILE)           // 147 KiB: one workgroup per CU
 
-__device__ __forceinline__ void b64_mfma_acc_a(float16_t& d, p64_bf16x8_t a, p64_bf16x8_t b) {       // accumulator in an AGPR block
+__device__ __forceinline__ void b64_mfma_acc_a(float16_t& d, bf16x8_t a, bf16x8_t b) {       // accumulator in an AGPR block
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(d) : "v"(a), "v"(b));
 }
 // score chains: accumulator in VGPRs, the STATIONARY operand (K / V fragments) in accumulator registers (gfx90a+: an MFMA's A / B
 // operands may come from either file) — 64 VGPRs the vector work needs
-__device__ __forceinline__ void b64_mfma_first_b(float16_t& d, p64_bf16x8_t a, p64_bf16x8_t b, const float16_t& c) {
+__device__ __forceinline__ void b64_mfma_first_b(float16_t& d, bf16x8_t a, bf16x8_t b, const float16_t& c) {
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
 }
-__device__ __forceinline__ void b64_mfma_acc_b(float16_t& d, p64_bf16x8_t a, p64_bf16x8_t b) {
+__device__ __forceinline__ void b64_mfma_acc_b(float16_t& d, bf16x8_t a, bf16x8_t b) {
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
 }
 __device__ __forceinline__ float b64_mul(float a, float b) {
@@ -50,25 +51,15 @@ __device__ __forceinline__ float b64_mul(float a, float b) {
     asm volatile("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-typedef float b64_float2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ b64_float2_t b64_pk_mul(b64_float2_t a, b64_float2_t b) {
-    b64_float2_t r;
+__device__ __forceinline__ float2v_t b64_pk_mul(float2v_t a, float2v_t b) {
+    float2v_t r;
     asm volatile("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-// LDS-DMA pieces with M0 declared clobbered (one wave per SIMD: every instruction is four cycles of the wave's issue time, and the
-// save / restore pair of p64_dma16 is two of five)
-__device__ __forceinline__ void b64_dma16(unsigned voff, p64_uint4_t srd, unsigned soff, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" : : "v"(voff), "s"(srd), "s"(lds_byte_addr), "s"(soff) : "memory", "m0");
-}
-__device__ __forceinline__ void b64_dma4(unsigned voff, p64_uint4_t srd, unsigned soff, unsigned lds_byte_addr) {      // 64 lanes x 4 B
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dword %0, %1, %3 offen lds" : : "v"(voff), "s"(srd), "s"(lds_byte_addr), "s"(soff) : "memory", "m0");
-}
 // the two transposing reads of one transposed A operand (see tr_operand): addresses a0 / a1 are the lane's, `imm` the slab offset
 template <int IMM>
-__device__ __forceinline__ p64_bf16x8_t b64_tr(const char* a0, const char* a1) {
-    const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((ab_lds_v4_t)(ab_lds_ptr_t)(a0 + IMM));
-    const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((ab_lds_v4_t)(ab_lds_ptr_t)(a1 + IMM));
+__device__ __forceinline__ bf16x8_t b64_tr(const char* a0, const char* a1) {
+    const bf16x4_t lo = lds_read_tr16(a0 + IMM), hi = lds_read_tr16(a1 + IMM);
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
@@ -84,7 +75,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hi = lane >> 5, l31 = lane & 31;
-    const unsigned lds0 = (unsigned)(size_t)(ab_lds_ptr_t)smem;
+    const unsigned lds0 = lds_addr(smem);
     const int nt = (p.Nq + 63) >> 6;
 #ifdef B64_TIMING
     unsigned long long t_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_last = __builtin_amdgcn_s_memtime();
@@ -119,9 +110,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
     };
 
     // ---- the stream: per tile and wave 2 pieces of Q rows, 2 of dO rows (rows 16 w .. 16 w + 15), 1 of the scalars ----
-    const p64_uint4_t srd_q = p64_make_srd(p.Q, (unsigned)((((int64_t)p.B - 1) * p.q_sb + ((int64_t)p.H - 1) * p.q_sh + ((int64_t)p.Nq - 1) * p.q_sn + 64) * 2));
-    const p64_uint4_t srd_o = p64_make_srd(p.dO, (unsigned)((((int64_t)p.B - 1) * p.o_sb + ((int64_t)p.H - 1) * p.o_sh + ((int64_t)p.Nq - 1) * p.o_sn + 64) * 2));
-    const p64_uint4_t srd_a = p64_make_srd(p.aux, (unsigned)((int64_t)nbh * 2 * p.nq_pad * 4));
+    const uint4_t srd_q = make_srd(p.Q, (unsigned)((((int64_t)p.B - 1) * p.q_sb + ((int64_t)p.H - 1) * p.q_sh + ((int64_t)p.Nq - 1) * p.q_sn + 64) * 2));
+    const uint4_t srd_o = make_srd(p.dO, (unsigned)((((int64_t)p.B - 1) * p.o_sb + ((int64_t)p.H - 1) * p.o_sh + ((int64_t)p.Nq - 1) * p.o_sn + 64) * 2));
+    const uint4_t srd_a = make_srd(p.aux, (unsigned)((int64_t)nbh * 2 * p.nq_pad * 4));
     unsigned voff_q[2], voff_o[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -157,8 +148,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
     };
     // the wave's 64 K rows and 64 V rows of an item into its staging area (16 pieces of 8 rows; key rows >= Nk read as zeros)
     auto issue_stage = [&](const Item& it) {
-        const p64_uint4_t srd_k = p64_make_srd((const void*)it.kb, (unsigned)((((int64_t)p.Nk - 1) * p.k_sn + 64) * 2));
-        const p64_uint4_t srd_v = p64_make_srd((const void*)it.vb, (unsigned)((((int64_t)p.Nk - 1) * p.v_sn + 64) * 2));
+        const uint4_t srd_k = make_srd((const void*)it.kb, (unsigned)((((int64_t)p.Nk - 1) * p.k_sn + 64) * 2));
+        const uint4_t srd_v = make_srd((const void*)it.vb, (unsigned)((((int64_t)p.Nk - 1) * p.v_sn + 64) * 2));
         const unsigned dst = lds0 + (unsigned)(B64_STAGE_OFF + wave * 2 * B64_TILE);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -167,8 +158,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
             const unsigned vk = (unsigned)(((int64_t)rr * p.k_sn + cch * 8) * 2), vv = (unsigned)(((int64_t)rr * p.v_sn + cch * 8) * 2);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                p64_dma16(vk, srd_k, (unsigned)((int64_t)(it.key0 + 16 * k) * p.k_sn * 2), __builtin_amdgcn_readfirstlane(dst + k * 2048 + i * 1024));
-                p64_dma16(vv, srd_v, (unsigned)((int64_t)(it.key0 + 16 * k) * p.v_sn * 2), __builtin_amdgcn_readfirstlane(dst + B64_TILE + k * 2048 + i * 1024));
+                dma16_buf_to_lds(vk, srd_k, (unsigned)((int64_t)(it.key0 + 16 * k) * p.k_sn * 2), __builtin_amdgcn_readfirstlane(dst + k * 2048 + i * 1024));
+                dma16_buf_to_lds(vv, srd_v, (unsigned)((int64_t)(it.key0 + 16 * k) * p.v_sn * 2), __builtin_amdgcn_readfirstlane(dst + B64_TILE + k * 2048 + i * 1024));
             }
         }
     };
@@ -188,19 +179,19 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
         for (int i = 0; i < 2 * B64_TILE / 16 / 256; ++i) z[i * 256 + tid] = make_uint4(0u, 0u, 0u, 0u);
     }
 
-    p64_bf16x8_t kf[2][4], vf[2][4];       // stationary B operands: lane key = kb * 32 + l31, channels 16 st + 8 hi .. + 7; K carries scale * log2(e)
+    bf16x8_t kf[2][4], vf[2][4];       // stationary B operands: lane key = kb * 32 + l31, channels 16 st + 8 hi .. + 7; K carries scale * log2(e)
     float16_t dk[2][2], dv[2][2];          // [channel block db][key block kb], transposed: row = channel, column = key
     float16_t S[2], dP[2];                 // [key block]: rows = the block's 32 queries
-    p64_bf16x8_t P[2][2][2], dS[2][2][2];  // [generation][key block][16-query slab]
-    p64_bf16x8_t FA[8], F[4];              // row fragments of phase A, ring of transposed fragments of phase B (plans: the phases' comments)
+    bf16x8_t P[2][2][2], dS[2][2][2];  // [generation][key block][16-query slab]
+    bf16x8_t FA[8], F[4];              // row fragments of phase A, ring of transposed fragments of phase B (plans: the phases' comments)
     float16_t L, Dl;                       // the next block's start values
     float e0 = 0.f, e1 = 0.f;              // the exponentials in flight between an "exp" slot and the next ("fin") slot
-    b64_float2_t dd = {0.f, 0.f};          // ... and the pair's products, converted in the exponential slot after
+    float2v_t dd = {0.f, 0.f};          // ... and the pair's products, converted in the exponential slot after
 
     // lane addresses inside the ring (advanced with the slots): row fragments, transposed fragments, start values
     const char* ka[4];
 #pragma unroll
-    for (int st = 0; st < 4; ++st) ka[st] = smem + bswz(l31, 2 * st + hi);
+    for (int st = 0; st < 4; ++st) ka[st] = smem + tile_swz(l31, 2 * st + hi);
     const char* tr0[2];
     const char* tr1[2];
     {
@@ -234,12 +225,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
-                union { p64_bf16x8_t v; unsigned u[4]; } a;
-                a.v = *reinterpret_cast<const p64_bf16x8_t*>(sk + kb * 4096 + bswz(l31, 2 * st + hi));
+                union { bf16x8_t v; unsigned u[4]; } a;
+                a.v = *reinterpret_cast<const bf16x8_t*>(sk + kb * 4096 + tile_swz(l31, 2 * st + hi));
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) a.u[q4] = pack_bf16x2(__uint_as_float(a.u[q4] << 16) * c, __uint_as_float(a.u[q4] & 0xffff0000u) * c);
                 kf[kb][st] = a.v;
-                vf[kb][st] = *reinterpret_cast<const p64_bf16x8_t*>(sk + B64_TILE + kb * 4096 + bswz(l31, 2 * st + hi));
+                vf[kb][st] = *reinterpret_cast<const bf16x8_t*>(sk + B64_TILE + kb * 4096 + tile_swz(l31, 2 * st + hi));
             }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -249,14 +240,14 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
-                P[1][kb][hf] = (p64_bf16x8_t)(0.f);       // generation 1 = "block -1"
-                dS[1][kb][hf] = (p64_bf16x8_t)(0.f);
+                P[1][kb][hf] = (bf16x8_t)(0.f);       // generation 1 = "block -1"
+                dS[1][kb][hf] = (bf16x8_t)(0.f);
             }
         // the item's first phase A finishes "block -1"'s softmax (pairs 11..15, key block 1): exp2(-1e30) = 0, 0 * 0 = 0
 #pragma unroll
         for (int r = 0; r < 16; ++r) { S[1][r] = -1e30f; dP[1][r] = 0.f; }
         e0 = 0.f; e1 = 0.f;
-        dd = (b64_float2_t){0.f, 0.f};
+        dd = (float2v_t){0.f, 0.f};
     };
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -266,12 +257,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
     // block 0's start values and first fragments
     init_quad(cad, P64Int<0>()); init_quad(cad, P64Int<1>()); init_quad(cad, P64Int<2>()); init_quad(cad, P64Int<3>());
     init_quad(cad, P64Int<4>()); init_quad(cad, P64Int<5>()); init_quad(cad, P64Int<6>()); init_quad(cad, P64Int<7>());
-    FA[0] = *reinterpret_cast<const p64_bf16x8_t*>(ka[0]);
-    FA[1] = *reinterpret_cast<const p64_bf16x8_t*>(ka[0] + B64_TILE);
-    FA[2] = *reinterpret_cast<const p64_bf16x8_t*>(ka[1]);
-    FA[3] = *reinterpret_cast<const p64_bf16x8_t*>(ka[1] + B64_TILE);
-    FA[4] = *reinterpret_cast<const p64_bf16x8_t*>(ka[2]);
-    FA[5] = *reinterpret_cast<const p64_bf16x8_t*>(ka[2] + B64_TILE);
+    FA[0] = *reinterpret_cast<const bf16x8_t*>(ka[0]);
+    FA[1] = *reinterpret_cast<const bf16x8_t*>(ka[0] + B64_TILE);
+    FA[2] = *reinterpret_cast<const bf16x8_t*>(ka[1]);
+    FA[3] = *reinterpret_cast<const bf16x8_t*>(ka[1] + B64_TILE);
+    FA[4] = *reinterpret_cast<const bf16x8_t*>(ka[2]);
+    FA[5] = *reinterpret_cast<const bf16x8_t*>(ka[2] + B64_TILE);
 
     // The schedule of one 32-query block j (slots g = 0 .. 39 counted from its phase A; one MFMA per slot):
     //   phase A, g = 0..15   g < 8: S[0] / dP[0] (key block 0: even / odd slots, chunk pair st = g >> 1), g >= 8: S[1] / dP[1]; the chains' first
@@ -299,7 +290,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
 #endif
     auto sm_cvt_ds = [&](auto qp_tag, auto gen_tag) __attribute__((always_inline)) {
         constexpr int qp = decltype(qp_tag)::value, kbp = qp >> 3, ip = qp & 7, G = decltype(gen_tag)::value;
-        union { p64_bf16x8_t v; unsigned u[4]; } d;
+        union { bf16x8_t v; unsigned u[4]; } d;
         d.v = dS[G][kbp][ip >> 2];
         d.u[ip & 3] = p64_cvt_pk(dd.x, dd.y);
         dS[G][kbp][ip >> 2] = d.v;
@@ -315,9 +306,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
     auto sm_fin = [&](auto q_tag, auto gen_tag) __attribute__((always_inline)) {
         constexpr int q = decltype(q_tag)::value, kb = q >> 3, i = q & 7, G = decltype(gen_tag)::value;
         if constexpr (B64_DBG & 1) return;
-        if constexpr (B64_PKMUL) dd = b64_pk_mul((b64_float2_t){e0, e1}, (b64_float2_t){dP[kb][2 * i], dP[kb][2 * i + 1]});
+        if constexpr (B64_PKMUL) dd = b64_pk_mul((float2v_t){e0, e1}, (float2v_t){dP[kb][2 * i], dP[kb][2 * i + 1]});
         else { dd.x = b64_mul(e0, dP[kb][2 * i]); dd.y = b64_mul(e1, dP[kb][2 * i + 1]); }
-        union { p64_bf16x8_t v; unsigned u[4]; } a;
+        union { bf16x8_t v; unsigned u[4]; } a;
         a.v = P[G][kb][i >> 2];
         a.u[i & 3] = p64_cvt_pk(e0, e1);
         P[G][kb][i >> 2] = a.v;
@@ -330,7 +321,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
         constexpr int qb = decltype(qb_tag)::value, pq = qb ^ 1;       // pq: the previous block's position in ITS tile (which tr0 / tr1 point at)
         auto slot = [&](auto k_tag) __attribute__((always_inline)) {
             constexpr int k = decltype(k_tag)::value, st = (k & 7) >> 1, kb = k >> 3;
-            if constexpr (!(B64_DBG & 8) && k < 2) FA[6 + k] = *reinterpret_cast<const p64_bf16x8_t*>(ka[3] + qb * 4096 + (k & 1) * B64_TILE);
+            if constexpr (!(B64_DBG & 8) && k < 2) FA[6 + k] = *reinterpret_cast<const bf16x8_t*>(ka[3] + qb * 4096 + (k & 1) * B64_TILE);
             if constexpr (!(B64_DBG & 4) && k == 12) F[0] = b64_tr<B64_TILE + 4096 * pq>(tr0[0], tr1[0]);          // b0: dO^T, slab 2 pq, channel block 0
             if constexpr (!(B64_DBG & 4) && k == 13) F[1] = b64_tr<4096 * pq>(tr0[0], tr1[0]);                     // b1: Q^T,  slab 2 pq, channel block 0
             if constexpr (!(B64_DBG & 4) && k == 15) F[2] = b64_tr<B64_TILE + 4096 * pq>(tr0[1], tr1[1]);          // b2: dO^T, slab 2 pq, channel block 1
@@ -380,7 +371,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
             if constexpr (!(B64_DBG & 4) && k == 4) F[1] = b64_tr<4096 * pq + 2048>(tr0[0], tr1[0]);                   // b5: Q^T
             if constexpr (!(B64_DBG & 4) && k == 6) F[2] = b64_tr<B64_TILE + 4096 * pq + 2048>(tr0[1], tr1[1]);        // b6: dO^T slab 2 pq + 1, channel block 1
             if constexpr (!(B64_DBG & 4) && k == 8) F[3] = b64_tr<4096 * pq + 2048>(tr0[1], tr1[1]);                   // b7: Q^T
-            if constexpr (!(B64_DBG & 8) && k >= 10) FA[k - 10] = *reinterpret_cast<const p64_bf16x8_t*>(ka[(k - 10) >> 1] + nb_rows + ((k - 10) & 1) * B64_TILE);
+            if constexpr (!(B64_DBG & 8) && k >= 10) FA[k - 10] = *reinterpret_cast<const bf16x8_t*>(ka[(k - 10) >> 1] + nb_rows + ((k - 10) & 1) * B64_TILE);
             if constexpr (c == 0) b64_mfma_acc_a(dv[db][0], F[(2 * pp) & 3], P[GR][0][hf]);
             else if constexpr (c == 1) b64_mfma_acc_a(dv[db][1], F[(2 * pp) & 3], P[GR][1][hf]);
             else if constexpr (c == 2) b64_mfma_acc_a(dk[db][0], F[(2 * pp + 1) & 3], dS[GR][0][hf]);
@@ -454,8 +445,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
         for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
-                const p64_bf16x8_t ta = hf ? b64_tr<B64_TILE + 4096 + 2048>(tr0[db], tr1[db]) : b64_tr<B64_TILE + 4096>(tr0[db], tr1[db]);
-                const p64_bf16x8_t tq = hf ? b64_tr<4096 + 2048>(tr0[db], tr1[db]) : b64_tr<4096>(tr0[db], tr1[db]);
+                const bf16x8_t ta = hf ? b64_tr<B64_TILE + 4096 + 2048>(tr0[db], tr1[db]) : b64_tr<B64_TILE + 4096>(tr0[db], tr1[db]);
+                const bf16x8_t tq = hf ? b64_tr<4096 + 2048>(tr0[db], tr1[db]) : b64_tr<4096>(tr0[db], tr1[db]);
                 b64_mfma_acc_a(dv[db][0], ta, P[1][0][hf]);
                 b64_mfma_acc_a(dv[db][1], ta, P[1][1][hf]);
                 b64_mfma_acc_a(dk[db][0], tq, dS[1][0][hf]);
@@ -507,8 +498,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv64_kernel(AttnBwdParams p)
                 const unsigned o8 = (unsigned)(8 * sn * 2);
 #pragma unroll
                 for (int ps = 0; ps < 8; ++ps) {
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                    const u32x4 d = {rw[ps].x, rw[ps].y, rw[ps].z, rw[ps].w};
+                    const uint4_t d = {rw[ps].x, rw[ps].y, rw[ps].z, rw[ps].w};
                     __builtin_amdgcn_raw_buffer_store_b128(d, rsrc, (int)vo, (int)(ps * o8), 0);
                 }
             }
@@ -564,7 +554,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hi = lane >> 5, l31 = lane & 31;
-    const unsigned lds0 = (unsigned)(size_t)(ab_lds_ptr_t)smem;
+    const unsigned lds0 = lds_addr(smem);
     const int nt = (p.Nk + 63) >> 6;
 
     const int g = blockIdx.x, xcd = g & 7, slot_w = g >> 3, nslots = (int)(gridDim.x >> 3);
@@ -588,7 +578,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
 
     // ---- the stream: per tile and wave 2 pieces of K rows, 2 of V rows (rows 16 w .. 16 w + 15) ----
     const unsigned kbytes = (unsigned)((((int64_t)p.Nk - 1) * p.k_sn + 64) * 2);        // key rows >= Nk read as zeros
-    const p64_uint4_t srd_v = p64_make_srd(p.V, (unsigned)((((int64_t)p.B - 1) * p.v_sb + ((int64_t)p.H - 1) * p.v_sh + ((int64_t)p.Nk - 1) * p.v_sn + 64) * 2));
+    const uint4_t srd_v = make_srd(p.V, (unsigned)((((int64_t)p.B - 1) * p.v_sb + ((int64_t)p.H - 1) * p.v_sh + ((int64_t)p.Nk - 1) * p.v_sn + 64) * 2));
     unsigned voff_k[2], voff_v[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -599,10 +589,10 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
     }
     const unsigned kstep = (unsigned)(64 * p.k_sn * 2), vstep = (unsigned)(64 * p.v_sn * 2);
     const unsigned k16 = (unsigned)(16 * p.k_sn * 2) * (unsigned)wave, v16 = (unsigned)(16 * p.v_sn * 2) * (unsigned)wave;
-    struct Pieces { p64_uint4_t srd_k; unsigned so_k, so_v, dst; };
+    struct Pieces { uint4_t srd_k; unsigned so_k, so_v, dst; };
     auto prep = [&](const Item& it, int t, int s) -> Pieces {
         Pieces pc;
-        pc.srd_k = p64_make_srd((const void*)it.kb, kbytes);
+        pc.srd_k = make_srd((const void*)it.kb, kbytes);
         pc.so_k = __builtin_amdgcn_readfirstlane((unsigned)t * kstep + k16);
         pc.so_v = __builtin_amdgcn_readfirstlane(it.ov + (unsigned)t * vstep + v16);
         pc.dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(s * D64_SLOT) + (unsigned)wave * 2048u);
@@ -625,10 +615,10 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
         const bf16_t* gb = p.dO + (int64_t)it.b * p.o_sb + (int64_t)it.h * p.o_sh + (int64_t)it.q0 * p.o_sn;
         const bf16_t* ob = p.O + (int64_t)it.b * p.o_sb + (int64_t)it.h * p.o_sh + (int64_t)it.q0 * p.o_sn;
         const float* lb = p.LSE + ((int64_t)it.b * p.H + it.h) * p.Nq + it.q0;
-        const p64_uint4_t srd_q = p64_make_srd(qb, rows > 0 ? (unsigned)(((rows - 1) * p.q_sn + 64) * 2) : 0u);
-        const p64_uint4_t srd_g = p64_make_srd(gb, rows > 0 ? (unsigned)(((rows - 1) * p.o_sn + 64) * 2) : 0u);
-        const p64_uint4_t srd_o = p64_make_srd(ob, rows > 0 ? (unsigned)(((rows - 1) * p.o_sn + 64) * 2) : 0u);
-        const p64_uint4_t srd_l = p64_make_srd(lb, rows > 0 ? (unsigned)(rows * 4) : 0u);
+        const uint4_t srd_q = make_srd(qb, rows > 0 ? (unsigned)(((rows - 1) * p.q_sn + 64) * 2) : 0u);
+        const uint4_t srd_g = make_srd(gb, rows > 0 ? (unsigned)(((rows - 1) * p.o_sn + 64) * 2) : 0u);
+        const uint4_t srd_o = make_srd(ob, rows > 0 ? (unsigned)(((rows - 1) * p.o_sn + 64) * 2) : 0u);
+        const uint4_t srd_l = make_srd(lb, rows > 0 ? (unsigned)(rows * 4) : 0u);
         const unsigned dst = lds0 + (unsigned)(D64_STAGE_OFF + wave * D64_STAGE_W);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -637,9 +627,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
             const unsigned vq = (unsigned)(((int64_t)rr * p.q_sn + cch * 8) * 2), vo = (unsigned)(((int64_t)rr * p.o_sn + cch * 8) * 2);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                p64_dma16(vq, srd_q, (unsigned)((int64_t)(16 * k) * p.q_sn * 2), __builtin_amdgcn_readfirstlane(dst + k * 2048 + i * 1024));
-                p64_dma16(vo, srd_g, (unsigned)((int64_t)(16 * k) * p.o_sn * 2), __builtin_amdgcn_readfirstlane(dst + B64_TILE + k * 2048 + i * 1024));
-                p64_dma16(vo, srd_o, (unsigned)((int64_t)(16 * k) * p.o_sn * 2), __builtin_amdgcn_readfirstlane(dst + 2 * B64_TILE + k * 2048 + i * 1024));
+                dma16_buf_to_lds(vq, srd_q, (unsigned)((int64_t)(16 * k) * p.q_sn * 2), __builtin_amdgcn_readfirstlane(dst + k * 2048 + i * 1024));
+                dma16_buf_to_lds(vo, srd_g, (unsigned)((int64_t)(16 * k) * p.o_sn * 2), __builtin_amdgcn_readfirstlane(dst + B64_TILE + k * 2048 + i * 1024));
+                dma16_buf_to_lds(vo, srd_o, (unsigned)((int64_t)(16 * k) * p.o_sn * 2), __builtin_amdgcn_readfirstlane(dst + 2 * B64_TILE + k * 2048 + i * 1024));
             }
         }
         b64_dma4((unsigned)lane * 4u, srd_l, 0u, __builtin_amdgcn_readfirstlane(dst + 3 * B64_TILE));
@@ -659,17 +649,17 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
         for (int i = 0; i < B64_TILE / 16 / 256; ++i) z[i * 256 + tid] = make_uint4(0u, 0u, 0u, 0u);
     }
 
-    p64_bf16x8_t qf[2][4], dof[2][4];      // stationary B operands: lane query = qb * 32 + l31, channels 16 st + 8 hi .. + 7; Q carries scale * log2(e)
+    bf16x8_t qf[2][4], dof[2][4];      // stationary B operands: lane query = qb * 32 + l31, channels 16 st + 8 hi .. + 7; Q carries scale * log2(e)
     float16_t dq[2][2];                    // [channel block db][query block qb], transposed: row = channel, column = query
     float16_t S[2], dP[2];                 // [query block]: rows = the granule's 32 keys, column = the lane's query
     float16_t neg_lse[2], neg_dlt[2];      // the chains' start values: the lane's scalars, 16 times
-    p64_bf16x8_t dS[2][2][2];              // [generation][query block][16-key slab]
-    p64_bf16x8_t FA[8], F[4];
+    bf16x8_t dS[2][2][2];              // [generation][query block][16-key slab]
+    bf16x8_t FA[8], F[4];
     float e0 = 0.f, e1 = 0.f, d0 = 0.f, d1 = 0.f;
 
     const char* ka[4];
 #pragma unroll
-    for (int st = 0; st < 4; ++st) ka[st] = smem + bswz(l31, 2 * st + hi);
+    for (int st = 0; st < 4; ++st) ka[st] = smem + tile_swz(l31, 2 * st + hi);
     const char* tr0[2];
     const char* tr1[2];
     {
@@ -694,13 +684,13 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
             float dlt = 0.f;
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
-                union { p64_bf16x8_t v; unsigned u[4]; } a;
-                a.v = *reinterpret_cast<const p64_bf16x8_t*>(sq + qb * 4096 + bswz(l31, 2 * st + hi));
+                union { bf16x8_t v; unsigned u[4]; } a;
+                a.v = *reinterpret_cast<const bf16x8_t*>(sq + qb * 4096 + tile_swz(l31, 2 * st + hi));
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) a.u[q4] = pack_bf16x2(__uint_as_float(a.u[q4] << 16) * c, __uint_as_float(a.u[q4] & 0xffff0000u) * c);
                 qf[qb][st] = a.v;
-                const p64_bf16x8_t gf = *reinterpret_cast<const p64_bf16x8_t*>(sq + B64_TILE + qb * 4096 + bswz(l31, 2 * st + hi));
-                const p64_bf16x8_t of = *reinterpret_cast<const p64_bf16x8_t*>(sq + 2 * B64_TILE + qb * 4096 + bswz(l31, 2 * st + hi));
+                const bf16x8_t gf = *reinterpret_cast<const bf16x8_t*>(sq + B64_TILE + qb * 4096 + tile_swz(l31, 2 * st + hi));
+                const bf16x8_t of = *reinterpret_cast<const bf16x8_t*>(sq + 2 * B64_TILE + qb * 4096 + tile_swz(l31, 2 * st + hi));
                 dof[qb][st] = gf;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) dlt = fmaf((float)of[e], (float)gf[e], dlt);
@@ -726,7 +716,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
-            for (int hf = 0; hf < 2; ++hf) dS[1][qb][hf] = (p64_bf16x8_t)(0.f);       // generation 1 = "granule -1"
+            for (int hf = 0; hf < 2; ++hf) dS[1][qb][hf] = (bf16x8_t)(0.f);       // generation 1 = "granule -1"
         // the item's first phase A finishes "granule -1"'s softmax (pairs 13..15, query block 1): exp2(-1e30) = 0, 0 * 0 = 0
 #pragma unroll
         for (int r = 0; r < 16; ++r) { S[1][r] = -1e30f; dP[1][r] = 0.f; }
@@ -741,7 +731,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
         issue_stage(nxt);
     }
 #pragma unroll
-    for (int m = 0; m < 8; ++m) FA[m] = *reinterpret_cast<const p64_bf16x8_t*>(ka[m >> 1] + (m & 1) * B64_TILE);
+    for (int m = 0; m < 8; ++m) FA[m] = *reinterpret_cast<const bf16x8_t*>(ka[m >> 1] + (m & 1) * B64_TILE);
 
     // softmax pair q of a granule: query block q >> 3, accumulator rows 2 (q & 7), + 1 (keys).  A slot runs, in this order, the conversion of
     // pair C's products (computed a slot earlier), the products of pair F (exponentials a slot earlier), the exponentials of pair E.
@@ -749,7 +739,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
         constexpr int C = decltype(c_tag)::value, Fq = decltype(f_tag)::value, E = decltype(e_tag)::value, G = decltype(gen_tag)::value;
         if constexpr (B64_DBG & 1) return;
         if constexpr (C >= 0) {
-            union { p64_bf16x8_t v; unsigned u[4]; } d;
+            union { bf16x8_t v; unsigned u[4]; } d;
             d.v = dS[G][C >> 3][(C & 7) >> 2];
             d.u[C & 3] = p64_cvt_pk(d0, d1);
             dS[G][C >> 3][(C & 7) >> 2] = d.v;
@@ -808,7 +798,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
         auto slot = [&](auto k_tag) __attribute__((always_inline)) {
             constexpr int k = decltype(k_tag)::value, pp = k >> 1, hf = pp >> 1, db = pp & 1, qb = k & 1;
             if constexpr (!(B64_DBG & 4) && k == 1) F[3] = b64_tr<4096 * pq + 2048>(tr0[1], tr1[1]);      // slab 2 pq + 1, channel block 1
-            if constexpr (!(B64_DBG & 8)) FA[k] = *reinterpret_cast<const p64_bf16x8_t*>(ka[k >> 1] + nb_rows + (k & 1) * B64_TILE);
+            if constexpr (!(B64_DBG & 8)) FA[k] = *reinterpret_cast<const bf16x8_t*>(ka[k >> 1] + nb_rows + (k & 1) * B64_TILE);
             b64_mfma_acc_a(dq[db][qb], F[pp], dS[GR][qb][hf]);
             if constexpr (k == 0) sm(P64Int<5>(), P64Int<6>(), P64Int<7>(), P64Int<kb>());
             if constexpr (k == 1) sm(P64Int<6>(), P64Int<7>(), N_(), P64Int<kb>());
@@ -856,7 +846,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
         for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
-                const p64_bf16x8_t tk = hf ? b64_tr<4096 + 2048>(tr0[db], tr1[db]) : b64_tr<4096>(tr0[db], tr1[db]);
+                const bf16x8_t tk = hf ? b64_tr<4096 + 2048>(tr0[db], tr1[db]) : b64_tr<4096>(tr0[db], tr1[db]);
                 b64_mfma_acc_a(dq[db][0], tk, dS[1][0][hf]);
                 b64_mfma_acc_a(dq[db][1], tk, dS[1][1][hf]);
             }
@@ -917,8 +907,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(AttnBwdParams p) 
             const unsigned o8 = (unsigned)(8 * p.dq_sn * 2);
 #pragma unroll
             for (int ps = 0; ps < 8; ++ps) {
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 d = {rw[ps].x, rw[ps].y, rw[ps].z, rw[ps].w};
+                const uint4_t d = {rw[ps].x, rw[ps].y, rw[ps].z, rw[ps].w};
                 __builtin_amdgcn_raw_buffer_store_b128(d, rsrc, (int)vo, (int)(ps * o8), 0);
             }
         }

@@ -10,9 +10,7 @@
 // pair (lane, lane ^ 32) holds the 64 channels of one query in both accumulators, so the combine + RMSNorm epilogue needs one
 // cross-lane add.  Registers: 4 x 16 accumulators + 2 x 32 scores + 2 x 16 packed probabilities + 16 Q fragment + 16 staging.
 // fp32 kernel (diff_attn_f32_kernel): one thread per query in the style of attn_f32_kernel, 32-key tiles of K1, K2 and V in LDS.
-#include "common.h"
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+#include "mma_tile.h"
 
 struct DiffParams {
     const void* Q;
@@ -32,14 +30,6 @@ struct DiffParams {
 
 #define DKV_TILE 64
 #define DTILE_BYTES (DKV_TILE * 128)
-
-__device__ __forceinline__ int dswz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-// key offset inside a 16-key group for VT position pp (inverse of uc_vt_perm, include/uc_hip.h)
-__device__ __forceinline__ int dvt_key_of_pos(int pp) {
-    const int hi = pp >> 3, j = pp & 7;
-    return (j & 3) + 8 * (j >> 2) + 4 * hi;
-}
 
 // one online-softmax step of a lane pair's query over the 64 scores s[2][16] (keys k0 + 32 kb + (r&3) + 8 (r>>2) + 4 hi):
 // updates (m_run, l_run), rescales o[2] when a maximum of the wave grew, returns the packed probabilities
@@ -139,7 +129,7 @@ __global__ __launch_bounds__(256) void diff_attn_bf16_kernel(DiffParams p) {
             unsigned m[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                if (gbase + dvt_key_of_pos(pbase + j) >= p.Nk) m[j >> 1] &= (j & 1) ? 0x0000ffffu : 0xffff0000u;
+                if (gbase + vt_key_of_pos(pbase + j) >= p.Nk) m[j >> 1] &= (j & 1) ? 0x0000ffffu : 0xffff0000u;
             v.x &= m[0]; v.y &= m[1]; v.z &= m[2]; v.w &= m[3];
         }
         return v;
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(256) void diff_attn_bf16_kernel(DiffParams p) {
         rv0 = load_v((k0_), sr);            \
         rv1 = load_v((k0_), sr + 32);       \
     } while (0)
-    const int w_off = dswz(sr, cc);   // rows r and r + 32 share the swizzle key
+    const int w_off = tile_swz(sr, cc);   // rows r and r + 32 share the swizzle key
 #define DIFF_STAGE_WRITE(buf_)                                                 \
     do {                                                                       \
         char* sk_ = smem + (buf_) * 2 * DTILE_BYTES + w_off;                   \
@@ -162,7 +152,7 @@ __global__ __launch_bounds__(256) void diff_attn_bf16_kernel(DiffParams p) {
     } while (0)
     int r_off[4];   // row l31 (+ 32 via immediate), chunk 2 st + hi: K tile st 0, 1 = K1, st 2, 3 = K2; VT tile: 16-key slab st
 #pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = dswz(l31, 2 * st + hi);
+    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
 
     float16_t o1[2], o2[2];   // O^T accumulators: channel d = 32 db + (r&3) + 8 (r>>2) + 4 hi, query l31
     o1[0] = o1[1] = o2[0] = o2[1] = (float16_t)(0.f);

@@ -14,7 +14,7 @@
 //     32*kb + (r&3) + 8*(r>>2) + 4*hh.  Pad positions are zero, so tail tiles need no masking of V.
 // Operand layout of the instruction (probed, tools/probes/f8_layout.hip): byte e of lane l is A[row = l&31][k] resp.
 // B[k][col = l&31] with ANY k assignment shared by A and B across the two lane halves; C/D as every 32x32 MFMA.
-#include "common.h"
+#include "mma_tile.h"
 
 typedef int v8i_t __attribute__((ext_vector_type(8)));
 
@@ -56,16 +56,10 @@ __global__ __launch_bounds__(256) void attn_fp8_kernel(AttnF8Params p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int hi = lane >> 5, l31 = lane & 31;
-    // 1-D grid; query tiles of one (batch, head) get ids that differ by multiples of 8 = one XCD's L2 (see attn_bf16_dma_kernel)
+    // 1-D grid; query tiles of one (batch, head) meet in one XCD's L2 (xcd_tile_order)
     const int nq = (p.Nq + 127) / 128, nbh = p.B * p.H;
     int qt, bh;
-    {
-        const int w = blockIdx.x;
-        const int per_group = 8 * nq;
-        const int grp = w / per_group, within = w - grp * per_group;
-        if ((grp + 1) * 8 <= nbh) { bh = grp * 8 + (within & 7); qt = within >> 3; }
-        else { const int rem = w - (nbh / 8) * 8 * nq; bh = (nbh / 8) * 8 + rem / nq; qt = rem % nq; }
-    }
+    xcd_tile_order((int)blockIdx.x, nq, nbh, qt, bh);
     const int b = bh / p.H, h = bh - b * p.H;
     const int q0 = qt * 128 + wave * 32;
 
@@ -220,25 +214,6 @@ __global__ __launch_bounds__(256) void attn_fp8_kernel(AttnF8Params p) {
 // kernel above converts every K tile once per query tile, 8x redundantly at N = 1024), Nk % 64 == 0, outputs through an
 // LDS bounce into whole-row stores, XCD-aware workgroup order.
 // ---------------------------------------------------------------------------------------
-typedef unsigned f8_uint4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void f8_dma16(unsigned voff, f8_uint4_t srd, unsigned soff, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 4\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(lds_byte_addr), "s"(soff)
-        : "memory");
-}
-__device__ __forceinline__ f8_uint4_t f8_make_srd(const void* base) {
-    const unsigned long long pa = (unsigned long long)base;
-    return (f8_uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pa),
-                        (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pa >> 32) & 0xffffu)), 0xffffff00u, 0x00020000u};
-}
-
 struct AttnF8DmaParams {
     const bf16_t* Q;
     const unsigned char* K8;
@@ -257,20 +232,14 @@ __global__ __launch_bounds__(256, 4) void attn_fp8_dma_kernel(AttnF8DmaParams p)
     const int hi = lane >> 5, l31 = lane & 31;
     const int nq = (p.Nq + 127) / 128, nbh = p.B * p.H;
     int qt, bh;
-    {
-        const int w = blockIdx.x;
-        const int per_group = 8 * nq;
-        const int grp = w / per_group, within = w - grp * per_group;
-        if ((grp + 1) * 8 <= nbh) { bh = grp * 8 + (within & 7); qt = within >> 3; }
-        else { const int rem = w - (nbh / 8) * 8 * nq; bh = (nbh / 8) * 8 + rem / nq; qt = rem % nq; }
-    }
+    xcd_tile_order((int)blockIdx.x, nq, nbh, qt, bh);
     const int b = bh / p.H, h = bh - b * p.H;
     const int q0 = qt * 128 + wave * 32;
     const bf16_t* Qb = p.Q + (int64_t)b * p.q_sb + (int64_t)h * p.q_sh;
 
     // ---- DMA assignment: a 64x64-byte tile is 4 instructions of 16 rows; waves 0,1 carry the K8 tile, waves 2,3 the VT8 tile ----
     const bool is_v = wave >= 2;
-    const f8_uint4_t srd = is_v ? f8_make_srd(p.VT8 + (int64_t)bh * 64 * (int64_t)p.npad) : f8_make_srd(p.K8 + (int64_t)bh * (int64_t)p.npad * 64);
+    const uint4_t srd = is_v ? make_srd(p.VT8 + (int64_t)bh * 64 * (int64_t)p.npad) : make_srd(p.K8 + (int64_t)bh * (int64_t)p.npad * 64);
     unsigned voff[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -279,11 +248,11 @@ __global__ __launch_bounds__(256, 4) void attn_fp8_dma_kernel(AttnF8DmaParams p)
         voff[i] = is_v ? (unsigned)(row * p.npad + cch * 16) : (unsigned)(row * 64 + cch * 16);
     }
     const unsigned tstep = is_v ? 64u : 4096u;                    // bytes between key tiles
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)smem;
+    const unsigned lds0 = lds_addr(smem);
     auto issue_tile = [&](int t, int buf) {
         const unsigned dst = lds0 + (unsigned)(buf * 2 * F8_TILE + (is_v ? F8_TILE : 0) + (wave & 1) * 2048);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) f8_dma16(voff[i], srd, (unsigned)t * tstep, __builtin_amdgcn_readfirstlane(dst + i * 1024));
+        for (int i = 0; i < 2; ++i) dma16_buf_to_lds(voff[i], srd, (unsigned)t * tstep, __builtin_amdgcn_readfirstlane(dst + i * 1024));
     };
     issue_tile(0, 0);
 

@@ -31,10 +31,7 @@
 // Layouts are attention.hip's: Q, K [B, N, H, 64] bf16 by strides; V in the packed VT layout ([B, H, 64, npad], key order
 // permuted inside 16-key groups, pads zero); S^T = K Q^T (swapped product) so that a query's scores sit in one lane pair.
 #pragma once
-#include "common.h"
-
-typedef __bf16 p64_bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned p64_uint4_t __attribute__((ext_vector_type(4)));
+#include "mma_tile.h"
 
 struct AttnP64Params {
     const void* Q;
@@ -59,27 +56,6 @@ struct AttnP64Params {
 #define P64_Q_OFF (2 * P64_RING * P64_TILE)             // 4 waves x 8 KiB of Q rows (next item)
 #define P64_LDS_BYTES (P64_Q_OFF + 4 * P64_TILE)        // 80 KiB: two workgroups per CU
 
-__device__ __forceinline__ int p64_swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ void p64_dma16(unsigned voff, p64_uint4_t srd, unsigned soff, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 4\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(lds_byte_addr), "s"(soff)
-        : "memory");
-}
-__device__ __forceinline__ p64_uint4_t p64_make_srd(const void* base, unsigned bytes) {
-    const unsigned long long pa = (unsigned long long)base;
-    return (p64_uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pa),
-                         (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pa >> 32) & 0xffffu)),
-                         (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-
 struct P64TagF { static constexpr bool value = false; };
 struct P64TagT { static constexpr bool value = true; };
 template <int I> struct P64Int { static constexpr int value = I; };
@@ -95,13 +71,13 @@ template <int I> struct P64Int { static constexpr int value = I; };
 // iteration.  What hipcc does not do for asm MFMAs (cdna_hip_programming.md 5.7): wait states between the last MFMA of a chain
 // and the first VALU access to its result — the main loop places 8 PV MFMAs (>= 256 cycles) between them by construction, the
 // other sites carry p64_mfma_settle().
-__device__ __forceinline__ void p64_mfma_first(float16_t& d, p64_bf16x8_t a, p64_bf16x8_t b, const float16_t& c) {
+__device__ __forceinline__ void p64_mfma_first(float16_t& d, bf16x8_t a, bf16x8_t b, const float16_t& c) {
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
 }
-__device__ __forceinline__ void p64_mfma_first0(float16_t& d, p64_bf16x8_t a, p64_bf16x8_t b) {       // C = 0: no zeroing pass
+__device__ __forceinline__ void p64_mfma_first0(float16_t& d, bf16x8_t a, bf16x8_t b) {       // C = 0: no zeroing pass
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));
 }
-__device__ __forceinline__ void p64_mfma_acc(float16_t& d, p64_bf16x8_t a, p64_bf16x8_t b) {
+__device__ __forceinline__ void p64_mfma_acc(float16_t& d, bf16x8_t a, bf16x8_t b) {
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
 }
 // pinned single-instruction vector helpers of the hand-placed regions
@@ -151,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
         asm volatile("" : "+v"(l));
         return l;
     };
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)smem;
+    const unsigned lds0 = lds_addr(smem);
 
     // ---- this workgroup's item list: XCD x = g % 8 owns the (batch, head) pairs bh = 8 k + x; its items j = k * nq + qt are dealt
     //      round-robin to the XCD's workgroups ----
@@ -191,12 +167,12 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
     };
     // the four DMA pieces of one iteration's tiles (K tile tk, VT tile tv of an item into ring slot s): wave w carries pieces 2w, 2w+1
     // of each tile (rows 16w .. 16w+15).  Prepared as scalars at the head of an iteration, issued one per slot inside the regions.
-    struct Pieces { p64_uint4_t srd_k, srd_v; unsigned so_k, so_v, dst_k, dst_v; };
+    struct Pieces { uint4_t srd_k, srd_v; unsigned so_k, so_v, dst_k, dst_v; };
     auto prep = [&](const Item& it, int i, int s) -> Pieces {       // iteration i of an item reads K(i + 1) (i <= nt - 2) and VT(i) (i >= 0)
         Pieces pc;
         const int tk = i + 1 <= nt - 1 ? i + 1 : 0, tv = i >= 0 ? i : 0;     // (dummy tiles keep the piece count per iteration at four)
-        pc.srd_k = p64_make_srd((const void*)it.kb, kbytes);
-        pc.srd_v = p64_make_srd((const void*)it.vb, vbytes);
+        pc.srd_k = make_srd((const void*)it.kb, kbytes);
+        pc.srd_v = make_srd((const void*)it.vb, vbytes);
         pc.so_k = (unsigned)tk * kstep + (unsigned)wave * k16;
         pc.so_v = (unsigned)tv * 128u + (unsigned)wave * v16;
         pc.dst_k = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(P64_K_OFF + s * P64_TILE + wave * 2048));
@@ -205,23 +181,23 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
     };
     auto issue_piece = [&](const Pieces& pc, auto n_tag) __attribute__((always_inline)) {
         constexpr int n = decltype(n_tag)::value;
-        if constexpr (n == 0) p64_dma16(voff_k[0], pc.srd_k, pc.so_k, pc.dst_k);
-        else if constexpr (n == 1) p64_dma16(voff_k[1], pc.srd_k, pc.so_k, pc.dst_k + 1024);
-        else if constexpr (n == 2) p64_dma16(voff_v[0], pc.srd_v, pc.so_v, pc.dst_v);
-        else p64_dma16(voff_v[1], pc.srd_v, pc.so_v, pc.dst_v + 1024);
+        if constexpr (n == 0) dma16_buf_to_lds(voff_k[0], pc.srd_k, pc.so_k, pc.dst_k);
+        else if constexpr (n == 1) dma16_buf_to_lds(voff_k[1], pc.srd_k, pc.so_k, pc.dst_k + 1024);
+        else if constexpr (n == 2) dma16_buf_to_lds(voff_v[0], pc.srd_v, pc.so_v, pc.dst_v);
+        else dma16_buf_to_lds(voff_v[1], pc.srd_v, pc.so_v, pc.dst_v + 1024);
     };
     auto issue_all = [&](const Pieces& pc) __attribute__((always_inline)) {
         issue_piece(pc, P64Int<0>()); issue_piece(pc, P64Int<1>()); issue_piece(pc, P64Int<2>()); issue_piece(pc, P64Int<3>());
     };
     auto issue_q = [&](const Item& it) {        // the wave's own 64 rows: 8 pieces into its private 8 KiB
         const unsigned dst = lds0 + (unsigned)(P64_Q_OFF + wave * P64_TILE);
-        const p64_uint4_t srd = p64_make_srd((const void*)it.qb, it.qbytes);
+        const uint4_t srd = make_srd((const void*)it.qb, it.qbytes);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int rr = i * 8 + (lane >> 3);
             const unsigned vq = (unsigned)(((int64_t)rr * p.q_sn + ((lane & 7) ^ ((rr >> 1) & 7)) * 8) * 2);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) p64_dma16(vq, srd, (unsigned)k * q16, __builtin_amdgcn_readfirstlane(dst + k * 2048 + i * 1024));
+            for (int k = 0; k < 4; ++k) dma16_buf_to_lds(vq, srd, (unsigned)k * q16, __builtin_amdgcn_readfirstlane(dst + k * 2048 + i * 1024));
         }
     };
 
@@ -231,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
     // alike) + s_rd * P64_TILE; advanced with s_rd
     int ka[4];
 #pragma unroll
-    for (int st = 0; st < 4; ++st) ka[st] = p64_swz(lane & 31, 2 * st + (lane >> 5));
+    for (int st = 0; st < 4; ++st) ka[st] = tile_swz(lane & 31, 2 * st + (lane >> 5));
 
     // ---- warm-up of the stream: Q and the tiles of iterations -1, 0 of the first item ----
     int j = slot_w;
@@ -252,9 +228,9 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
 
     float16_t S[2][2], negm;       // ONE stale maximum per lane for its two queries (l31 of block A and of block B)
     float16_t o[2][2];             // [query block][channel block]
-    p64_bf16x8_t qf[2][4];
-    p64_bf16x8_t P[2][2][2];       // [key block][query block][16-key slab]
-    p64_bf16x8_t F[4];             // fragment ring of the main loop
+    bf16x8_t qf[2][4];
+    bf16x8_t P[2][2][2];       // [key block][query block][16-key slab]
+    bf16x8_t F[4];             // fragment ring of the main loop
     float m2, l[2];
 
     // ================================================================== building blocks ==========================================
@@ -262,10 +238,10 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
     auto qk_plain = [&](int kb, auto zero_tag) __attribute__((always_inline)) {      // zero_tag: scores started at 0 (no maximum yet)
         constexpr bool ZERO = decltype(zero_tag)::value;
         const char* sk = smem + P64_K_OFF + kb * 4096;
-        const p64_bf16x8_t k0 = *reinterpret_cast<const p64_bf16x8_t*>(sk + ka[0]);
-        const p64_bf16x8_t k1 = *reinterpret_cast<const p64_bf16x8_t*>(sk + ka[1]);
-        const p64_bf16x8_t k2 = *reinterpret_cast<const p64_bf16x8_t*>(sk + ka[2]);
-        const p64_bf16x8_t k3 = *reinterpret_cast<const p64_bf16x8_t*>(sk + ka[3]);
+        const bf16x8_t k0 = *reinterpret_cast<const bf16x8_t*>(sk + ka[0]);
+        const bf16x8_t k1 = *reinterpret_cast<const bf16x8_t*>(sk + ka[1]);
+        const bf16x8_t k2 = *reinterpret_cast<const bf16x8_t*>(sk + ka[2]);
+        const bf16x8_t k3 = *reinterpret_cast<const bf16x8_t*>(sk + ka[3]);
         if constexpr (ZERO) {
             p64_mfma_first0(S[kb][0], k0, qf[0][0]);
             p64_mfma_first0(S[kb][1], k0, qf[1][0]);
@@ -285,8 +261,8 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
         const char* sv = smem + P64_V_OFF;
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-            const p64_bf16x8_t v0 = *reinterpret_cast<const p64_bf16x8_t*>(sv + ka[2 * kb + hf]);
-            const p64_bf16x8_t v1 = *reinterpret_cast<const p64_bf16x8_t*>(sv + ka[2 * kb + hf] + 4096);
+            const bf16x8_t v0 = *reinterpret_cast<const bf16x8_t*>(sv + ka[2 * kb + hf]);
+            const bf16x8_t v1 = *reinterpret_cast<const bf16x8_t*>(sv + ka[2 * kb + hf] + 4096);
             p64_mfma_acc(o[0][0], v0, P[kb][0][hf]);
             p64_mfma_acc(o[1][0], v0, P[kb][1][hf]);
             p64_mfma_acc(o[0][1], v1, P[kb][0][hf]);
@@ -309,7 +285,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
             l[qb] += a0 + a1;
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
-                union { p64_bf16x8_t v; unsigned u[4]; } pk;
+                union { bf16x8_t v; unsigned u[4]; } pk;
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) pk.u[q4] = pack_bf16x2(e[hf * 8 + 2 * q4], e[hf * 8 + 2 * q4 + 1]);
                 P[kb][qb][hf] = pk.v;
@@ -353,14 +329,14 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
             // ---- fragment read for two slots x 2 ahead ----
             if constexpr ((k & 1) == 0) {
                 constexpr int f = (k >> 1) + 2;                   // fragment index, 2 .. 9 (8, 9 = region B's 0, 1)
-                if constexpr (f < 4) F[f & 3] = *reinterpret_cast<const p64_bf16x8_t*>(smem + P64_K_OFF + KQ * 4096 + ka[f]);
-                else if constexpr (f < 8) F[f & 3] = *reinterpret_cast<const p64_bf16x8_t*>(smem + P64_V_OFF + ((f - 4) & 1) * 4096 + ka[2 * KQ + ((f - 4) >> 1)]);
-                else if constexpr (KQ == 0) F[f & 3] = *reinterpret_cast<const p64_bf16x8_t*>(smem + P64_K_OFF + 4096 + ka[f - 8]);
+                if constexpr (f < 4) F[f & 3] = *reinterpret_cast<const bf16x8_t*>(smem + P64_K_OFF + KQ * 4096 + ka[f]);
+                else if constexpr (f < 8) F[f & 3] = *reinterpret_cast<const bf16x8_t*>(smem + P64_V_OFF + ((f - 4) & 1) * 4096 + ka[2 * KQ + ((f - 4) >> 1)]);
+                else if constexpr (KQ == 0) F[f & 3] = *reinterpret_cast<const bf16x8_t*>(smem + P64_K_OFF + 4096 + ka[f - 8]);
                 else {
                     // region B, slots 12 / 14: the iteration's last LDS read of the current ring slot was slot 10 — the end-of-iteration
                     // wait + barrier sits HERE, and region A's first fragments of the NEXT tile are read under the last four MFMAs
                     if constexpr (k == 12) wait_barrier(qi);
-                    F[f & 3] = *reinterpret_cast<const p64_bf16x8_t*>(smem + P64_K_OFF + nstep + ka[f - 8]);
+                    F[f & 3] = *reinterpret_cast<const bf16x8_t*>(smem + P64_K_OFF + nstep + ka[f - 8]);
                 }
             }
             if constexpr (k == 9) issue_piece(pc, P64Int<2 * KQ>());
@@ -381,7 +357,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
                 constexpr int kp = k - 1, qbp = kp >> 3, idx = kp & 7;
                 p64_add(acc[qbp][0], e0);
                 p64_add(acc[qbp][1], e1);
-                union { p64_bf16x8_t v; unsigned u[4]; } pk;
+                union { bf16x8_t v; unsigned u[4]; } pk;
                 pk.v = P[KS][qbp][idx >> 2];
                 pk.u[idx & 3] = p64_cvt_pk(e0, e1);
                 P[KS][qbp][idx >> 2] = pk.v;
@@ -406,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
             asm volatile("s_nop 0");                               // transcendental -> use
             p64_add(acc[1][0], e0);
             p64_add(acc[1][1], e1);
-            union { p64_bf16x8_t v; unsigned u[4]; } pk;
+            union { bf16x8_t v; unsigned u[4]; } pk;
             pk.v = P[KS][1][1];
             pk.u[3] = p64_cvt_pk(e0, e1);
             P[KS][1][1] = pk.v;
@@ -435,13 +411,13 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
-            for (int st = 0; st < 4; ++st) qf[qb][st] = *reinterpret_cast<const p64_bf16x8_t*>(sq + ka[st] + qb * 4096);
+            for (int st = 0; st < 4; ++st) qf[qb][st] = *reinterpret_cast<const bf16x8_t*>(sq + ka[st] + qb * 4096);
         if (!p.q_prescaled) {
 #pragma unroll
             for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
                 for (int st = 0; st < 4; ++st) {
-                    union { p64_bf16x8_t v; unsigned u[4]; } a;
+                    union { bf16x8_t v; unsigned u[4]; } a;
                     a.v = qf[qb][st];
 #pragma unroll
                     for (int q4 = 0; q4 < 4; ++q4)
@@ -488,8 +464,8 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
             P64_TS(11);
             issue_all(pc);
             end_iteration(qi);
-            F[0] = *reinterpret_cast<const p64_bf16x8_t*>(smem + P64_K_OFF + ka[0]);      // region A's first fragments (later: by region B)
-            F[1] = *reinterpret_cast<const p64_bf16x8_t*>(smem + P64_K_OFF + ka[1]);
+            F[0] = *reinterpret_cast<const bf16x8_t*>(smem + P64_K_OFF + ka[0]);      // region A's first fragments (later: by region B)
+            F[1] = *reinterpret_cast<const bf16x8_t*>(smem + P64_K_OFF + ka[1]);
         }
         // ---- iterations 0 .. nt-2: region 2i+1 = { QK^T(i+1, kb0), softmax(i, kb1), PV(i, kb0) }, region 2i+2 = { QK^T(i+1, kb1),
         //      softmax(i+1, kb0), PV(i, kb1) }; ring slot s_rd holds K(i+1) and VT(i) ----
@@ -580,8 +556,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_p64_kernel(AttnP64Params p) 
                 const unsigned o8 = (unsigned)(8 * p.o_sn * 2);
 #pragma unroll
                 for (int ps = 0; ps < 8; ++ps) {
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                    const u32x4 d = {rw[ps].x, rw[ps].y, rw[ps].z, rw[ps].w};
+                    const uint4_t d = {rw[ps].x, rw[ps].y, rw[ps].z, rw[ps].w};
                     __builtin_amdgcn_raw_buffer_store_b128(d, orsrc, (int)vo, (int)(ps * o8), 0);
                 }
             }

@@ -11,34 +11,9 @@
 // stores.  The operands come from a split pass (uc_attention_fwd_x3 runs it into the caller's workspace): Q is multiplied by
 // scale * log2(e) in fp32 BEFORE the split, so the scores arrive in the exp2 domain and the softmax needs no multiply.
 // Reference sites: libs/croco/blocks.py:123-125, models/utils/transformer_blocks.py:244-246, 373-375 (F.scaled_dot_product_attention).
-#include "common.h"
-
-typedef __bf16 x3_bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned x3_uint4_t __attribute__((ext_vector_type(4)));
+#include "mma_tile.h"
 
 #define X3_TILE_BYTES (64 * 128)   // 64 rows x 128 B (one bf16 tile: 64 keys x 64 channels, or 64 channels x 64 key positions)
-
-__device__ __forceinline__ int x3_swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int x3_key_of_pos(int pp) { const int hi = pp >> 3, j = pp & 7; return (j & 3) + 8 * (j >> 2) + 4 * hi; }
-
-__device__ __forceinline__ void x3_dma16(unsigned voff, x3_uint4_t srd, unsigned soff, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 4\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(lds_byte_addr), "s"(soff)
-        : "memory");
-}
-__device__ __forceinline__ x3_uint4_t x3_make_srd(const void* base, unsigned bytes) {
-    const unsigned long long pa = (unsigned long long)base;
-    return (x3_uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pa),
-                        (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pa >> 32) & 0xffffu)),
-                        (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // split passes.  rows: fp32 [B, N, H, 64] strided (unit channel stride) -> hi, lo bf16 [B, N, H, 64] contiguous, x * mul first.
@@ -111,7 +86,7 @@ __global__ __launch_bounds__(256) void x3_vt_pack_kernel(const float* __restrict
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int pos = p8 + j;
-            e[j] = tile[(pos & ~15) + x3_key_of_pos(pos & 15)][d];
+            e[j] = tile[(pos & ~15) + vt_key_of_pos(pos & 15)][d];
         }
         unsigned hh[4], ll[4];
 #pragma unroll
@@ -146,16 +121,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
     const int nq = (p.Nq + QT - 1) / QT;
     const int nbh = p.B * p.H;
     int qt, bh;
-    {   // query tiles of one (batch, head) meet on one XCD (see attn_bf16_dma_kernel)
-        const int w = blockIdx.x;
-        const int per_group = 8 * nq;
-        const int grp = (int)uc_div((unsigned)w, p.dGroup), within = w - grp * per_group;
-        if ((grp + 1) * 8 <= nbh) { bh = grp * 8 + (within & 7); qt = within >> 3; }
-        else {
-            const int rem = w - (nbh >> 3) * 8 * nq, rb = (int)uc_div((unsigned)rem, p.dNq);
-            bh = (nbh >> 3) * 8 + rb; qt = rem - rb * nq;
-        }
-    }
+    xcd_tile_order((int)blockIdx.x, nq, nbh, p.dGroup, p.dNq, qt, bh);
     const int b = (int)uc_div((unsigned)bh, p.dH), h = bh - b * p.H;
     const int q0 = qt * QT + wave * 32;
     const int64_t row_stride = (int64_t)p.H * 64;         // elements between tokens of the contiguous split operands
@@ -163,9 +129,9 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
     const int64_t vbase = ((int64_t)b * p.H + h) * 64 * (int64_t)p.npad;
 
     const unsigned k_bytes = (unsigned)((((int64_t)p.Nk - 1) * row_stride + 64) * 2);    // key rows >= Nk read as zeros
-    const x3_uint4_t srd_kh = x3_make_srd(p.Kh + kbase, k_bytes), srd_kl = x3_make_srd(p.Kl + kbase, k_bytes);
-    const x3_uint4_t srd_vh = x3_make_srd(p.VTh + vbase, 0xffffff00u), srd_vl = x3_make_srd(p.VTl + vbase, 0xffffff00u);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)smem;
+    const uint4_t srd_kh = make_srd(p.Kh + kbase, k_bytes), srd_kl = make_srd(p.Kl + kbase, k_bytes);
+    const uint4_t srd_vh = make_srd(p.VTh + vbase), srd_vl = make_srd(p.VTl + vbase);
+    const unsigned lds0 = lds_addr(smem);
     unsigned voff_k[2], voff_v[2];       // a tile is 8 instructions of 8 rows x 128 B; wave w issues instructions 2w, 2w + 1 of all four tiles
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -179,39 +145,39 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
         const unsigned dst = lds0 + (unsigned)(buf * 4 * X3_TILE_BYTES + wave * 2048);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            x3_dma16(voff_k[i], srd_kh, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + i * 1024));
-            x3_dma16(voff_k[i], srd_kl, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + X3_TILE_BYTES + i * 1024));
-            x3_dma16(voff_v[i], srd_vh, (unsigned)t * 128u, __builtin_amdgcn_readfirstlane(dst + 2 * X3_TILE_BYTES + i * 1024));
-            x3_dma16(voff_v[i], srd_vl, (unsigned)t * 128u, __builtin_amdgcn_readfirstlane(dst + 3 * X3_TILE_BYTES + i * 1024));
+            dma16_buf_to_lds(voff_k[i], srd_kh, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + i * 1024));
+            dma16_buf_to_lds(voff_k[i], srd_kl, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + X3_TILE_BYTES + i * 1024));
+            dma16_buf_to_lds(voff_v[i], srd_vh, (unsigned)t * 128u, __builtin_amdgcn_readfirstlane(dst + 2 * X3_TILE_BYTES + i * 1024));
+            dma16_buf_to_lds(voff_v[i], srd_vl, (unsigned)t * 128u, __builtin_amdgcn_readfirstlane(dst + 3 * X3_TILE_BYTES + i * 1024));
         }
     };
     {   // Q rows of this wave (hi, lo) into the second stage
         const int64_t q_rows = min((int64_t)32, (int64_t)p.Nq - q0);
         const unsigned q_bytes = q_rows > 0 ? (unsigned)(((q_rows - 1) * row_stride + 64) * 2) : 0u;
-        const x3_uint4_t srd_qh = x3_make_srd(p.Qh + qbase + (int64_t)q0 * row_stride, q_bytes);
-        const x3_uint4_t srd_ql = x3_make_srd(p.Ql + qbase + (int64_t)q0 * row_stride, q_bytes);
+        const uint4_t srd_qh = make_srd(p.Qh + qbase + (int64_t)q0 * row_stride, q_bytes);
+        const uint4_t srd_ql = make_srd(p.Ql + qbase + (int64_t)q0 * row_stride, q_bytes);
         const unsigned dstq = lds0 + (unsigned)(4 * X3_TILE_BYTES + wave * 8192);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int rr = i * 8 + (lane >> 3);
             const int cch = (lane & 7) ^ ((rr >> 1) & 7);
             const unsigned vo = (unsigned)(((int64_t)rr * row_stride + cch * 8) * 2);
-            x3_dma16(vo, srd_qh, 0u, __builtin_amdgcn_readfirstlane(dstq + i * 1024));
-            x3_dma16(vo, srd_ql, 0u, __builtin_amdgcn_readfirstlane(dstq + 4096 + i * 1024));
+            dma16_buf_to_lds(vo, srd_qh, 0u, __builtin_amdgcn_readfirstlane(dstq + i * 1024));
+            dma16_buf_to_lds(vo, srd_ql, 0u, __builtin_amdgcn_readfirstlane(dstq + 4096 + i * 1024));
         }
     }
     int r_off[4];
 #pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = x3_swz(l31, 2 * st + hi);
+    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
 
     issue_tile(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    x3_bf16x8_t qh[4], ql[4];
+    bf16x8_t qh[4], ql[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        qh[s] = *reinterpret_cast<const x3_bf16x8_t*>(smem + 4 * X3_TILE_BYTES + wave * 8192 + r_off[s]);
-        ql[s] = *reinterpret_cast<const x3_bf16x8_t*>(smem + 4 * X3_TILE_BYTES + wave * 8192 + 4096 + r_off[s]);
+        qh[s] = *reinterpret_cast<const bf16x8_t*>(smem + 4 * X3_TILE_BYTES + wave * 8192 + r_off[s]);
+        ql[s] = *reinterpret_cast<const bf16x8_t*>(smem + 4 * X3_TILE_BYTES + wave * 8192 + 4096 + r_off[s]);
     }
     __syncthreads();
 
@@ -235,8 +201,8 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
             s[kb] = (float16_t)(0.f);
 #pragma unroll
             for (int st = 0; st < 4; ++st) {      // the two small terms first, the large one last
-                const x3_bf16x8_t kh = *reinterpret_cast<const x3_bf16x8_t*>(skh + r_off[st] + kb * (32 * 128));
-                const x3_bf16x8_t kl = *reinterpret_cast<const x3_bf16x8_t*>(skl + r_off[st] + kb * (32 * 128));
+                const bf16x8_t kh = *reinterpret_cast<const bf16x8_t*>(skh + r_off[st] + kb * (32 * 128));
+                const bf16x8_t kl = *reinterpret_cast<const bf16x8_t*>(skl + r_off[st] + kb * (32 * 128));
                 s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl, qh[st], s[kb], 0, 0, 0);
                 s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, ql[st], s[kb], 0, 0, 0);
                 s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh[st], s[kb], 0, 0, 0);
@@ -270,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
                 for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
         }
         float psum = 0.f;
-        x3_bf16x8_t ph[4], pl[4];
+        bf16x8_t ph[4], pl[4];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
@@ -281,7 +247,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
                     e[j] = __builtin_amdgcn_exp2f(s[kb][hf * 8 + j] - m_run);
                     psum += e[j];
                 }
-                union { x3_bf16x8_t v; unsigned u[4]; } a, c;
+                union { bf16x8_t v; unsigned u[4]; } a, c;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     a.u[j] = pack_bf16x2(e[2 * j], e[2 * j + 1]);
@@ -296,8 +262,8 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const x3_bf16x8_t vh = *reinterpret_cast<const x3_bf16x8_t*>(svh + r_off[g] + db * (32 * 128));
-                const x3_bf16x8_t vl = *reinterpret_cast<const x3_bf16x8_t*>(svl + r_off[g] + db * (32 * 128));
+                const bf16x8_t vh = *reinterpret_cast<const bf16x8_t*>(svh + r_off[g] + db * (32 * 128));
+                const bf16x8_t vl = *reinterpret_cast<const bf16x8_t*>(svl + r_off[g] + db * (32 * 128));
                 o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph[g], o[db], 0, 0, 0);
                 o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl[g], o[db], 0, 0, 0);
                 o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph[g], o[db], 0, 0, 0);

@@ -43,6 +43,7 @@ __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(
 // attention softmax.
 typedef __bf16 bf16x2v_t __attribute__((ext_vector_type(2)));
 typedef float float2v_t __attribute__((ext_vector_type(2)));
+typedef _Float16 half2v_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
     const float2v_t v = {lo, hi};

@@ -16,7 +16,7 @@
 // With the 16x16 MFMA C layout (col = lane&15, row = 4*(lane>>4)+reg) and a 64-column wave tile
 // aligned to a 64-wide head, the RoPE partner of channel d (< 16) is channel d+16 of the same
 // row: fragment ni and ni+1 of the SAME lane and register, so the rotation needs no cross-lane traffic.
-#include "common.h"
+#include "mma_tile.h"
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -26,8 +26,6 @@
 #include "knobs.h"
 #include <stdlib.h>
 #include <algorithm>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 struct GemmParams {
     const void* A;
@@ -74,15 +72,6 @@ __device__ __forceinline__ void store_out(void* c, int dtype, int64_t idx, float
     else ((bf16_t*)c)[idx] = f32_to_bf16(v);
 }
 
-// XCD-aware tile order: consecutive workgroup ids land on different XCDs (id % 8); give each XCD a
-// contiguous run of tiles so tiles that share an A row-panel / W column-panel share one L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + k;
-}
-
 // =======================================================================================
 // bf16 MFMA kernel
 // =======================================================================================
@@ -93,22 +82,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // LDS: 2 stages x (A 128x64 + W 128x64) bf16 = 2 x 32 KiB
 #define TILE_BYTES (BM * BK * 2)
 
-__device__ __forceinline__ int swz_off(int row, int chunk) {  // byte offset inside a 128-row x 128-B tile
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-
-__device__ __forceinline__ uint4 relu_bf16x8(uint4 v) {
-    unsigned* p = reinterpret_cast<unsigned*>(&v);
-    typedef short short2_t __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int i = 0; i < 4; ++i)      // negative bf16 <=> negative int16: one v_pk_max_i16 per register
-        p[i] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(short2_t, p[i]), (short2_t){0, 0}));
-    return v;
-}
-
 // F16: fp16 operands (v_mfma_f32_16x16x32_f16) and fp16 outputs / residuals — the fallback of the heads' TF32-class mode for channel
 // counts the direct-to-LDS kernels do not take (small test models); bias / activation / residuals only.
-typedef _Float16 gemm_f16x8_t __attribute__((ext_vector_type(8)));
 template <int A_MODE, bool F16 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -187,8 +162,8 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmParams p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = r0 + 32 * i;
-            *reinterpret_cast<uint4*>(sa + swz_off(row, cc)) = ra[i];
-            *reinterpret_cast<uint4*>(sw + swz_off(row, cc)) = rw[i];
+            *reinterpret_cast<uint4*>(sa + tile_swz(row, cc)) = ra[i];
+            *reinterpret_cast<uint4*>(sw + tile_swz(row, cc)) = rw[i];
         }
     };
 
@@ -218,18 +193,18 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmParams p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = wr * 64 + i * 16 + frow;
-                af[i] = *reinterpret_cast<const bf16x8_t*>(sa + swz_off(row, chunk));
+                af[i] = *reinterpret_cast<const bf16x8_t*>(sa + tile_swz(row, chunk));
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int row = wc * 64 + j * 16 + frow;
-                wf[j] = *reinterpret_cast<const bf16x8_t*>(sw + swz_off(row, chunk));
+                wf[j] = *reinterpret_cast<const bf16x8_t*>(sw + tile_swz(row, chunk));
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if constexpr (F16) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gemm_f16x8_t, af[i]), __builtin_bit_cast(gemm_f16x8_t, wf[j]), acc[i][j], 0, 0, 0);
+                    if constexpr (F16) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, af[i]), __builtin_bit_cast(f16x8_t, wf[j]), acc[i][j], 0, 0, 0);
                     else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], wf[j], acc[i][j], 0, 0, 0);
         }
         if (kt + 1 < nk) stage_write(buf ^ 1);

@@ -1,5 +1,5 @@
 #pragma once
-// Dense bf16 GEMM for gfx950 with direct global->LDS staging (global_load_lds_dwordx4, 1 KiB per wave-instruction).
+// Dense bf16 GEMM for gfx950 with direct global->LDS staging (LDS-DMA, mma_tile.h: 1 KiB per wave-instruction).
 //
 //   C[M,N] = epilogue(A[M,K] . W[N,K]^T),  K % 64 == 0, A/W bf16 row-major.
 //
@@ -14,11 +14,8 @@
 // permutation 16*(a>>2)+4j+(a&3), a lane's 16 values are 16 consecutive columns.  Tiles that take the RoPE epilogue
 // keep the identity column map (partner channel d+16 = next fragment, same lane/register); V tiles that are written
 // in the packed VT layout use the un-swapped orientation (a lane owns 4 consecutive TOKENS of one channel).
-#include "common.h"
+#include "mma_tile.h"
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
 #include "gemm_glds.h"
 #include "knobs.h"
@@ -39,8 +36,6 @@ typedef const GldsParams& glds_pe_t;
 // libs/croco/blocks.py:15 / factory/dust3r.py:288-309), at the bf16 rate.  Only the EPI_ALL family is instantiated for it (3x3
 // convolutions, 1x1 convolutions / ConvTranspose GEMMs: bias, ReLU / GELU, residuals, fused tail); RoPE / VT / LayerNorm options
 // are rejected by the launcher.
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 glds_half2_t __attribute__((ext_vector_type(2)));
 template <bool F16>
 __device__ __forceinline__ float4_t glds_mfma(bf16x8_t a, bf16x8_t b, float4_t c) {
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
@@ -50,12 +45,12 @@ template <bool F16>
 __device__ __forceinline__ unsigned glds_pack2(float lo, float hi) {
     if constexpr (F16) {
         const float2v_t v = {uc_sat_f16(lo), uc_sat_f16(hi)};      // (saturating: see common.h)
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, glds_half2_t));
+        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, half2v_t));
     } else return pack_bf16x2(lo, hi);
 }
 __device__ __forceinline__ float4_t glds_unpack_f16x4(uint2 q) {
-    const float2v_t a = __builtin_convertvector(__builtin_bit_cast(glds_half2_t, q.x), float2v_t);
-    const float2v_t b = __builtin_convertvector(__builtin_bit_cast(glds_half2_t, q.y), float2v_t);
+    const float2v_t a = __builtin_convertvector(__builtin_bit_cast(half2v_t, q.x), float2v_t);
+    const float2v_t b = __builtin_convertvector(__builtin_bit_cast(half2v_t, q.y), float2v_t);
     return (float4_t){a.x, a.y, b.x, b.y};
 }
 
@@ -94,102 +89,10 @@ __device__ __forceinline__ float glds_act(float v, int act) {
     return v;
 }
 
-__device__ __forceinline__ int glds_xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + k;
-}
-
-// ReLU of eight bf16 values: a bf16 is negative exactly when its bit pattern is negative as an int16, so max(int16, 0) is the
-// ReLU (-0 -> +0): one v_pk_max_i16 per register instead of shift / and / multiply / and-not — the fragment-load ReLU of the
-// residual conv units sits in the K-loop, where vector instructions take their cycles from the matrix pipe.
-typedef short glds_short2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint4 glds_relu_bf16x8(uint4 v) {
-    unsigned* q = reinterpret_cast<unsigned*>(&v);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        q[i] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(glds_short2_t, q[i]), (glds_short2_t){0, 0}));
-    return v;
-}
-
-// One 1-KiB LDS-DMA piece issued through inline asm.  With the __builtin form hipcc tracks the DMA as an LDS write it
-// cannot disambiguate from the fragment ds_reads of the OTHER stage buffer and inserts `s_waitcnt vmcnt(0)` in front of
-// them — the whole global->LDS latency is then exposed in every K-step (measured: matrix pipe 39 % busy, 57 % of wave
-// cycles parked).  The asm form is invisible to that pass; completion is enforced by hand with counted s_waitcnt
-// vmcnt(N) + s_barrier (see the K-loops).  M0 carries the wave-uniform LDS byte address; it is compiler-reserved, so it
-// is saved and restored inside the statement; s_nop 0 covers the M0-write -> LDS-DMA hazard.
-__device__ __forceinline__ void dma16_to_lds(const void* gsrc, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_byte_addr)
-        : "memory");
-}
-
-// saddr form: wave-uniform 64-bit base (SGPR pair) + 32-bit per-lane byte offset
-__device__ __forceinline__ void dma16_s_to_lds(unsigned voff, const void* sbase, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(lds_byte_addr)
-        : "memory");
-}
-
 // chunk swizzle key of LDS row r: 128-B rows (r>>1)&7, 64-B rows 3*((r>>2)&1) — both make the ds_read_b128 fragment
 // loads (lane = row, lane>>4 = k chunk) conflict-free within the hardware's 16-lane service groups
 template <int BK_>
 __device__ __forceinline__ int glds_swz(int r) { return BK_ == 64 ? ((r >> 1) & 7) : (((r >> 2) & 1) * 3); }
-
-// Buffer-addressed form: source = descriptor base + voff + soff (bytes); a lane whose offset is outside the descriptor's
-// range gets zeros written to its 16 LDS bytes.  s_nop 4 covers SGPR (descriptor / soffset / M0) write -> VMEM read.
-typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void dma16_buf_to_lds(unsigned voff, uint4_t srd, unsigned soff, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 4\n\t"
-        "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(lds_byte_addr), "s"(soff)
-        : "memory");
-}
-
-// ... under a wave-uniform execution mask (all lanes or none): a slot of a fixed per-wave DMA schedule that only some waves fill is
-// issued with EXEC = 0 by the others — no branch in the instruction stream (a branch splits the MFMA stream into basic blocks),
-// no work in the memory pipeline.
-__device__ __forceinline__ void dma16_buf_to_lds_if(unsigned exec_half, unsigned voff, uint4_t srd, unsigned soff, unsigned lds_byte_addr) {
-    unsigned keep;
-    unsigned long long keep_exec;
-    asm volatile(
-        "s_mov_b64 %0, exec\n\t"
-        "s_mov_b32 %1, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_mov_b32 exec_lo, %6\n\t"
-        "s_mov_b32 exec_hi, %6\n\t"
-        "s_nop 4\n\t"
-        "buffer_load_dwordx4 %2, %3, %5 offen lds\n\t"
-        "s_mov_b64 exec, %0\n\t"
-        "s_mov_b32 m0, %1"
-        : "=&s"(keep_exec), "=&s"(keep)
-        : "v"(voff), "s"(srd), "s"(lds_byte_addr), "s"(soff), "s"(exec_half)
-        : "memory");
-}
-
-template <int N_>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory"); }
 
 // Side panel of the eight-wave kernel (GldsParams::side_lds): 8 KiB of LDS behind the two-stage ring, filled by one DMA piece per wave
 // before the first K-step — (mean, rstd) of the tile's 256 rows, column sums and bias of its 256 columns, RoPE positions of its rows.
@@ -1289,7 +1192,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, WGS_PER_CU * WAVES_M * WAVES
     const bool fuse2 = FUSE2_OK && p.fuse_split2;
     const int ksplit = fuse2 ? ((int)blockIdx.x >= nwg ? 1 : 0)
                              : (p.split_k > 1 ? (int)uc_div(blockIdx.x, p.dNwg) : 0);   // split-K slice
-    const int t = glds_xcd_remap((int)blockIdx.x - ksplit * nwg, nwg);
+    const int t = xcd_remap((int)blockIdx.x - ksplit * nwg, nwg);
     // Tile order inside an XCD's run: groups of GM row panels swept column by column, so the ~32 tiles an XCD runs
     // concurrently form a GM x (32/GM) block that shares GM A-panels and 32/GM W-panels in its L2 (a plain row-major
     // order shares 2 A-panels but streams ALL of W through every pair of row panels: 2.4x algorithmic fetch traffic).
@@ -1336,10 +1239,8 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, WGS_PER_CU * WAVES_M * WAVES
     uint4_t srd_a = (uint4_t){0u, 0u, 0u, 0u}, srd_w = srd_a;
     if constexpr (A_MODE != UC_A_DENSE) {
         const int b0 = (int)uc_div((unsigned)min(m0, p.M - 1), p.dHWo);     // < 2^30 output pixels (launcher-checked)
-        const unsigned long long pa = (unsigned long long)(p.A + ((int64_t)b0 * p.cH * p.cW - (p.cW + 1)) * p.cCin);
-        const unsigned long long pw = (unsigned long long)(p.W + min(n0, p.N - 1) * p.K);
-        srd_a = (uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pa), (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pa >> 32) & 0xffffu)), 0xffffff00u, 0x00020000u};
-        srd_w = (uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pw), (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pw >> 32) & 0xffffu)), 0xffffff00u, 0x00020000u};
+        srd_a = make_srd(p.A + ((int64_t)b0 * p.cH * p.cW - (p.cW + 1)) * p.cCin);
+        srd_w = make_srd(p.W + min(n0, p.N - 1) * p.K);
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
             const int rr = (wave * PER + q) * RPI + lane / CPR;
@@ -1372,7 +1273,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, WGS_PER_CU * WAVES_M * WAVES
             else src[q] = p.W + min(n0 + (rr - BM_), p.N - 1) * p.K + c * 8;
         }
     }
-    const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)smem;   // LDS byte address of the dynamic region
+    const unsigned lds_base = lds_addr(smem);   // LDS byte address of the dynamic region
     auto issue_stage = [&](int stage, int64_t k0) {
         int tap = 0;
         unsigned soff_a = 0, soff_w = 0;
@@ -1434,7 +1335,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, WGS_PER_CU * WAVES_M * WAVES
             for (int i = 0; i < FA; ++i) {
                 uint4 raw = *reinterpret_cast<const uint4*>(st + a_base + ch_off[ks] + i * 16 * ROWB);
                 if constexpr (A_MODE != UC_A_DENSE) {
-                    if (p.relu_a) raw = glds_relu_bf16x8(raw);   // uniform flag: ReLU of the DPT residual conv unit, applied on load
+                    if (p.relu_a) raw = relu_bf16x8(raw);   // uniform flag: ReLU of the DPT residual conv unit, applied on load
                 }
                 af[i] = __builtin_bit_cast(bf16x8_t, raw);
             }
@@ -1619,7 +1520,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_glds8_kernel(GldsParams p) {
     const int wr = wave / WAVES_N, wc = wave % WAVES_N;
     const int nwg = p.tiles_m * p.tiles_n;
     const int ksplit = p.split_k > 1 ? (int)uc_div(blockIdx.x, p.dNwg) : 0;
-    const int t = glds_xcd_remap((int)blockIdx.x - ksplit * nwg, nwg);
+    const int t = xcd_remap((int)blockIdx.x - ksplit * nwg, nwg);
     int tm, tn;
     {   // tile order: see the 16-wave kernel
         const int GM = p.group_m;
@@ -1661,7 +1562,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_glds8_kernel(GldsParams p) {
     }
     const unsigned voff_row = (unsigned)((lane >> 3) * (int)ld_src) * 2u;
     const unsigned voff2[2] = {voff_row + (unsigned)(((lane & 7) ^ (lane >> 4)) << 4), voff_row + (unsigned)(((lane & 7) ^ (4 + (lane >> 4))) << 4)};
-    const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)smem;
+    const unsigned lds_base = lds_addr(smem);
     auto issue_piece = [&](int stage, int64_t k0, int q) __attribute__((always_inline)) {
         const unsigned dst = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(stage * STAGE_BYTES + wave * (PER * 1024) + q * 1024));
         dma16_s_to_lds(voff2[q & 1], sbase[q] + k0, dst);
@@ -1858,7 +1759,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_glds4_kernel(GldsParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
     const int nwg = p.tiles_m * p.tiles_n;
-    const int t = glds_xcd_remap((int)blockIdx.x, nwg);
+    const int t = xcd_remap((int)blockIdx.x, nwg);
     int tm, tn;
     {   // tile order: see the 16-wave kernel
         const int GM = p.group_m;
@@ -1897,7 +1798,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_glds4_kernel(GldsParams p) {
     const unsigned voff_row = (unsigned)(lane >> 3) * pitch;
     const unsigned voff0 = voff_row + (unsigned)(((lane & 7) ^ (lane >> 4)) << 4);
     const unsigned voff1 = voff_row + (unsigned)(((lane & 7) ^ (4 + (lane >> 4))) << 4);
-    const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)smem;
+    const unsigned lds_base = lds_addr(smem);
     const unsigned lds_dma = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + (unsigned)wave * 16384u));
     // fragment read addresses of stage 0 (K halves 0 / 1): row frow of the wave's block 0, chunk (4 ks + fk) ^ swizzle(frow)
     const int frow = lane & 15, fk = lane >> 4, f_sw = glds_swz<64>(frow);
@@ -1962,7 +1863,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows_kernel(GldsParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
     const int nwg = p.tiles_m * p.tiles_n;
-    const int t = glds_xcd_remap((int)blockIdx.x, nwg);
+    const int t = xcd_remap((int)blockIdx.x, nwg);
     int tm, tn;
     {   // tile order: see the 16-wave kernel
         const int GM = p.group_m;
@@ -1986,10 +1887,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows_kernel(GldsParams p) {
     const int oy0 = (int)(rowid0 - b0 * (unsigned)H_);
     // descriptors: the slab's source window shifted back by one image row + one pixel (tap row ky and the chunk are a uniform
     // non-negative soffset), and the tile's weight rows
-    const unsigned long long pa = (unsigned long long)(p.A + (((int64_t)rowid0 - 1) * W_ + (ox0 - 1)) * Cin);
-    const unsigned long long pw = (unsigned long long)(p.W + n0 * p.K);
-    const uint4_t srd_a = (uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pa), (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pa >> 32) & 0xffffu)), 0xffffff00u, 0x00020000u};
-    const uint4_t srd_w = (uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pw), (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pw >> 32) & 0xffffu)), 0xffffff00u, 0x00020000u};
+    const uint4_t srd_a = make_srd(p.A + (((int64_t)rowid0 - 1) * W_ + (ox0 - 1)) * Cin);
+    const uint4_t srd_w = make_srd(p.W + n0 * p.K);
     // slab pieces of this wave: piece n = wave + 8 q covers slab rows 8 n .. 8 n + 7; lane -> row 8 n + lane / 8, physical chunk lane % 8
     unsigned sl_off[5], sl_mask[5];
 #pragma unroll
@@ -2013,7 +1912,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows_kernel(GldsParams p) {
         const int c = (lane & 7) ^ glds_swz<64>(row);
         w_off[q] = (unsigned)(((int64_t)row * p.K + c * 8) * 2);
     }
-    const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)smem;
+    const unsigned lds_base = lds_addr(smem);
     const unsigned lds_w = lds_base + 2u * SLAB_BYTES;
     const int nch = Cin / 64;
     const int nunit = 9 * nch;
@@ -2062,7 +1961,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows_kernel(GldsParams p) {
             for (int i = 0; i < FA; ++i) {
                 const int row = a_row[i] + kx;
                 uint4 raw = *reinterpret_cast<const uint4*>(slab + row * ROWB + (((ks * 4 + fk) ^ glds_swz<64>(row)) << 4));
-                if (p.relu_a) raw = glds_relu_bf16x8(raw);
+                if (p.relu_a) raw = relu_bf16x8(raw);
                 af[i] = __builtin_bit_cast(bf16x8_t, raw);
             }
 #pragma unroll
@@ -2176,7 +2075,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows8_kernel(GldsParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
     const int nwg = p.tiles_m * p.tiles_n;
-    const int t = glds_xcd_remap((int)blockIdx.x, nwg);
+    const int t = xcd_remap((int)blockIdx.x, nwg);
     int tm, tn;
     {   // tile order: see the 16-wave kernel
         const int GM = p.group_m;
@@ -2200,11 +2099,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows8_kernel(GldsParams p) {
     const int oy0 = (int)(rowid0 - b0 * (unsigned)H_);
     // slab row 0 of kernel row 0: segmented form = pixel (row above the tile's first, one left of its first column); flat form = flat
     // pixel m0 - W - 1.  (Either may lie before the tensor: lanes that would read there are masked — the descriptor base is only an origin.)
-    const unsigned long long pa = FLAT ? (unsigned long long)(p.A + ((int64_t)m0 - 1 - W_) * Cin)
-                                       : (unsigned long long)(p.A + (((int64_t)rowid0 - 1) * W_ + (ox0 - 1)) * Cin);
-    const unsigned long long pw = (unsigned long long)(p.W + n0 * p.K);
-    const uint4_t srd_a = (uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pa), (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pa >> 32) & 0xffffu)), 0xffffff00u, 0x00020000u};
-    const uint4_t srd_w = (uint4_t){(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pw), (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(pw >> 32) & 0xffffu)), 0xffffff00u, 0x00020000u};
+    const uint4_t srd_a = make_srd(FLAT ? p.A + ((int64_t)m0 - 1 - W_) * Cin : p.A + (((int64_t)rowid0 - 1) * W_ + (ox0 - 1)) * Cin);
+    const uint4_t srd_w = make_srd(p.W + n0 * p.K);
     // slab pieces of this wave: piece n = wave + 8 q covers slab rows 16 n .. 16 n + 15; lane -> row 16 n + lane / 4, physical chunk lane % 4
     // (piece 32 = q 4 of wave 0 only).  sl_mask: bit 3 q + ky = the lane's pixel exists for tap row ky
     unsigned sl_off[5], sl_mask = 0;
@@ -2242,7 +2138,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows8_kernel(GldsParams p) {
         w_off = (__umul24((unsigned)row, (unsigned)p.K) + (unsigned)c * 8u) * 2u;
         asm volatile("" : "+v"(w_off));
     }
-    const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)smem;
+    const unsigned lds_base = lds_addr(smem);
     // both halves of the fifth slot's EXEC.  (Scalar by construction: as `readfirstlane(wave == 0 ? -1 : 0)` hipcc drops the readfirstlane
     //  of a value it knows to be uniform, may still SELECT it on the vector unit, and then hands the VGPR to the asm's "s" operand.)
     unsigned wave0_exec;
@@ -2312,7 +2208,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows8_kernel(GldsParams p) {
     };
     auto mma_row = [&](int i, bf16x8_t (&wv)[4], auto ckx) __attribute__((always_inline)) {      // ckx: the tap column these MFMAs belong to
         bf16x8_t av = a[i];
-        if constexpr (RELU_A) av = __builtin_bit_cast(bf16x8_t, glds_relu_bf16x8(__builtin_bit_cast(uint4, av)));
+        if constexpr (RELU_A) av = __builtin_bit_cast(bf16x8_t, relu_bf16x8(__builtin_bit_cast(uint4, av)));
         if constexpr (FLAT && decltype(ckx)::value == 0) av = (i & 1) ? glds_zero_edge_lanes<1>(av, edge0[i >> 1]) : glds_zero_edge_lanes<0>(av, edge0[i >> 1]);
         if constexpr (FLAT && decltype(ckx)::value == 2) av = (i & 1) ? glds_zero_edge_lanes<1>(av, edge2[i >> 1]) : glds_zero_edge_lanes<0>(av, edge2[i >> 1]);
 #pragma unroll

@@ -12,15 +12,10 @@
 // 32-byte column block, so the 32-byte block index is XOR-ed with s(r) = (r&3) | ((r>>3)&1)<<2 — eight distinct
 // 8-bank groups.  As in the NT kernel the permutation is applied to the DMA's per-lane SOURCE address.
 // Split-K over t: slice s stores its partial product to the slab C + s*I*J (plain stores; see uc_splitk_reduce).
-#include "common.h"
+#include "mma_tile.h"
 #include "gemm_tn_plan.h"
 
 #include <mutex>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* tn_lds_ptr_t;
 
 struct TnParams {
     const bf16_t* A;     // [T, I], leading dim lda
@@ -40,30 +35,7 @@ struct TnParams {
 
 __device__ uint4 g_tn_zero[2];   // 16 zero bytes (+ slack): DMA source for rows beyond T and for the conv's zero padding
 
-__device__ __forceinline__ void tn_dma16(const void* gsrc, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_byte_addr)
-        : "memory");
-}
-
 __device__ __forceinline__ int tn_swz(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
-
-__device__ __forceinline__ bf16x4_t tn_relu4(bf16x4_t v) {
-    uint2 u = __builtin_bit_cast(uint2, v);
-    unsigned* q = reinterpret_cast<unsigned*>(&u);
-    typedef short tn_short2_t __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int i = 0; i < 2; ++i)      // negative bf16 <=> negative int16: one v_pk_max_i16 per register
-        q[i] = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(tn_short2_t, q[i]), (tn_short2_t){0, 0}));
-    return __builtin_bit_cast(bf16x4_t, u);
-}
 
 #define TN_BN UC_TN_BN
 
@@ -108,7 +80,7 @@ __global__ __launch_bounds__(BM_ * 4) void gemm_tn_kernel(TnParams p) {
         if (col + 8 > lim) col = lim - 8;                                // duplicate a valid chunk; those outputs are never stored
         d_col[q] = (int)col;
     }
-    const unsigned lds_base = (unsigned)(size_t)(tn_lds_ptr_t)smem;
+    const unsigned lds_base = lds_addr(smem);
     auto issue_stage = [&](int stage, int64_t t0) {
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
@@ -134,7 +106,7 @@ __global__ __launch_bounds__(BM_ * 4) void gemm_tn_kernel(TnParams p) {
                         g = p.B + (((int64_t)b * p.cH + iy) * p.cW + ix) * p.cCin + c;
                 }
             }
-            tn_dma16(g, __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(stage * STAGE + n * 1024)));
+            dma16_to_lds(g, __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(stage * STAGE + n * 1024)));
         }
     };
 
@@ -163,12 +135,11 @@ __global__ __launch_bounds__(BM_ * 4) void gemm_tn_kernel(TnParams p) {
     const int nk = max(0, min(nk_per, nk_total - kt0));
     const int64_t tbase = (int64_t)kt0 * 64;
 
-    typedef __attribute__((address_space(3))) bf16x4_t* lds_v4_t;
 #define TN_FRAG(dst_, st_, off_, ks_, ROWB_, relu_)                                                                                 \
     do {                                                                                                                            \
-        bf16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4_t)(tn_lds_ptr_t)((st_) + (off_) + (ks_) * (32 * (ROWB_))));                 \
-        bf16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4_t)(tn_lds_ptr_t)((st_) + (off_) + (ks_) * (32 * (ROWB_)) + 4 * (ROWB_)));   \
-        if (relu_) { lo_ = tn_relu4(lo_); hi_ = tn_relu4(hi_); }                                                                     \
+        bf16x4_t lo_ = lds_read_tr16((st_) + (off_) + (ks_) * (32 * (ROWB_)));                                                         \
+        bf16x4_t hi_ = lds_read_tr16((st_) + (off_) + (ks_) * (32 * (ROWB_)) + 4 * (ROWB_));                                           \
+        if (relu_) { lo_ = relu_bf16x4(lo_); hi_ = relu_bf16x4(hi_); }                                                               \
         (dst_) = __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7);                                                          \
     } while (0)
 
@@ -291,7 +262,7 @@ __global__ __launch_bounds__(512) void conv_dw_rows_kernel(CdwParams p) {
     //      A pieces 0..15 (wave w: 2w, 2w+1), X pieces 0..16 (wave w: 2w, 2w+1; wave 0 also 16 = rows 64..67, of which 64, 65 count) ----
     const int d_r = lane >> 4, d_pc = lane & 15;
     auto src_col = [&](int row) { return ((((d_pc >> 1) ^ tn_swz(row)) << 1) | (d_pc & 1)) * 8; };
-    const unsigned lds_base = (unsigned)(size_t)(tn_lds_ptr_t)smem;
+    const unsigned lds_base = lds_addr(smem);
     auto issue_stage = [&](int stage, int64_t seg) {
         // segment -> (image row id = b * H + oy, ox0): wave-uniform
         const unsigned sg = (unsigned)seg;
@@ -307,7 +278,7 @@ __global__ __launch_bounds__(512) void conv_dw_rows_kernel(CdwParams p) {
         for (int q = 0; q < 2; ++q) {
             const int n = wave * 2 + q;
             const int r = n * 4 + d_r;
-            tn_dma16(p.A + (t0 + r) * p.lda + i0 + src_col(r), __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(stage * STAGE + n * 1024)));
+            dma16_to_lds(p.A + (t0 + r) * p.lda + i0 + src_col(r), __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(stage * STAGE + n * 1024)));
         }
         const int nx = wave == 0 ? 3 : 2;
         for (int q = 0; q < nx; ++q) {
@@ -316,7 +287,7 @@ __global__ __launch_bounds__(512) void conv_dw_rows_kernel(CdwParams p) {
             const int ix = ox0 - 1 + r;
             const void* g = g_tn_zero;
             if (row_ok && r < 66 && ix >= 0 && ix < p.W) g = xrow + (int64_t)r * p.Cin + src_col(r);
-            tn_dma16(g, __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(stage * STAGE + A_TILE + n * 1024)));
+            dma16_to_lds(g, __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(stage * STAGE + A_TILE + n * 1024)));
         }
     };
 
@@ -345,7 +316,6 @@ __global__ __launch_bounds__(512) void conv_dw_rows_kernel(CdwParams p) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[kx][i][j] = (float4_t){0.f, 0.f, 0.f, 0.f};
 
-    typedef __attribute__((address_space(3))) bf16x4_t* lds_v4_t;
     const bool do_colsum = p.colsum != nullptr && ky == 1 && tc == 0 && wc == 0;   // wave-uniform
     float csum[4] = {0.f, 0.f, 0.f, 0.f};
     const bf16x2_t ones2 = {(__bf16)1.0f, (__bf16)1.0f};
@@ -384,9 +354,9 @@ __global__ __launch_bounds__(512) void conv_dw_rows_kernel(CdwParams p) {
                 bf16x8_t bf[2];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    bf16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4_t)(tn_lds_ptr_t)(st + b_off[kx][0][j] + ks * (32 * ROWB)));
-                    bf16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4_t)(tn_lds_ptr_t)(st + b_off[kx][1][j] + ks * (32 * ROWB)));
-                    if (relu) { lo_ = tn_relu4(lo_); hi_ = tn_relu4(hi_); }
+                    bf16x4_t lo_ = lds_read_tr16(st + b_off[kx][0][j] + ks * (32 * ROWB));
+                    bf16x4_t hi_ = lds_read_tr16(st + b_off[kx][1][j] + ks * (32 * ROWB));
+                    if (relu) { lo_ = relu_bf16x4(lo_); hi_ = relu_bf16x4(hi_); }
                     bf[j] = __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7);
                 }
 #pragma unroll

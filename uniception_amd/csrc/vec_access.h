@@ -8,13 +8,12 @@
 
 struct Vec8 { float v[8]; };
 
-typedef _Float16 uc_half2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pack_f16x2(float lo, float hi) {       // round-to-nearest-even, like torch's Half
     const float2v_t v = {uc_sat_f16(lo), uc_sat_f16(hi)};            // (saturating: see common.h)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, uc_half2_t));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, half2v_t));
 }
 __device__ __forceinline__ void unpack_f16x2(unsigned u, float& lo, float& hi) {
-    const float2v_t v = __builtin_convertvector(__builtin_bit_cast(uc_half2_t, u), float2v_t);
+    const float2v_t v = __builtin_convertvector(__builtin_bit_cast(half2v_t, u), float2v_t);
     lo = v.x; hi = v.y;
 }
 // four bf16 as they lie in memory -> fp32 (bf16 -> fp32 is a shift: common.h)
