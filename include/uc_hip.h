@@ -62,8 +62,10 @@ const char* uc_last_error(void);
  *       uc_diff_attention_combine_ws_bytes added (nothing existing changed).
  *   18: token pooling of the summary heads — uc_token_pool, uc_token_pool_ws_bytes, uc_token_pool_bwd added (nothing existing changed).
  *   19: the MoGe head's channels-last passes — uc_group_norm_nhwc (+ _bwd, two _ws_bytes queries), uc_replicate_pad_nhwc (+ _bwd),
- *       uc_crop_add_nhwc, uc_crop_embed_nhwc, uc_resize_bilinear_nhwc (+ _bwd) added (nothing existing changed). */
-#define UC_ABI_VERSION 19
+ *       uc_crop_add_nhwc, uc_crop_embed_nhwc, uc_resize_bilinear_nhwc (+ _bwd) added (nothing existing changed).
+ *   20: the streaming steps of the non-image input encoders — uc_unshuffle_rows (+ _bwd), uc_act, uc_ln_pe_ln,
+ *       uc_ln_param_grads (+ _ws_bytes) added (nothing existing changed). */
+#define UC_ABI_VERSION 20
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -709,6 +711,47 @@ int uc_resize_bilinear_nhwc(const void* src, void* dst, int dtype, int B, int Hi
                             uc_stream_t stream);
 int uc_resize_bilinear_nhwc_bwd(const void* dy, void* dx, int dtype, int B, int Hi, int Wi, int C, int Ho, int Wo, int align_corners,
                                 uc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Streaming steps of the non-image input encoders (encoders/patch_embedder.py, dense_rep_encoder.py, global_rep_encoder.py).
+ * They allocate nothing; every reduction runs in a fixed order (the same bits on every run); every argument is checked before
+ * anything is launched (UC_ERR_BAD_ARG, message prefixed with the function name).
+ *
+ *   uc_unshuffle_rows:      nn.PixelUnshuffle(P) of an NCHW map as GEMM operand rows.  src [B, C, h P, w P] contiguous (UC_F32 |
+ *                           UC_BF16) -> dst rows [B h w, ld] (UC_F32 | UC_BF16), ld >= C P P:
+ *                             dst[(b h + i) w + j][c P P + u P + v] = src[b, c, i P + u, j P + v],  columns [C P P, ld) = 0
+ *                           (the zero columns are the K padding of the direct-to-LDS GEMM routes: ld % 64 == 0 there).
+ *                           uc_pixel_unshuffle is the adjoint of the linear head's pixel shuffle and has no leading dimension.
+ *   uc_unshuffle_rows_bwd:  its adjoint, a permutation: dst fp32 [B, C, h P, w P] <- rows [B h w, ld] (UC_F32 | UC_BF16); the pad
+ *                           columns are not read.
+ *   uc_act:                 y[i] = act(x[i]), i < n, act = UC_ACT_GELU_ERF (0.5 x (1 + erf(x / sqrt 2)), libm erff) | UC_ACT_RELU,
+ *                           x and y in `dtype` (UC_F32 | UC_BF16), evaluated in fp32; y == x (in place) is allowed.  The backward is
+ *                           uc_act_bwd on the saved x.
+ *   uc_ln_pe_ln:            one pass over the rows x [B N, C]:  y[b, n, :] = LN2(LN1(x[b, n, :]) + pe[n, :]).
+ *                           gamma1 == NULL: no LN1 (Identity, beta1 must be NULL too); pe == NULL: no table; gamma2 == NULL: no LN2;
+ *                           at least one of the three is present.  x: UC_F32 | UC_BF16; gamma, beta, pe [N, C]: fp32; y: UC_F32 |
+ *                           UC_BF16; mid (optional, fp32 [B N, C]): the input of LN2, which the backward of LN2 and the gradient of
+ *                           pe need.  Statistics are two-pass in fp32 (mean, then the squared deviations from it) per norm, eps1 / eps2
+ *                           > 0 where the norm is present.  One wavefront per row, the row held in registers (C % 4 == 0, C <= 2048
+ *                           and 16-byte aligned rows; any other C or alignment takes a scalar three-pass form).  A single norm
+ *                           without pe and without mid is handed to uc_layernorm: bit for bit its result.  The backward is uc_layernorm_bwd (LN2, on mid), uc_colsum
+ *                           over the batch ([B, N C]) for pe, uc_layernorm_bwd (LN1, on x), with uc_ln_param_grads for dgamma / dbeta.
+ * ---------------------------------------------------------------------------------- */
+int uc_unshuffle_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int B, int C, int h, int w, int P, int64_t ld,
+                      uc_stream_t stream);
+int uc_unshuffle_rows_bwd(const void* rows, int rows_dtype, float* dst, int B, int C, int h, int w, int P, int64_t ld, uc_stream_t stream);
+int uc_act(const void* x, void* y, int dtype, int act, int64_t n, uc_stream_t stream);
+/*   uc_ln_param_grads:      dgamma[c] = sum_r dy[r, c] x^[r, c], dbeta[c] = sum_r dy[r, c] of y = LN(x) over rows [rows, C] (x, dy:
+ *                           UC_F32 | UC_BF16; dgamma, dbeta: fp32, overwritten), every sum in one fixed order — row statistics per
+ *                           wavefront, 64-row slabs per column with rows ascending, slabs ascending — so the same bits on every run.
+ *                           uc_layernorm_bwd forms the same two sums with fp32 atomics (their last bits change from run to run); the
+ *                           backward of uc_ln_pe_ln takes dx from it and the parameter gradients from here.  ws: caller-provided,
+ *                           uc_ln_param_grads_ws_bytes(rows, C) bytes, 8-byte aligned; at most 65535 * 64 rows. */
+int64_t uc_ln_param_grads_ws_bytes(int64_t rows, int64_t C);
+int uc_ln_param_grads(const void* x, int x_dtype, const void* dy, int dy_dtype, float* dgamma, float* dbeta, float* ws, int64_t rows, int C,
+                      float eps, uc_stream_t stream);
+int uc_ln_pe_ln(const void* x, int x_dtype, const float* gamma1, const float* beta1, float eps1, const float* pe, const float* gamma2,
+                const float* beta2, float eps2, void* y, int y_dtype, float* mid, int64_t B, int64_t N, int C, uc_stream_t stream);
 
 #ifdef __cplusplus
 }

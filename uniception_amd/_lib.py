@@ -168,12 +168,18 @@ SIGNATURES = {
     "uc_crop_embed_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
     "uc_resize_bilinear_nhwc": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "uc_resize_bilinear_nhwc_bwd": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "uc_unshuffle_rows": [vp, i32, vp, i32, i32, i32, i32, i32, i32, i64, vp],
+    "uc_unshuffle_rows_bwd": [vp, i32, vp, i32, i32, i32, i32, i32, i64, vp],
+    "uc_act": [vp, vp, i32, i32, i64, vp],
+    "uc_ln_param_grads_ws_bytes": [i64, i64],
+    "uc_ln_param_grads": [vp, i32, vp, i32, vp, vp, vp, i64, i32, f32, vp],
+    "uc_ln_pe_ln": [vp, i32, vp, vp, f32, vp, vp, vp, f32, vp, i32, vp, i64, i64, i32, vp],
 }
 
 _lib = None
 
 
-ABI_VERSION = 19   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 20   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

@@ -1393,30 +1393,31 @@ def _head_weight_t(layers, dt, kp: int, npad: int):
     return _w_t(layers[0], ("head", kp, npad, len(layers)), tuple(l.weight for l in layers), build_2d, dt)
 
 
-def _head_linear_fwd(x2d, residual, layers, dt, out_dtype, relu: bool, npad: int, want_gate: bool):
-    """(y [M, npad], gate | None, the operand rows in dt).  gate is what the ReLU's backward reads: the output itself, or — under
-    a residual, where the output no longer tells — the pre-activation the same launch stores (uc_gemm preact_out)."""
+def _head_linear_fwd(x2d, residual, layers, dt, out_dtype, act: Optional[str], npad: int, want_gate: bool):
+    """(y [M, npad], gate | None, the operand rows in dt).  gate is what the activation's backward reads: for a ReLU the output itself,
+    or — under a residual, where the output no longer tells, and for a GELU always — the pre-activation the same launch stores
+    (uc_gemm preact_out)."""
     x2d = _c(x2d)
     xb = x2d if x2d.dtype == dt else ops.convert(x2d, dt)
     w, b = head_weights(layers, dt, xb.shape[1], npad)
-    if relu and residual is not None and want_gate:
+    if act is not None and want_gate and (residual is not None or act != "relu"):
         gate = torch.empty((xb.shape[0], npad), dtype=out_dtype, device=xb.device)
-        return ops.gemm(xb, w, b, act="relu", residual=residual, out_dtype=out_dtype, preact_out=gate), gate, xb
-    y = ops.gemm(xb, w, b, act="relu" if relu else None, residual=residual, out_dtype=out_dtype)
-    return y, (y if relu and want_gate else None), xb
+        return ops.gemm(xb, w, b, act=act, residual=residual, out_dtype=out_dtype, preact_out=gate), gate, xb
+    y = ops.gemm(xb, w, b, act=act, residual=residual, out_dtype=out_dtype)
+    return y, (y if act is not None and want_gate else None), xb
 
 
 @_sink_aware
 class HeadLinearFn(Function):
-    """y = [relu](x W^T + b) [+ residual] over padded widths, optionally followed by the mean over each sample's T rows
+    """y = [act](x W^T + b) [+ residual] (act: "relu" | "gelu" | None) over padded widths, optionally followed by the mean over each sample's T rows
     (pool = (B, T): the ResConvBlock's last convolution and the AdaptiveAvgPool2d(1) after it as one node, whose backward
     writes the ReLU-gated broadcast with uc_token_pool_bwd instead of storing the broadcast map first)."""
 
     @staticmethod
-    def forward(ctx, x2d, residual, layers, dt, out_dtype, relu, npad, pool, *params):
-        y, gate, xb = _head_linear_fwd(x2d, residual, layers, dt, dt if pool else out_dtype, relu, npad, True)
+    def forward(ctx, x2d, residual, layers, dt, out_dtype, act, npad, pool, *params):
+        y, gate, xb = _head_linear_fwd(x2d, residual, layers, dt, dt if pool else out_dtype, act, npad, True)
         ctx.save_for_backward(xb, gate)
-        ctx.layers, ctx.dt, ctx.relu, ctx.npad, ctx.pool, ctx.x_dtype = layers, dt, relu, npad, pool, x2d.dtype
+        ctx.layers, ctx.dt, ctx.act, ctx.npad, ctx.pool, ctx.x_dtype = layers, dt, act, npad, pool, x2d.dtype
         ctx.res_dtype = None if residual is None else residual.dtype
         return ops.token_pool(y, *pool) if pool else y
 
@@ -1429,15 +1430,15 @@ class HeadLinearFn(Function):
         if ctx.pool:
             T = ctx.pool[1]
             g = dy if dy.dtype == torch.float32 else ops.convert(dy, torch.float32)
-            du = ops.token_pool_bwd(g, T, dt, gate if ctx.relu else None)
+            du = ops.token_pool_bwd(g, T, dt, gate if ctx.act else None)
             if ctx.res_dtype is not None and ctx.needs_input_grad[1]:
                 dres = ops.token_pool_bwd(g, T, ctx.res_dtype)
         else:
             if ctx.res_dtype is not None and ctx.needs_input_grad[1]:
                 dres = dy if dy.dtype == ctx.res_dtype else ops.convert(dy, ctx.res_dtype)
             du = dy
-            if ctx.relu:
-                du = ops.act_bwd(dy if dy.dtype == gate.dtype else ops.convert(dy, gate.dtype), gate, "relu")
+            if ctx.act:
+                du = ops.act_bwd(dy if dy.dtype == gate.dtype else ops.convert(dy, gate.dtype), gate, ctx.act)
         du = _as_dt(_c(du), dt)
         kp = xb.shape[1]
         rows = [l.weight.shape[0] for l in layers]
@@ -1460,19 +1461,24 @@ class HeadLinearFn(Function):
         return (dx, dres, None, None, None, None, None, None) + tuple(grads)
 
 
-def head_linear(x2d, layers, dt, out_dtype=None, relu: bool = False, residual=None, npad: Optional[int] = None, pool=None):
+def head_linear(x2d, layers, dt, out_dtype=None, relu: bool = False, residual=None, npad: Optional[int] = None, pool=None, act: Optional[str] = None):
     """One layer of a summary head on padded widths (see above): x2d [M, Kp] -> [M, npad] in out_dtype (default dt), or the
     fp32 [B, npad] mean over each sample's T rows with pool = (B, T).  `layers`: one nn.Linear / 1x1 nn.Conv2d, or several
-    sharing the input (their outputs side by side).  Records a HeadLinearFn when a gradient is needed, else only launches."""
+    sharing the input (their outputs side by side).  relu / act="relu" | "gelu": the activation in the GEMM's epilogue (the GELU's
+    backward reads the pre-activation stored by the same launch, which needs Kp % 64 == 0; no pooled form).  Records a HeadLinearFn
+    when a gradient is needed, else only launches."""
     layers = tuple(layers)
+    act = act or ("relu" if relu else None)
     N, K = sum(l.weight.shape[0] for l in layers), layers[0].weight[0].numel()
     npad = head_pad(N) if npad is None else npad
     if x2d.shape[1] < K or npad < N or (residual is not None and residual.shape[1] != npad):
         raise UcHipError(f"head_linear: operand width {x2d.shape[1]} / padded output width {npad} do not fit a [{N}, {K}] layer")
+    if act not in (None, "relu", "gelu") or (pool and act == "gelu"):
+        raise UcHipError(f"head_linear: act={act!r}{' with a pooled output' if pool else ''} has no HIP path")
     params = tuple(t for l in layers for t in (l.weight, l.bias))
     if grad_needed(x2d, residual, *params):
-        return HeadLinearFn.apply(x2d, residual, layers, dt, out_dtype or dt, relu, npad, pool, *params)
-    y, _, _ = _head_linear_fwd(x2d, residual, layers, dt, dt if pool else (out_dtype or dt), relu, npad, False)
+        return HeadLinearFn.apply(x2d, residual, layers, dt, out_dtype or dt, act, npad, pool, *params)
+    y, _, _ = _head_linear_fwd(x2d, residual, layers, dt, dt if pool else (out_dtype or dt), act, npad, False)
     return ops.token_pool(y, *pool) if pool else y
 
 
@@ -1609,16 +1615,19 @@ def _conv3x3_padded_rot_weight(conv, dt, cin_pad: int, cout_pad: int):
 @_sink_aware
 class Conv3x3PaddedFn(Function):
     """Zero-padded 3x3 convolution (stride 1) of an NHWC map whose channel count was padded with zero channels to `cin_pad`, to
-    `cout_pad` output channels (zero weight rows): the output block's Conv2d(64 + 2 -> 32) and Conv2d(32 -> dim_out, 3)."""
+    `cout_pad` output channels (zero weight rows): the output block's Conv2d(64 + 2 -> 32) and Conv2d(32 -> dim_out, 3).  residual
+    [B, H, W, cout_pad] (optional) is added in the epilogue (the dense encoder's ResidualBlock: conv2 + shortcut)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, conv, cout_pad, out_dtype):
+    def forward(ctx, x, weight, bias, conv, cout_pad, out_dtype, residual=None):
         x = _c(x)
         B, H, W, cin_pad = x.shape
         w, b = _conv3x3_padded_weights(conv, x.dtype, cin_pad, cout_pad)
         ctx.save_for_backward(x)
         ctx.meta = (conv, cout_pad, bias is not None)
-        return ops.gemm(x, w, b, conv=(B, H, W, cin_pad, 1), out_dtype=out_dtype).view(B, H, W, cout_pad)
+        ctx.res_dtype = None if residual is None else residual.dtype
+        r = None if residual is None else _c(residual).reshape(-1, cout_pad)
+        return ops.gemm(x, w, b, residual=r, conv=(B, H, W, cin_pad, 1), out_dtype=out_dtype).view(B, H, W, cout_pad)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1636,7 +1645,10 @@ class Conv3x3PaddedFn(Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.gemm(dz, _conv3x3_padded_rot_weight(conv, dt, cin_pad, cout_pad), conv=(B, H, W, cout_pad, 1)).view(B, H, W, cin_pad)
-        return dx, dW, (db[:conv.out_channels] if has_b else None), None, None, None
+        dres = None
+        if ctx.res_dtype is not None and ctx.needs_input_grad[6]:
+            dres = dy if dy.dtype == ctx.res_dtype else _as_dt(dy, ctx.res_dtype)
+        return dx, dW, (db[:conv.out_channels] if has_b else None), None, None, None, dres
 
 
 @_sink_aware
@@ -1855,3 +1867,134 @@ class MlpFn(Function):
 
 def mlp(x2d, fc1, fc2, act, dt, drops=None):
     return MlpFn.apply(x2d, fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc1, fc2, act, dt, drops)
+
+
+# =================================================================================================================
+# Non-image input encoders (encoders/patch_embedder.py, dense_rep_encoder.py, global_rep_encoder.py): PixelUnshuffle as operand rows,
+# the activation around the residual sum, and LN2(LN1(x) + pe) in one pass.  Channel counts are zero-padded to ENC_PAD (the Cin % 64 /
+# K % 64 granule of the direct-to-LDS routes) in the prepared weights and in the activations; zero weight rows and zero bias entries
+# keep the padded channels exactly zero through bias, GELU(0) = ReLU(0) = 0 and the residual sum.
+# =================================================================================================================
+ENC_PAD = 64
+
+
+@_sink_aware
+class UnshuffleRowsFn(Function):
+    "rows [B h w, ld] in dt = PixelUnshuffle(P)(img [B, C, h P, w P]), columns beyond C P P zero; the backward is the inverse permutation"
+
+    @staticmethod
+    def forward(ctx, img, P, ld, dt):
+        ctx.geom = (tuple(img.shape), P, img.dtype)
+        img = _c(img if img.dtype in (torch.float32, torch.bfloat16) else img.float())
+        return ops.unshuffle_rows(img, P, ld, dt)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (B, Cn, H, W), P, idt = ctx.geom
+        dimg = ops.unshuffle_rows_bwd(_c(dy), B, Cn, H // P, W // P, P)
+        return (dimg if idt == torch.float32 else dimg.to(idt)), None, None, None
+
+
+def unshuffle_rows(img, P: int, ld: int, dt):
+    if grad_needed(img):
+        return UnshuffleRowsFn.apply(img, P, ld, dt)
+    return ops.unshuffle_rows(_c(img if img.dtype in (torch.float32, torch.bfloat16) else img.float()), P, ld, dt)
+
+
+@_sink_aware
+class ActFn(Function):
+    "y = act(u) as a pass of its own (the activation AFTER a residual sum; uc_gemm's epilogues apply theirs before it); saves u"
+
+    @staticmethod
+    def forward(ctx, u, name):
+        u = _c(u)
+        ctx.save_for_backward(u)
+        ctx.name = name
+        return ops.act(u, name)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (u,) = ctx.saved_tensors
+        return ops.act_bwd(_as_dt(_c(dy), u.dtype), u, ctx.name), None
+
+
+def act(u, name: str):
+    "act(u), name in ('gelu', 'relu'); without a graph the pass runs in place on u (which must be the caller's own temporary)"
+    if grad_needed(u):
+        return ActFn.apply(u, name)
+    u = _c(u)
+    return ops.act(u, name, out=u)
+
+
+def conv3x3_padded(x, conv, cout_pad: int, out_dtype=None, residual=None):
+    "Conv2d(k=3, padding=1) on an NHWC map with zero-padded channel counts (Conv3x3PaddedFn), residual added in the epilogue"
+    if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
+            or conv.padding_mode != "zeros":
+        raise UcHipError("conv3x3_padded: only a dense zero-padded 3x3 convolution of stride 1 has a HIP path")
+    return Conv3x3PaddedFn.apply(x, conv.weight, conv.bias, conv, cout_pad, out_dtype or x.dtype, residual)
+
+
+def _ln_args(ln):
+    "(gamma, beta, eps) fp32 of an nn.LayerNorm, None for Identity / None"
+    if ln is None or isinstance(ln, nn.Identity):
+        return None
+    g, b = engine.ln_params(ln)
+    return g, b, ln.eps
+
+
+@_sink_aware
+class LnPeLnFn(Function):
+    """y = LN2(LN1(x) + pe) over rows [B N, C] in one kernel (uc_ln_pe_ln), each step optional.  The backward is composed:
+    uc_layernorm_bwd on the saved LN2 input, uc_colsum over the batch ([B, N C]) for pe, uc_layernorm_bwd on x.  The one case the
+    existing kernels cannot express is a REPRODUCIBLE dgamma / dbeta (uc_layernorm_bwd adds them with fp32 atomics): those come from
+    uc_ln_param_grads, in a fixed order, and uc_layernorm_bwd's own are discarded."""
+
+    @staticmethod
+    def forward(ctx, x2d, pe, g1, b1, g2, b2, B, N, eps1, eps2, out_dtype):
+        x2d = _c(x2d)
+        if x2d.dtype not in (torch.float32, torch.bfloat16):
+            raise UcHipError("ln_pe_ln: the token rows are fp32 or bf16")
+        f = lambda t: None if t is None else t.detach().float().contiguous()      # noqa: E731
+        pe_, g1_, b1_, g2_, b2_ = f(pe), f(g1), f(b1), f(g2), f(b2)
+        ln1 = None if g1 is None else (g1_, b1_, eps1)
+        ln2 = None if g2 is None else (g2_, b2_, eps2)
+        if ln2 is not None:
+            y, mid = ops.ln_pe_ln(x2d, B, N, ln1, pe_, ln2, out_dtype, want_mid=True)
+        else:
+            y, mid = ops.ln_pe_ln(x2d, B, N, ln1, pe_, None, out_dtype), None
+        ctx.save_for_backward(x2d if ln1 is not None else None, mid, g1_, g2_)
+        ctx.meta = (B, N, eps1, eps2, x2d.dtype, pe is not None and tuple(pe.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2d, mid, g1, g2 = ctx.saved_tensors
+        B, N, eps1, eps2, x_dtype, pe_shape = ctx.meta
+        d = _c(dy)
+        dg1 = db1 = dg2 = db2 = dpe = None
+        if g2 is not None:
+            dg2, db2 = ops.ln_param_grads(mid, d, eps2)
+            d = ops.layernorm_bwd(mid, g2, d, eps2, torch.zeros_like(g2), torch.zeros_like(g2))       # fp32 (mid's dtype)
+        if pe_shape and ctx.needs_input_grad[1]:
+            d32 = d if d.dtype == torch.float32 else ops.convert(d, torch.float32)
+            dpe = _colsum(d32.view(B, -1)).view(pe_shape)
+        if g1 is not None:
+            dg1, db1 = ops.ln_param_grads(x2d, d, eps1)
+            dx = ops.layernorm_bwd(x2d, g1, d, eps1, torch.zeros_like(g1), torch.zeros_like(g1))
+        else:
+            dx = d if d.dtype == x_dtype else ops.convert(d, x_dtype)
+        return dx, dpe, dg1, db1, dg2, db2, None, None, None, None, None
+
+
+def ln_pe_ln(x2d, B: int, N: int, ln1, pe, ln2, out_dtype=torch.float32):
+    """LN2(LN1(x2d) + pe): ln1 / ln2 an nn.LayerNorm, nn.Identity or None; pe [N, C] (any float dtype; may require grad) or None.
+    With nothing to apply the rows are returned as they are (converted to out_dtype)."""
+    a1, a2 = _ln_args(ln1), _ln_args(ln2)
+    if a1 is None and a2 is None and pe is None:
+        return x2d if x2d.dtype == out_dtype else convert(x2d, out_dtype)
+    p1 = (ln1.weight, ln1.bias) if a1 is not None else (None, None)
+    p2 = (ln2.weight, ln2.bias) if a2 is not None else (None, None)
+    if grad_needed(x2d, pe, *p1, *p2):
+        return LnPeLnFn.apply(x2d, pe, p1[0], p1[1], p2[0], p2[1], B, N, a1[2] if a1 else 0.0, a2[2] if a2 else 0.0, out_dtype)
+    pe_ = None if pe is None else (pe if pe.dtype == torch.float32 and pe.is_contiguous() else pe.float().contiguous())
+    return ops.ln_pe_ln(_c(x2d), B, N, a1, pe_, a2, out_dtype)

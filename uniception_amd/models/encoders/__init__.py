@@ -1,15 +1,21 @@
-"""Encoder factory, restricted to the encoders on the DUSt3R path (reference: encoders/__init__.py:32-117)."""
+"""Encoder factory, restricted to the encoders with a HIP path (reference: encoders/__init__.py:32-140)."""
 from .base import (EncoderGlobalRepInput, EncoderGlobalRepOutput, EncoderInput, EncoderOutput, UniCeptionEncoderBase,  # noqa: F401
                    UniCeptionViTEncoderBase, ViTEncoderInput, ViTEncoderNonImageInput, ViTEncoderOutput)
 from .croco import CroCoEncoder, CroCoIntermediateFeatureReturner
+from .dense_rep_encoder import DenseRepresentationEncoder, ResidualBlock  # noqa: F401
 from .dinov2 import DINOv2Encoder, DINOv2IntermediateFeatureReturner
+from .global_rep_encoder import GlobalRepresentationEncoder
 from .image_normalizations import IMAGE_NORMALIZATION_DICT  # noqa: F401
+from .patch_embedder import PatchEmbedder
 
 ENCODER_CONFIGS = {
     "croco": {"class": CroCoEncoder, "intermediate_feature_returner_class": CroCoIntermediateFeatureReturner,
               "supported_models": ["CroCov2", "DUSt3R", "MASt3R"]},
+    "dense_rep_encoder": {"class": DenseRepresentationEncoder, "supported_models": ["Dense-Representation-Encoder"]},
     "dinov2": {"class": DINOv2Encoder, "intermediate_feature_returner_class": DINOv2IntermediateFeatureReturner,
                "supported_models": ["DINOv2", "DINOv2-Registers", "DINOv2-Depth-Anythingv2"]},
+    "global_rep_encoder": {"class": GlobalRepresentationEncoder, "supported_models": ["Global-Representation-Encoder"]},
+    "patch_embedder": {"class": PatchEmbedder, "supported_models": ["Patch-Embedder"]},
 }
 
 

@@ -17,5 +17,6 @@ _TABLE = {
     "croco": _IMAGENET,
     "dust3r": ([0.5, 0.5, 0.5], [0.5, 0.5, 0.5]),
     "dinov2": _IMAGENET,
+    "patch_embedder": _IMAGENET,
 }
 IMAGE_NORMALIZATION_DICT = {k: ImageNormalization(mean=torch.tensor(m), std=torch.tensor(s)) for k, (m, s) in _TABLE.items()}

@@ -1360,3 +1360,75 @@ def resize_bilinear_nhwc_bwd(dy: torch.Tensor, Hi: int, Wi: int, align_corners: 
     _lib.check(_lib.load().uc_resize_bilinear_nhwc_bwd(dy.data_ptr(), dx.data_ptr(), _dt(dy.dtype), B, Hi, Wi, Cn, Ho, Wo,
                                                        1 if align_corners else 0, _stream()), "uc_resize_bilinear_nhwc_bwd")
     return dx
+
+
+# --------------------------------------------------------------------------------------------
+# streaming steps of the non-image input encoders (csrc/input_encoders.hip)
+# --------------------------------------------------------------------------------------------
+def unshuffle_rows(x: torch.Tensor, P: int, ld: int, out_dtype: torch.dtype) -> torch.Tensor:
+    """nn.PixelUnshuffle(P) of x [B,C,h*P,w*P] (fp32 | bf16, contiguous) as rows [B*h*w, ld] in out_dtype: column c*P*P + u*P + v,
+    columns [C*P*P, ld) zero (the K padding of the GEMM that reads the rows)."""
+    _need_gpu(x)
+    assert x.dim() == 4 and x.is_contiguous() and x.shape[2] % P == 0 and x.shape[3] % P == 0 and ld >= x.shape[1] * P * P
+    B, Cn, H, W = x.shape
+    h, w = H // P, W // P
+    y = torch.empty((B * h * w, ld), dtype=out_dtype, device=x.device)
+    _lib.check(_lib.load().uc_unshuffle_rows(x.data_ptr(), _dt(x.dtype), y.data_ptr(), _dt(out_dtype), B, Cn, h, w, P, ld, _stream()),
+               "uc_unshuffle_rows")
+    return y
+
+
+def unshuffle_rows_bwd(rows: torch.Tensor, B: int, Cn: int, h: int, w: int, P: int) -> torch.Tensor:
+    "adjoint of unshuffle_rows: rows [B*h*w, ld] (fp32 | bf16) -> fp32 [B,C,h*P,w*P]"
+    _need_gpu(rows)
+    assert rows.dim() == 2 and rows.is_contiguous() and rows.shape[0] == B * h * w and rows.shape[1] >= Cn * P * P
+    y = torch.empty((B, Cn, h * P, w * P), dtype=torch.float32, device=rows.device)
+    _lib.check(_lib.load().uc_unshuffle_rows_bwd(rows.data_ptr(), _dt(rows.dtype), y.data_ptr(), B, Cn, h, w, P, rows.shape[1], _stream()),
+               "uc_unshuffle_rows_bwd")
+    return y
+
+
+def act(x: torch.Tensor, name: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    "act(x) for name in ('gelu', 'relu') (exact-erf GELU), fp32 | bf16; out=x works in place"
+    _need_gpu(x, out)
+    if name not in ("gelu", "relu"):
+        raise UcHipError(f"act: {name!r} has no kernel (supported: 'gelu', 'relu')")
+    assert x.is_contiguous()
+    y = torch.empty_like(x) if out is None else out
+    assert y.is_contiguous() and y.shape == x.shape and y.dtype == x.dtype
+    _lib.check(_lib.load().uc_act(x.data_ptr(), y.data_ptr(), _dt(x.dtype), ACT[name], x.numel(), _stream()), "uc_act")
+    return y
+
+
+def ln_pe_ln(x: torch.Tensor, B: int, N: int, ln1: Optional[Tuple[torch.Tensor, torch.Tensor, float]], pe: Optional[torch.Tensor],
+             ln2: Optional[Tuple[torch.Tensor, torch.Tensor, float]], out_dtype: torch.dtype, want_mid: bool = False):
+    """y = LN2(LN1(x) + pe) over rows x [B*N, C] (fp32 | bf16) in one pass; ln1 / ln2: (gamma, beta, eps) fp32 or None (Identity),
+    pe: fp32 [N, C] or None.  Returns y, or (y, mid) with want_mid: mid fp32 [B*N, C] is the input of LN2."""
+    f32 = [t for n in (ln1, ln2) if n is not None for t in n[:2]] + ([pe] if pe is not None else [])
+    _need_gpu(x, *f32)
+    Cn = x.shape[-1]
+    assert x.dim() == 2 and x.is_contiguous() and x.shape[0] == B * N
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in f32) and all(t.numel() == Cn for n in (ln1, ln2) if n is not None for t in n[:2])
+    assert pe is None or pe.shape == (N, Cn)
+    y = torch.empty((B * N, Cn), dtype=out_dtype, device=x.device)
+    mid = torch.empty((B * N, Cn), dtype=torch.float32, device=x.device) if want_mid else None
+    g1, b1, e1 = ln1 if ln1 is not None else (None, None, 0.0)
+    g2, b2, e2 = ln2 if ln2 is not None else (None, None, 0.0)
+    _lib.check(_lib.load().uc_ln_pe_ln(x.data_ptr(), _dt(x.dtype), _p(g1), _p(b1), float(e1), _p(pe), _p(g2), _p(b2), float(e2), y.data_ptr(),
+                                       _dt(out_dtype), _p(mid), B, N, Cn, _stream()), "uc_ln_pe_ln")
+    return (y, mid) if want_mid else y
+
+
+def ln_param_grads(x: torch.Tensor, dy: torch.Tensor, eps: float):
+    """(dgamma, dbeta) fp32 [C] of y = LN(x) over rows x [rows, C] with cotangent dy (fp32 | bf16 each), every sum in a fixed order:
+    the same bits on every run (uc_layernorm_bwd's atomics do not give that)."""
+    _need_gpu(x, dy)
+    assert x.dim() == 2 and x.is_contiguous() and dy.is_contiguous() and dy.shape == x.shape
+    rows, Cn = x.shape
+    lib = _lib.load()
+    dg = torch.empty(Cn, dtype=torch.float32, device=x.device)
+    db = torch.empty(Cn, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(2, lib.uc_ln_param_grads_ws_bytes(rows, Cn) // 4), dtype=torch.float32, device=x.device)
+    _lib.check(lib.uc_ln_param_grads(x.data_ptr(), _dt(x.dtype), dy.data_ptr(), _dt(dy.dtype), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), rows, Cn,
+                                     float(eps), _stream()), "uc_ln_param_grads")
+    return dg, db
