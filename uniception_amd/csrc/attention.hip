@@ -1,19 +1,12 @@
-// Fused scaled-dot-product attention (no mask, no dropout) for gfx950.
+// Fused scaled-dot-product attention for gfx950.
 //
 // attn_bf16_kernel — flash-style, head_dim 64, v_mfma_f32_32x32x16_bf16.
-//   Workgroup = 4 wavefronts = 128 query rows of one (batch, head); each wave owns 32 queries.
-//   Per 64-key tile:   S^T[key,q] = K . Q^T   (A = K rows from LDS, B = Q^T held in registers)
-//   The swapped product puts a query's whole score column in ONE lane pair (lane, lane^32):
-//   row max / row sum are 31 in-register ops + one cross-half exchange; the running max,
-//   the rescale factor and the normaliser are lane-local scalars.
-//   P^T (bf16) in the S^T accumulator layout is directly the B operand of  O^T[d,q] += V^T . P^T
-//   when the key order inside each 16-key group is permuted the same way on the V side — which
-//   is what the "VT" layout (uc_hip.h) bakes into memory, so the A operand V^T[d, 8 keys] is one
-//   16-byte LDS read.  K and VT tiles are staged global -> VGPR -> LDS one tile ahead
-//   (double-buffered, XOR-swizzled 128-byte rows, one barrier per tile).
+//   Workgroup = 4 wavefronts = 128 query rows of one (batch, head); each wave owns 32 queries.  The per-key-tile step and its operand
+//   layout are those of attention_tile.h; here K and VT tiles are staged global -> VGPR -> LDS one tile ahead (double-buffered,
+//   XOR-swizzled 128-byte rows, one barrier per tile).
 //
 // attn_f32_kernel — verification mode: one thread per query row, fp32 FMA chains, expf.
-#include "mma_tile.h"
+#include "attention_tile.h"
 #include "knobs.h"
 #include "attention_p64.h"
 #include "attention_plan.h"
@@ -33,9 +26,6 @@ struct AttnParams {
     int prio_young;               // eight-wave workgroups: s_setprio 1 for waves 4-7 (the younger half loses every VALU arbitration to the older one)
     UcDropout drop;               // attention dropout (uc_attention_fwd with drop_p > 0; thr 0 elsewhere)
 };
-
-#define KV_TILE 64
-#define ATT_TILE_BYTES (KV_TILE * 128)  // 64 rows x 128 B
 
 // the body of attn_bf16_kernel for the 128 queries from q0w of (batch b, head h): also what attn_bf16_fixup_kernel recomputes a
 // flagged block of the persistent kernel with (attention_p64.h)
@@ -74,25 +64,7 @@ __device__ __forceinline__ void attn_bf16_body(const AttnParams& p, const int b,
         if (key >= p.Nk) key = p.Nk - 1;  // clamped keys are masked in the softmax
         return *reinterpret_cast<const uint4*>(Kb + (int64_t)key * p.k_sn + cc * 8);
     };
-    auto load_v = [&](int k0, int row) -> uint4 {
-        // VT tile: row = channel d, 8 key positions [k0 + 8cc, +8)
-        uint4 v = *reinterpret_cast<const uint4*>(VTb + (int64_t)row * p.npad + k0 + cc * 8);
-        if (k0 + KV_TILE > p.Nk) {  // tail tile: zero positions whose key is out of range (0 * garbage guard)
-            const int gbase = k0 + ((cc * 8) & ~15);
-            const int pbase = (cc * 8) & 15;
-            unsigned m0 = 0xffffffffu, m1 = 0xffffffffu, m2 = 0xffffffffu, m3 = 0xffffffffu;
-            if (gbase + vt_key_of_pos(pbase + 0) >= p.Nk) m0 &= 0xffff0000u;
-            if (gbase + vt_key_of_pos(pbase + 1) >= p.Nk) m0 &= 0x0000ffffu;
-            if (gbase + vt_key_of_pos(pbase + 2) >= p.Nk) m1 &= 0xffff0000u;
-            if (gbase + vt_key_of_pos(pbase + 3) >= p.Nk) m1 &= 0x0000ffffu;
-            if (gbase + vt_key_of_pos(pbase + 4) >= p.Nk) m2 &= 0xffff0000u;
-            if (gbase + vt_key_of_pos(pbase + 5) >= p.Nk) m2 &= 0x0000ffffu;
-            if (gbase + vt_key_of_pos(pbase + 6) >= p.Nk) m3 &= 0xffff0000u;
-            if (gbase + vt_key_of_pos(pbase + 7) >= p.Nk) m3 &= 0x0000ffffu;
-            v.x &= m0; v.y &= m1; v.z &= m2; v.w &= m3;
-        }
-        return v;
-    };
+    auto load_v = [&](int k0, int row) -> uint4 { return att_load_vt_chunk(VTb, row, p.npad, k0, cc, p.Nk); };
 #define ATT_STAGE_LOAD(k0_)                 \
     do {                                    \
         rk0 = load_k((k0_), sr);            \
@@ -110,129 +82,47 @@ __device__ __forceinline__ void attn_bf16_body(const AttnParams& p, const int b,
         *reinterpret_cast<uint4*>(sk_ + ATT_TILE_BYTES) = rv0;                         \
         *reinterpret_cast<uint4*>(sk_ + ATT_TILE_BYTES + 32 * 128) = rv1;              \
     } while (0)
-    int r_off[4];   // fragment read offsets: row l31 (+32 via immediate), chunk 2*st+hi, st = 0..3 (K and VT tiles alike)
-#pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
+    int r_off[4];   // fragment read offsets (K and VT tiles alike)
+    att_frag_offsets(r_off, l31, hi);
 
-    float16_t o[2];   // O^T accumulators: d-block x (16 regs): d = 32*db + (r&3) + 8*(r>>2) + 4*hi, q = l31
+    float16_t o[2];   // O^T accumulators: d-block x (16 regs): d = att_frag_row(db, r, hi), q = l31
     o[0] = (float16_t)(0.f);
     o[1] = (float16_t)(0.f);
-    float m_run = -1e30f;   // running max of raw scores (shared by the lane pair)
+    float m_run = ATT_MASKED;   // running max of raw scores (shared by the lane pair)
     float l_run = 0.f;      // lane-partial running sum
-    const float c = p.scale * 1.44269504088896340736f;  // scale * log2(e)
+    const float c = p.scale * ATT_LOG2E;  // scale * log2(e)
     unsigned dk1 = 0, dk2 = 0;
     if constexpr (DROP) uc_drop_keys(p.drop, (unsigned)(b * p.H + h), dk1, dk2);
 
-    const int nt = (p.Nk + KV_TILE - 1) / KV_TILE;
+    const int nt = (p.Nk + ATT_KV_TILE - 1) / ATT_KV_TILE;
     ATT_STAGE_LOAD(0);
     ATT_STAGE_WRITE(0);
     __syncthreads();
 
     for (int t = 0; t < nt; ++t) {
         const int buf = t & 1;
-        const int k0 = t * KV_TILE;
-        if (t + 1 < nt) ATT_STAGE_LOAD(k0 + KV_TILE);
+        const int k0 = t * ATT_KV_TILE;
+        if (t + 1 < nt) ATT_STAGE_LOAD(k0 + ATT_KV_TILE);
         const char* sk = smem + buf * 2 * ATT_TILE_BYTES;
         const char* sv = sk + ATT_TILE_BYTES;
 
-        // ---- S^T = K . Q^T : two 32-key blocks, 4 k-steps (16 channels) each ----
         float16_t s[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            s[kb] = (float16_t)(0.f);
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(sk + r_off[st] + kb * (32 * 128));
-                s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[st], s[kb], 0, 0, 0);
-            }
-        }
-        // ---- mask the tail ----
-        if (k0 + KV_TILE > p.Nk) {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (key >= p.Nk) s[kb][r] = -1e30f;
-                }
-        }
+        att_scores_bf16(s, sk, r_off, qf);
+        if (k0 + ATT_KV_TILE > p.Nk) att_mask_tail(s, k0, p.Nk, hi);
         // ---- online softmax (per query = per lane pair) ----
-        float mt = s[0][0];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s[kb][r]);
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        // Deferred rescale: keep the old running max while no query of the wave grew by more than 2^RESCALE_LOG2 in the
-        // exp2 domain (P stays <= 2^8, exact in the final O/l ratio); the O/l rescale then runs on a wave-uniform branch.
-        const bool grow = (mt - m_run) * c > 8.0f;
-        if (__any(grow)) {
-            const float m_new = fmaxf(m_run, mt);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-        }
-        const float mc = m_run * c;
-        float psum = 0.f;
-        bf16x8_t pf[4];   // P^T B-operand fragments: slab g = 2*kb + half, 8 key slots per lane
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                float e[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    e[j] = __builtin_amdgcn_exp2f(fmaf(s[kb][hf * 8 + j], c, -mc));
-                    psum += e[j];
-                    if constexpr (DROP) {
-                        const int r = hf * 8 + j;
-                        const unsigned key = (unsigned)(k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi);
-                        e[j] = uc_drop_hash(dk1, dk2, (unsigned)(q0 + l31), key) >= p.drop.thr ? e[j] * p.drop.keep_scale : 0.f;
-                    }
-                }
-                union { bf16x8_t v; unsigned u[4]; } pk;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pk.u[j] = pack_bf16x2(e[2 * j], e[2 * j + 1]);
-                pf[kb * 2 + hf] = pk.v;
-            }
-        }
-        l_run += psum;
-
-        // ---- O^T += V^T . P^T : two 32-channel blocks x four 16-key slabs ----
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const bf16x8_t vf = *reinterpret_cast<const bf16x8_t*>(sv + r_off[g] + db * (32 * 128));
-                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[g], o[db], 0, 0, 0);
-            }
+        std::conditional_t<DROP, AttProbsBf16Drop, AttProbsBf16> pr;
+        if constexpr (DROP) { pr.k1 = dk1; pr.k2 = dk2; pr.q = (unsigned)(q0 + l31); pr.k0 = k0; pr.hi = hi; pr.drop = p.drop; }
+        att_softmax_step(s, m_run, l_run, o, c, pr);
+        att_pv_bf16(o, sv, r_off, pr.pf);
 
         if (t + 1 < nt) ATT_STAGE_WRITE(buf ^ 1);
         __syncthreads();
     }
 
-    // ---- normalise and store: lane holds 4 consecutive channels per (db, r>>2) ----
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
     const int q = q0 + l31;
-    if (p.lse && q < p.Nq && hi == 0) p.lse[((int64_t)b * p.H + h) * p.Nq + q] = m_run * p.scale + logf(l_tot);
-    if (q < p.Nq) {
-        bf16_t* op = (bf16_t*)p.O + (int64_t)b * p.o_sb + (int64_t)q * p.o_sn + (int64_t)h * p.o_sh;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int d = db * 32 + 8 * g4 + 4 * hi;
-                uint2 pk;
-                pk.x = pack_bf16x2(o[db][g4 * 4 + 0] * inv, o[db][g4 * 4 + 1] * inv);
-                pk.y = pack_bf16x2(o[db][g4 * 4 + 2] * inv, o[db][g4 * 4 + 3] * inv);
-                *reinterpret_cast<uint2*>(op + d) = pk;
-            }
-    }
+    att_store_lse(p.lse, (int64_t)b * p.H + h, p.Nq, q, hi, m_run, p.scale, l_tot);
+    if (q < p.Nq) att_store_rows_direct(o, 1.0f / l_tot, (bf16_t*)p.O + (int64_t)b * p.o_sb + (int64_t)q * p.o_sn + (int64_t)h * p.o_sh, hi);
 }
 
 __global__ __launch_bounds__(256) void attn_bf16_kernel(AttnParams p) {
@@ -350,35 +240,21 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_bf16_dma_kernel(AttnParams p)
         voff_k[i] = (unsigned)(((int64_t)rr * p.k_sn + cch * 8) * 2);
         voff_v[i] = (unsigned)(((int64_t)rr * p.npad + cch * 8) * 2);
     }
-    const unsigned kstep = (unsigned)(KV_TILE * p.k_sn * 2);   // bytes between key tiles of K
+    const unsigned kstep = (unsigned)(ATT_KV_TILE * p.k_sn * 2);   // bytes between key tiles of K
     auto issue_tile = [&](int t, int buf) {
         const unsigned dst = lds0 + (unsigned)(buf * 2 * ATT_TILE_BYTES + wave * (PW * 1024));
 #pragma unroll
         for (int i = 0; i < PW; ++i) {
             dma16_buf_to_lds(voff_k[i], srd_k, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + i * 1024));
-            dma16_buf_to_lds(voff_v[i], srd_v, (unsigned)t * (KV_TILE * 2), __builtin_amdgcn_readfirstlane(dst + ATT_TILE_BYTES + i * 1024));
+            dma16_buf_to_lds(voff_v[i], srd_v, (unsigned)t * (ATT_KV_TILE * 2), __builtin_amdgcn_readfirstlane(dst + ATT_TILE_BYTES + i * 1024));
         }
     };
 
-    // ---- Q: the wave's 32 query rows (128 B each) arrive by DMA too — 4 instructions of 8 whole rows instead of 4 loads
-    //      that touch 32 rows x 32 B each (the vector memory path pays per row segment) — into the second stage buffer,
-    //      which the K/VT ring only needs from tile 1 on.  Rows beyond Nq fall outside the descriptor: zeros. ----
-    {
-        const unsigned long long qa = (unsigned long long)(Qb + (int64_t)q0 * p.q_sn);
-        const int64_t q_rows = min((int64_t)32, (int64_t)p.Nq - q0);
-        uint4_t srd_q = make_srd((const void*)qa);
-        srd_q.z = (unsigned)__builtin_amdgcn_readfirstlane((int)(q_rows > 0 ? ((q_rows - 1) * p.q_sn + 64) * 2 : 0));
-        const unsigned dstq = lds0 + (unsigned)(2 * ATT_TILE_BYTES + wave * 4096);     // waves 4..7 land behind the second stage
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rr = i * 8 + (lane >> 3);
-            const int cch = (lane & 7) ^ ((rr >> 1) & 7);
-            dma16_buf_to_lds((unsigned)(((int64_t)rr * p.q_sn + cch * 8) * 2), srd_q, 0u, __builtin_amdgcn_readfirstlane(dstq + i * 1024));
-        }
-    }
-    int r_off[4];   // fragment read offsets: row l31 (+32 via immediate), chunk 2*st+hi, st = 0..3 (K and VT tiles alike)
-#pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
+    // ---- Q: the wave's 32 query rows arrive by DMA too, into the second stage buffer, which the K/VT ring only needs from tile 1 on ----
+    //      (waves 4..7 land behind it)
+    att_q_rows_to_lds(Qb + (int64_t)q0 * p.q_sn, p.q_sn, (int64_t)p.Nq - q0, lds0 + (unsigned)(2 * ATT_TILE_BYTES + wave * 4096), lane);
+    int r_off[4];   // fragment read offsets (K and VT tiles alike)
+    att_frag_offsets(r_off, l31, hi);
 
     issue_tile(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -392,22 +268,24 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_bf16_dma_kernel(AttnParams p)
     float16_t o[2];
     o[0] = (float16_t)(0.f);
     o[1] = (float16_t)(0.f);
-    float m_run = -1e30f;
+    float m_run = ATT_MASKED;
     float l_run = 0.f;
-    const float c = p.scale * 1.44269504088896340736f;  // scale * log2(e)
+    const float c = p.scale * ATT_LOG2E;  // scale * log2(e)
     if constexpr (NW == 8) {
         // static priority for the second-dispatched half (MI355X_MICROARCH.md "Two waves per SIMD", item 4): one s_setprio before the
         // loop, no per-segment flips (`wave` is a readfirstlane value: the branch is scalar, s_setprio ignores EXEC)
         if (p.prio_young && wave >= 4) __builtin_amdgcn_s_setprio(1);
     }
 
-    const int nt = (p.Nk + KV_TILE - 1) / KV_TILE;
+    const int nt = (p.Nk + ATT_KV_TILE - 1) / ATT_KV_TILE;
     for (int t = 0; t < nt; ++t) {
         const int buf = t & 1;
         if (t + 1 < nt) issue_tile(t + 1, buf ^ 1);
         const char* sk = smem + buf * 2 * ATT_TILE_BYTES;
         const char* sv = sk + ATT_TILE_BYTES;
 
+        // The tile step and the LSE line below are written out, not taken from attention_tile.h: through its helpers (any of them, the
+        // two MFMA loops included) the scheduler orders this loop differently, +1 % on whole tiles (profiles/attention_tile_codegen.txt)
         float16_t s[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
@@ -418,13 +296,13 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_bf16_dma_kernel(AttnParams p)
                 s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[st], s[kb], 0, 0, 0);
             }
         }
-        if (t == nt - 1 && (p.Nk & (KV_TILE - 1))) {    // ragged last tile: keys >= Nk (zero K rows, zero VT pads) leave the softmax
-            const int k0 = t * KV_TILE;
+        if (t == nt - 1 && (p.Nk & (ATT_KV_TILE - 1))) {    // ragged last tile: keys >= Nk (zero K rows, zero VT pads) leave the softmax
+            const int k0 = t * ATT_KV_TILE;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= p.Nk) s[kb][r] = -1e30f;
+                    if (k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= p.Nk) s[kb][r] = ATT_MASKED;   // key k0 + att_frag_row(kb, r, hi)
         }
         float mt = s[0][0];
 #pragma unroll
@@ -475,30 +353,12 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_bf16_dma_kernel(AttnParams p)
         if constexpr (!(DBG & 1)) __syncthreads();                    // ... everyone's; and every wave is done reading tile t
     }
 
-    // ---- normalise; bounce the wave's 32 x 64 outputs through its private 4 KiB of the (now free) ring so that every
-    //      store instruction writes 8 whole 128-B rows instead of 32 rows x 16 B ----
+    // ---- normalise and store through the wave's private 4 KiB of the (now free) ring ----
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = __builtin_amdgcn_rcpf(l_tot);
     const int q = q0 + l31;
     if (p.lse && q < p.Nq && hi == 0) p.lse[((int64_t)b * p.H + h) * p.Nq + q] = m_run * p.scale + logf(l_tot);
-    char* ob = smem + wave * 4096;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            uint2 pk;       // channels 32db + 8g4 + 4hi .. +3 of query l31 = half of 16-B chunk 4db + g4
-            pk.x = pack_bf16x2(o[db][g4 * 4 + 0] * inv, o[db][g4 * 4 + 1] * inv);
-            pk.y = pack_bf16x2(o[db][g4 * 4 + 2] * inv, o[db][g4 * 4 + 3] * inv);
-            *reinterpret_cast<uint2*>(ob + l31 * 128 + (((4 * db + g4) ^ (l31 & 7)) << 4) + hi * 8) = pk;
-        }
-    bf16_t* obase = (bf16_t*)p.O + (int64_t)b * p.o_sb + (int64_t)h * p.o_sh;
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-        const int R = 8 * ps + (lane >> 3);
-        const int chunk = (lane & 7) ^ (R & 7);
-        const uint4 v = *reinterpret_cast<const uint4*>(ob + R * 128 + ((lane & 7) << 4));
-        if (q0 + R < p.Nq) *reinterpret_cast<uint4*>(obase + (int64_t)(q0 + R) * p.o_sn + chunk * 8) = v;
-    }
+    att_store_rows_bounced(o, inv, smem + wave * 4096, (bf16_t*)p.O + (int64_t)b * p.o_sb + (int64_t)h * p.o_sh, p.o_sn, q0, p.Nq, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -553,30 +413,18 @@ __global__ __launch_bounds__(512, 4) void attn_bf16_rs_kernel(AttnParams p) {
         voff_k = (unsigned)(((int64_t)rr * p.k_sn + cch * 8) * 2);
         voff_v = (unsigned)(((int64_t)rr * p.npad + cch * 8) * 2);
     }
-    const unsigned kstep = (unsigned)(KV_TILE * p.k_sn * 2);
+    const unsigned kstep = (unsigned)(ATT_KV_TILE * p.k_sn * 2);
     auto issue_k = [&](int t) {
         dma16_buf_to_lds(voff_k, srd_k, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * 2 * ATT_TILE_BYTES + wave * 1024)));
     };
     auto issue_v = [&](int t) {
-        dma16_buf_to_lds(voff_v, srd_v, (unsigned)t * (KV_TILE * 2),
+        dma16_buf_to_lds(voff_v, srd_v, (unsigned)t * (ATT_KV_TILE * 2),
                   __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((t & 1) * 2 * ATT_TILE_BYTES + ATT_TILE_BYTES + wave * 1024)));
     };
-    {   // Q rows of this wave into the second stage (waves 0-3) / the third region (waves 4-7)
-        const unsigned long long qa = (unsigned long long)(Qb + (int64_t)q0 * p.q_sn);
-        const int64_t q_rows = min((int64_t)32, (int64_t)p.Nq - q0);
-        uint4_t srd_q = make_srd((const void*)qa);
-        srd_q.z = (unsigned)__builtin_amdgcn_readfirstlane((int)(q_rows > 0 ? ((q_rows - 1) * p.q_sn + 64) * 2 : 0));
-        const unsigned dstq = lds0 + (unsigned)(2 * ATT_TILE_BYTES + wave * 4096);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rr = i * 8 + (lane >> 3);
-            const int cch = (lane & 7) ^ ((rr >> 1) & 7);
-            dma16_buf_to_lds((unsigned)(((int64_t)rr * p.q_sn + cch * 8) * 2), srd_q, 0u, __builtin_amdgcn_readfirstlane(dstq + i * 1024));
-        }
-    }
+    // Q rows of this wave into the second stage (waves 0-3) / the third region (waves 4-7)
+    att_q_rows_to_lds(Qb + (int64_t)q0 * p.q_sn, p.q_sn, (int64_t)p.Nq - q0, lds0 + (unsigned)(2 * ATT_TILE_BYTES + wave * 4096), lane);
     int r_off[4];
-#pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
+    att_frag_offsets(r_off, l31, hi);
 
     issue_k(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -591,86 +439,33 @@ __global__ __launch_bounds__(512, 4) void attn_bf16_rs_kernel(AttnParams p) {
     o[1] = (float16_t)(0.f);
     sc[0] = (float16_t)(0.f);
     sc[1] = (float16_t)(0.f);
-    bf16x8_t pf[4];
+    AttProbsBf16 pr;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) pf[g] = (bf16x8_t)(0.f);
-    float m_run = -1e30f;
+    for (int g = 0; g < 4; ++g) pr.pf[g] = (bf16x8_t)(0.f);
+    float m_run = ATT_MASKED;
     float l_run = 0.f;
-    const float c = p.scale * 1.44269504088896340736f;
-    const int nt = (p.Nk + KV_TILE - 1) / KV_TILE;
+    const float c = p.scale * ATT_LOG2E;
+    const int nt = (p.Nk + ATT_KV_TILE - 1) / ATT_KV_TILE;
     auto issue = [&](int t) __attribute__((always_inline)) {       // start of even segment 2t: VT(t) and K(t+1) set out
         if (t < nt) issue_v(t);
         if (t + 1 < nt) issue_k(t + 1);
     };
     auto matrix = [&](int t) __attribute__((always_inline)) {      // O += VT(t-1) P(t-1); S = K(t) Q^T
-        if (t >= 1) {
-            const char* sv = smem + ((t - 1) & 1) * 2 * ATT_TILE_BYTES + ATT_TILE_BYTES;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const bf16x8_t vf = *reinterpret_cast<const bf16x8_t*>(sv + r_off[g] + db * (32 * 128));
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[g], o[db], 0, 0, 0);
-                }
-        }
-        if (t < nt) {
-            const char* sk = smem + (t & 1) * 2 * ATT_TILE_BYTES;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                sc[kb] = (float16_t)(0.f);
-#pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(sk + r_off[st] + kb * (32 * 128));
-                    sc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[st], sc[kb], 0, 0, 0);
-                }
-            }
-        }
+        if (t >= 1) att_pv_bf16(o, smem + ((t - 1) & 1) * 2 * ATT_TILE_BYTES + ATT_TILE_BYTES, r_off, pr.pf);
+        if (t < nt) att_scores_bf16(sc, smem + (t & 1) * 2 * ATT_TILE_BYTES, r_off, qf);
     };
     auto vector = [&](int t) __attribute__((always_inline)) {      // softmax of tile t: sc -> pf
-        if (t == nt - 1 && (p.Nk & (KV_TILE - 1))) {
-            const int k0 = t * KV_TILE;
+        if (t == nt - 1 && (p.Nk & (ATT_KV_TILE - 1))) {    // att_mask_tail as branches on a copy: with the shared select form this kernel spills 22 VGPRs
 #pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
+            for (int kb = 0; kb < 2; ++kb) {
+                float16_t v = sc[kb];
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= p.Nk) sc[kb][r] = -1e30f;
-        }
-        float mt = sc[0][0];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mt = fmaxf(mt, sc[kb][r]);
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        const bool grow = (mt - m_run) * c > 8.0f;     // deferred rescale, see attn_bf16_kernel (PV of tile t-1 is complete)
-        if (__any(grow)) {
-            const float m_new = fmaxf(m_run, mt);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-        }
-        const float mc = m_run * c;
-        float psum = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                float e[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    e[j] = __builtin_amdgcn_exp2f(fmaf(sc[kb][hf * 8 + j], c, -mc));
-                    psum += e[j];
-                }
-                union { bf16x8_t v; unsigned u[4]; } pk;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pk.u[j] = pack_bf16x2(e[2 * j], e[2 * j + 1]);
-                pf[kb * 2 + hf] = pk.v;
+                    if (t * ATT_KV_TILE + att_frag_row(kb, r, hi) >= p.Nk) v[r] = ATT_MASKED;
+                sc[kb] = v;
             }
         }
-        l_run += psum;
+        att_softmax_step(sc, m_run, l_run, o, c, pr);      // (the deferred rescale finds PV of tile t-1 complete)
     };
     // two loops with the same barrier sequence (2 nt + 2 segments), one segment apart: a single loop with a role switch keeps the
     // union of both roles' registers alive across its back edge (468 bytes of scratch at the 128-register budget)
@@ -699,28 +494,10 @@ __global__ __launch_bounds__(512, 4) void attn_bf16_rs_kernel(AttnParams p) {
         }
     }
 
+    // ---- normalise and store through the wave's private 4 KiB of the (now free) ring ----
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = __builtin_amdgcn_rcpf(l_tot);
-    const int q = q0 + l31;
-    if (p.lse && q < p.Nq && hi == 0) p.lse[((int64_t)b * p.H + h) * p.Nq + q] = m_run * p.scale + logf(l_tot);
-    char* ob = smem + wave * 4096;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            uint2 pk;
-            pk.x = pack_bf16x2(o[db][g4 * 4 + 0] * inv, o[db][g4 * 4 + 1] * inv);
-            pk.y = pack_bf16x2(o[db][g4 * 4 + 2] * inv, o[db][g4 * 4 + 3] * inv);
-            *reinterpret_cast<uint2*>(ob + l31 * 128 + (((4 * db + g4) ^ (l31 & 7)) << 4) + hi * 8) = pk;
-        }
-    bf16_t* obase = (bf16_t*)p.O + (int64_t)b * p.o_sb + (int64_t)h * p.o_sh;
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-        const int R = 8 * ps + (lane >> 3);
-        const int chunk = (lane & 7) ^ (R & 7);
-        const uint4 v = *reinterpret_cast<const uint4*>(ob + R * 128 + ((lane & 7) << 4));
-        if (q0 + R < p.Nq) *reinterpret_cast<uint4*>(obase + (int64_t)(q0 + R) * p.o_sn + chunk * 8) = v;
-    }
+    att_store_lse(p.lse, (int64_t)b * p.H + h, p.Nq, q0 + l31, hi, m_run, p.scale, l_tot);
+    att_store_rows_bounced(o, __builtin_amdgcn_rcpf(l_tot), smem + wave * 4096, (bf16_t*)p.O + (int64_t)b * p.o_sb + (int64_t)h * p.o_sh, p.o_sn, q0, p.Nq, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -967,7 +744,7 @@ extern "C" int uc_attention_fwd(const uc_attention_desc* desc, uc_stream_t strea
             pp.Q = Q; pp.K = K; pp.V = V; pp.O = O; pp.lse = d.lse; pp.B = B; pp.H = H; pp.Nq = Nq; pp.Nk = Nk;
             pp.q_sb = d.q_sb; pp.q_sn = d.q_sn; pp.q_sh = d.q_sh; pp.k_sb = d.k_sb; pp.k_sn = d.k_sn; pp.k_sh = d.k_sh;
             pp.o_sb = d.o_sb; pp.o_sn = d.o_sn; pp.o_sh = d.o_sh;
-            pp.npad = p.npad; pp.c = d.scale * 1.44269504088896340736f; pp.q_prescaled = 0;
+            pp.npad = p.npad; pp.c = d.scale * ATT_LOG2E; pp.q_prescaled = 0;
             pp.nq = (Nq + 255) / 256; pp.dNq = uc_make_fastdiv((unsigned)pp.nq); pp.dH = uc_make_fastdiv((unsigned)H);
             pp.dbg = nullptr;
             if (plan.kernel == UC_AF_P64_TAIL) hipLaunchKernelGGL(attn_bf16_p64_kernel<true>, grid, block, 0, st, pp);

@@ -10,7 +10,7 @@
 // pair (lane, lane ^ 32) holds the 64 channels of one query in both accumulators, so the combine + RMSNorm epilogue needs one
 // cross-lane add.  Registers: 4 x 16 accumulators + 2 x 32 scores + 2 x 16 packed probabilities + 16 Q fragment + 16 staging.
 // fp32 kernel (diff_attn_f32_kernel): one thread per query in the style of attn_f32_kernel, 32-key tiles of K1, K2 and V in LDS.
-#include "mma_tile.h"
+#include "attention_tile.h"
 
 struct DiffParams {
     const void* Q;
@@ -28,62 +28,8 @@ struct DiffParams {
     float scale, lambda, eps, out_scale;
 };
 
-#define DKV_TILE 64
-#define DTILE_BYTES (DKV_TILE * 128)
-
-// one online-softmax step of a lane pair's query over the 64 scores s[2][16] (keys k0 + 32 kb + (r&3) + 8 (r>>2) + 4 hi):
-// updates (m_run, l_run), rescales o[2] when a maximum of the wave grew, returns the packed probabilities
-__device__ __forceinline__ void diff_softmax_step(float16_t (&s)[2], float& m_run, float& l_run, float16_t (&o)[2], bf16x8_t (&pf)[4],
-                                                  const float c, const int k0, const int Nk, const int hi) {
-    if (k0 + DKV_TILE > Nk) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                if (key >= Nk) s[kb][r] = -1e30f;
-            }
-    }
-    float mt = s[0][0];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s[kb][r]);
-    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-    // deferred rescale (attention.hip): keep the old running maximum while no query of the wave grew by more than 2^8
-    const bool grow = (mt - m_run) * c > 8.0f;
-    if (__any(grow)) {
-        const float m_new = fmaxf(m_run, mt);
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-        m_run = m_new;
-        l_run *= alpha;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-    }
-    const float mc = m_run * c;
-    float psum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            float e[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                e[j] = __builtin_amdgcn_exp2f(fmaf(s[kb][hf * 8 + j], c, -mc));
-                psum += e[j];
-            }
-            union { bf16x8_t v; unsigned u[4]; } pk;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pk.u[j] = pack_bf16x2(e[2 * j], e[2 * j + 1]);
-            pf[kb * 2 + hf] = pk.v;
-        }
-    l_run += psum;
-}
-
 __global__ __launch_bounds__(256) void diff_attn_bf16_kernel(DiffParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[4 * DTILE_BYTES];   // 2 stages x (K1|K2 tile + VT tile)
+    __shared__ __attribute__((aligned(16))) char smem[4 * ATT_TILE_BYTES];   // 2 stages x (K1|K2 tile + VT tile)
     const int b = blockIdx.z, h = blockIdx.y;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -121,19 +67,7 @@ __global__ __launch_bounds__(256) void diff_attn_bf16_kernel(DiffParams p) {
         if (key >= p.Nk) key = p.Nk - 1;   // clamped keys are masked in the softmax
         return *reinterpret_cast<const uint4*>(Ksrc + (int64_t)key * p.k_sn);
     };
-    auto load_v = [&](int k0, int row) -> uint4 {
-        uint4 v = *reinterpret_cast<const uint4*>(VTb + (int64_t)row * p.npad + k0 + cc * 8);
-        if (k0 + DKV_TILE > p.Nk) {   // tail tile: zero the positions that hold no key (probability 0 times anything finite or not)
-            const int gbase = k0 + ((cc * 8) & ~15);
-            const int pbase = (cc * 8) & 15;
-            unsigned m[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (gbase + vt_key_of_pos(pbase + j) >= p.Nk) m[j >> 1] &= (j & 1) ? 0x0000ffffu : 0xffff0000u;
-            v.x &= m[0]; v.y &= m[1]; v.z &= m[2]; v.w &= m[3];
-        }
-        return v;
-    };
+    auto load_v = [&](int k0, int row) -> uint4 { return att_load_vt_chunk(VTb, row, p.npad, k0, cc, p.Nk); };
 #define DIFF_STAGE_LOAD(k0_)                \
     do {                                    \
         rk0 = load_k((k0_), sr);            \
@@ -144,32 +78,31 @@ __global__ __launch_bounds__(256) void diff_attn_bf16_kernel(DiffParams p) {
     const int w_off = tile_swz(sr, cc);   // rows r and r + 32 share the swizzle key
 #define DIFF_STAGE_WRITE(buf_)                                                 \
     do {                                                                       \
-        char* sk_ = smem + (buf_) * 2 * DTILE_BYTES + w_off;                   \
+        char* sk_ = smem + (buf_) * 2 * ATT_TILE_BYTES + w_off;                   \
         *reinterpret_cast<uint4*>(sk_) = rk0;                                  \
         *reinterpret_cast<uint4*>(sk_ + 32 * 128) = rk1;                       \
-        *reinterpret_cast<uint4*>(sk_ + DTILE_BYTES) = rv0;                    \
-        *reinterpret_cast<uint4*>(sk_ + DTILE_BYTES + 32 * 128) = rv1;         \
+        *reinterpret_cast<uint4*>(sk_ + ATT_TILE_BYTES) = rv0;                    \
+        *reinterpret_cast<uint4*>(sk_ + ATT_TILE_BYTES + 32 * 128) = rv1;         \
     } while (0)
-    int r_off[4];   // row l31 (+ 32 via immediate), chunk 2 st + hi: K tile st 0, 1 = K1, st 2, 3 = K2; VT tile: 16-key slab st
-#pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
+    int r_off[4];   // K tile: st 0, 1 = K1, st 2, 3 = K2; VT tile: 16-key slab st
+    att_frag_offsets(r_off, l31, hi);
 
-    float16_t o1[2], o2[2];   // O^T accumulators: channel d = 32 db + (r&3) + 8 (r>>2) + 4 hi, query l31
+    float16_t o1[2], o2[2];   // O^T accumulators: channel d = att_frag_row(db, r, hi), query l31
     o1[0] = o1[1] = o2[0] = o2[1] = (float16_t)(0.f);
-    float m1 = -1e30f, m2 = -1e30f, l1 = 0.f, l2 = 0.f;
-    const float c = p.scale * 1.44269504088896340736f;
+    float m1 = ATT_MASKED, m2 = ATT_MASKED, l1 = 0.f, l2 = 0.f;
+    const float c = p.scale * ATT_LOG2E;
 
-    const int nt = (p.Nk + DKV_TILE - 1) / DKV_TILE;
+    const int nt = (p.Nk + ATT_KV_TILE - 1) / ATT_KV_TILE;
     DIFF_STAGE_LOAD(0);
     DIFF_STAGE_WRITE(0);
     __syncthreads();
 
     for (int t = 0; t < nt; ++t) {
         const int buf = t & 1;
-        const int k0 = t * DKV_TILE;
-        if (t + 1 < nt) DIFF_STAGE_LOAD(k0 + DKV_TILE);
-        const char* sk = smem + buf * 2 * DTILE_BYTES;
-        const char* sv = sk + DTILE_BYTES;
+        const int k0 = t * ATT_KV_TILE;
+        if (t + 1 < nt) DIFF_STAGE_LOAD(k0 + ATT_KV_TILE);
+        const char* sk = smem + buf * 2 * ATT_TILE_BYTES;
+        const char* sv = sk + ATT_TILE_BYTES;
 
         float16_t s1[2], s2[2];
 #pragma unroll
@@ -184,9 +117,13 @@ __global__ __launch_bounds__(256) void diff_attn_bf16_kernel(DiffParams p) {
                 s2[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k2f, qf[2 + st], s2[kb], 0, 0, 0);
             }
         }
-        bf16x8_t pf1[4], pf2[4];
-        diff_softmax_step(s1, m1, l1, o1, pf1, c, k0, p.Nk, hi);
-        diff_softmax_step(s2, m2, l2, o2, pf2, c, k0, p.Nk, hi);
+        if (k0 + ATT_KV_TILE > p.Nk) {
+            att_mask_tail(s1, k0, p.Nk, hi);
+            att_mask_tail(s2, k0, p.Nk, hi);
+        }
+        AttProbsBf16 pr1, pr2;
+        att_softmax_step(s1, m1, l1, o1, c, pr1);
+        att_softmax_step(s2, m2, l2, o2, c, pr2);
 
         // O1^T += V^T P1^T, O2^T += V^T P2^T: every V^T fragment is read once and feeds both
 #pragma unroll
@@ -194,8 +131,8 @@ __global__ __launch_bounds__(256) void diff_attn_bf16_kernel(DiffParams p) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const bf16x8_t vf = *reinterpret_cast<const bf16x8_t*>(sv + r_off[g] + db * (32 * 128));
-                o1[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf1[g], o1[db], 0, 0, 0);
-                o2[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf2[g], o2[db], 0, 0, 0);
+                o1[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pr1.pf[g], o1[db], 0, 0, 0);
+                o2[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pr2.pf[g], o2[db], 0, 0, 0);
             }
 
         if (t + 1 < nt) DIFF_STAGE_WRITE(buf ^ 1);

@@ -10,11 +10,11 @@
 //   * P is converted with a x64 offset (P <= 2^2 under the rescale threshold -> <= 256 < 448 = e4m3 max; the offset keeps
 //     small probabilities out of the subnormal range) and divided out in the final normalisation.
 //   * V comes pre-packed by uc_vt_pack_fp8: transposed per head, e4m3, keys permuted inside every 64-key group so that the
-//     accumulator register order of P^T IS the MFMA k-slot order: position 32*hh + 16*kb + r holds key
-//     32*kb + (r&3) + 8*(r>>2) + 4*hh.  Pad positions are zero, so tail tiles need no masking of V.
+//     accumulator register order of P^T IS the MFMA k-slot order: position 32*hh + 16*kb + r holds key att_frag_row(kb, r, hh)
+//     (attention_tile.h).  Pad positions are zero, so tail tiles need no masking of V.
 // Operand layout of the instruction (probed, tools/probes/f8_layout.hip): byte e of lane l is A[row = l&31][k] resp.
 // B[k][col = l&31] with ANY k assignment shared by A and B across the two lane halves; C/D as every 32x32 MFMA.
-#include "mma_tile.h"
+#include "attention_tile.h"
 
 typedef int v8i_t __attribute__((ext_vector_type(8)));
 
@@ -31,7 +31,6 @@ struct AttnF8Params {
 #define F8_TILE (64 * 64)          // bytes of one 64-row fp8 tile
 #define F8_ONE 0x7f7f7f7f          // E8M0 scale bytes = 2^0
 #define F8_POFF 64.0f              // offset applied to P before the e4m3 conversion
-#define F8_RESCALE_LOG2 2.0f       // deferred-rescale threshold: P <= 2^2
 
 __device__ __forceinline__ int f8_swz(int row, int chunk16) { return row * 64 + ((chunk16 ^ ((row >> 2) & 3)) << 4); }
 
@@ -41,6 +40,17 @@ __device__ __forceinline__ unsigned cvt4_fp8(float a, float b, float c, float d)
     w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
     return (unsigned)w;
 }
+
+// att_softmax_step's emission as e4m3: P^T operand, byte 16*kb + r of lane (q, hi) = key att_frag_row(kb, r, hi)
+struct AttProbsFp8 {
+    static constexpr int GROUP = 4;
+    static constexpr float RESCALE_LOG2 = 2.0f;       // deferred-rescale threshold: P <= 2^2
+    static constexpr bool EXP2_DOMAIN = false;
+    v8i_t pf;
+    __device__ __forceinline__ void put(const int kb, const int w, const float (&e)[4]) {
+        pf[4 * kb + w] = (int)cvt4_fp8(e[0] * F8_POFF, e[1] * F8_POFF, e[2] * F8_POFF, e[3] * F8_POFF);
+    }
+};
 
 // 8 bf16 (one 16-byte chunk) -> 8 e4m3 bytes
 __device__ __forceinline__ uint2 bf16x8_to_fp8x8(uint4 v) {
@@ -119,8 +129,8 @@ __global__ __launch_bounds__(256) void attn_fp8_kernel(AttnF8Params p) {
     float16_t o[2];
     o[0] = (float16_t)(0.f);
     o[1] = (float16_t)(0.f);
-    float m_run = -1e30f, l_run = 0.f;
-    const float c = p.scale * 1.44269504088896340736f;
+    float m_run = ATT_MASKED, l_run = 0.f;
+    const float c = p.scale * ATT_LOG2E;
 
     const int nt = (p.Nk + 63) / 64;
     F8_STAGE_LOAD(0);
@@ -140,72 +150,28 @@ __global__ __launch_bounds__(256) void attn_fp8_kernel(AttnF8Params p) {
             s[kb] = (float16_t)(0.f);
             s[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(frag(sk, kb), qf, s[kb], 0, 0, 0, F8_ONE, 0, F8_ONE);
         }
-        if (k0 + 64 > p.Nk) {
+        if (k0 + 64 > p.Nk) {      // att_mask_tail written out: through the helper the scheduler reorders this loop (+1 % on 1370 keys)
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;      // k0 + att_frag_row(kb, r, hi)
                     if (key >= p.Nk) s[kb][r] = -1e30f;
                 }
         }
-        float mt = s[0][0];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s[kb][r]);
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        const bool grow = (mt - m_run) * c > F8_RESCALE_LOG2;
-        if (__any(grow)) {
-            const float m_new = fmaxf(m_run, mt);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-        }
-        const float mc = m_run * c;
-        float psum = 0.f;
-        v8i_t pf;   // P^T operand: byte 16*kb + r of lane (q, hi) = key 32*kb + (r&3) + 8*(r>>2) + 4*hi
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                float e[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    e[j] = __builtin_amdgcn_exp2f(fmaf(s[kb][4 * w + j], c, -mc));
-                    psum += e[j];
-                }
-                pf[4 * kb + w] = (int)cvt4_fp8(e[0] * F8_POFF, e[1] * F8_POFF, e[2] * F8_POFF, e[3] * F8_POFF);
-            }
-        l_run += psum;
+        AttProbsFp8 pr;
+        att_softmax_step(s, m_run, l_run, o, c, pr);
 #pragma unroll
         for (int db = 0; db < 2; ++db)
-            o[db] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(frag(sv, db), pf, o[db], 0, 0, 0, F8_ONE, 0, F8_ONE);
+            o[db] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(frag(sv, db), pr.pf, o[db], 0, 0, 0, F8_ONE, 0, F8_ONE);
 
         if (t + 1 < nt) F8_STAGE_WRITE(buf ^ 1);
         __syncthreads();
     }
 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / (l_tot * F8_POFF);
     const int q = q0 + l31;
-    if (q < p.Nq) {
-        bf16_t* op = p.O + (int64_t)b * p.o_sb + (int64_t)q * p.o_sn + (int64_t)h * p.o_sh;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int d = db * 32 + 8 * g4 + 4 * hi;
-                uint2 pk;
-                pk.x = pack_bf16x2(o[db][g4 * 4 + 0] * inv, o[db][g4 * 4 + 1] * inv);
-                pk.y = pack_bf16x2(o[db][g4 * 4 + 2] * inv, o[db][g4 * 4 + 3] * inv);
-                *reinterpret_cast<uint2*>(op + d) = pk;
-            }
-    }
+    if (q < p.Nq) att_store_rows_direct(o, 1.0f / (l_tot * F8_POFF), p.O + (int64_t)b * p.o_sb + (int64_t)q * p.o_sn + (int64_t)h * p.o_sh, hi);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -282,8 +248,8 @@ __global__ __launch_bounds__(256, 4) void attn_fp8_dma_kernel(AttnF8DmaParams p)
     float16_t o[2];
     o[0] = (float16_t)(0.f);
     o[1] = (float16_t)(0.f);
-    float m_run = -1e30f, l_run = 0.f;
-    const float c = p.scale * 1.44269504088896340736f;
+    float m_run = ATT_MASKED, l_run = 0.f;
+    const float c = p.scale * ATT_LOG2E;
     const int nt = p.Nk / 64;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -299,66 +265,17 @@ __global__ __launch_bounds__(256, 4) void attn_fp8_dma_kernel(AttnF8DmaParams p)
             s[kb] = (float16_t)(0.f);
             s[kb] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(frag(sk, kb), qf, s[kb], 0, 0, 0, F8_ONE, 0, F8_ONE);
         }
-        float mt = s[0][0];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s[kb][r]);
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        const bool grow = (mt - m_run) * c > F8_RESCALE_LOG2;
-        if (__any(grow)) {
-            const float m_new = fmaxf(m_run, mt);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-        }
-        const float mc = m_run * c;
-        float psum = 0.f;
-        v8i_t pf;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                float e[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    e[j] = __builtin_amdgcn_exp2f(fmaf(s[kb][4 * w + j], c, -mc));
-                    psum += e[j];
-                }
-                pf[4 * kb + w] = (int)cvt4_fp8(e[0] * F8_POFF, e[1] * F8_POFF, e[2] * F8_POFF, e[3] * F8_POFF);
-            }
-        l_run += psum;
+        AttProbsFp8 pr;
+        att_softmax_step(s, m_run, l_run, o, c, pr);
 #pragma unroll
         for (int db = 0; db < 2; ++db)
-            o[db] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(frag(sv, db), pf, o[db], 0, 0, 0, F8_ONE, 0, F8_ONE);
+            o[db] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(frag(sv, db), pr.pf, o[db], 0, 0, 0, F8_ONE, 0, F8_ONE);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = __builtin_amdgcn_rcpf(l_tot * F8_POFF);
-    char* ob = smem + wave * 4096;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            uint2 pk;
-            pk.x = pack_bf16x2(o[db][g4 * 4 + 0] * inv, o[db][g4 * 4 + 1] * inv);
-            pk.y = pack_bf16x2(o[db][g4 * 4 + 2] * inv, o[db][g4 * 4 + 3] * inv);
-            *reinterpret_cast<uint2*>(ob + l31 * 128 + (((4 * db + g4) ^ (l31 & 7)) << 4) + hi * 8) = pk;
-        }
-    bf16_t* obase = p.O + (int64_t)b * p.o_sb + (int64_t)h * p.o_sh;
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-        const int R = 8 * ps + (lane >> 3);
-        const int chunk = (lane & 7) ^ (R & 7);
-        const uint4 v = *reinterpret_cast<const uint4*>(ob + R * 128 + ((lane & 7) << 4));
-        if (q0 + R < p.Nq) *reinterpret_cast<uint4*>(obase + (int64_t)(q0 + R) * p.o_sn + chunk * 8) = v;
-    }
+    att_store_rows_bounced(o, __builtin_amdgcn_rcpf(l_tot * F8_POFF), smem + wave * 4096, p.O + (int64_t)b * p.o_sb + (int64_t)h * p.o_sh, p.o_sn, q0, p.Nq, lane);
 }
 
 extern "C" int uc_attention_fwd_fp8_k8(const void* Q, const void* K8, const void* VT8, void* O, int B, int H, int Nq, int Nk,

@@ -11,9 +11,7 @@
 // stores.  The operands come from a split pass (uc_attention_fwd_x3 runs it into the caller's workspace): Q is multiplied by
 // scale * log2(e) in fp32 BEFORE the split, so the scores arrive in the exp2 domain and the softmax needs no multiply.
 // Reference sites: libs/croco/blocks.py:123-125, models/utils/transformer_blocks.py:244-246, 373-375 (F.scaled_dot_product_attention).
-#include "mma_tile.h"
-
-#define X3_TILE_BYTES (64 * 128)   // 64 rows x 128 B (one bf16 tile: 64 keys x 64 channels, or 64 channels x 64 key positions)
+#include "attention_tile.h"
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // split passes.  rows: fp32 [B, N, H, 64] strided (unit channel stride) -> hi, lo bf16 [B, N, H, 64] contiguous, x * mul first.
@@ -111,7 +109,7 @@ struct X3Params {
 
 __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
     // 2 stages x (Kh, Kl, VTh, VTl); the Q rows (hi, lo: 2 x 4 KiB per wave) arrive in the second stage before the ring needs it
-    __shared__ __attribute__((aligned(16))) char smem[8 * X3_TILE_BYTES];
+    __shared__ __attribute__((aligned(16))) char smem[8 * ATT_TILE_BYTES];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -142,33 +140,22 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
     }
     const unsigned kstep = (unsigned)(64 * row_stride * 2);
     auto issue_tile = [&](int t, int buf) {
-        const unsigned dst = lds0 + (unsigned)(buf * 4 * X3_TILE_BYTES + wave * 2048);
+        const unsigned dst = lds0 + (unsigned)(buf * 4 * ATT_TILE_BYTES + wave * 2048);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             dma16_buf_to_lds(voff_k[i], srd_kh, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + i * 1024));
-            dma16_buf_to_lds(voff_k[i], srd_kl, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + X3_TILE_BYTES + i * 1024));
-            dma16_buf_to_lds(voff_v[i], srd_vh, (unsigned)t * 128u, __builtin_amdgcn_readfirstlane(dst + 2 * X3_TILE_BYTES + i * 1024));
-            dma16_buf_to_lds(voff_v[i], srd_vl, (unsigned)t * 128u, __builtin_amdgcn_readfirstlane(dst + 3 * X3_TILE_BYTES + i * 1024));
+            dma16_buf_to_lds(voff_k[i], srd_kl, (unsigned)t * kstep, __builtin_amdgcn_readfirstlane(dst + ATT_TILE_BYTES + i * 1024));
+            dma16_buf_to_lds(voff_v[i], srd_vh, (unsigned)t * 128u, __builtin_amdgcn_readfirstlane(dst + 2 * ATT_TILE_BYTES + i * 1024));
+            dma16_buf_to_lds(voff_v[i], srd_vl, (unsigned)t * 128u, __builtin_amdgcn_readfirstlane(dst + 3 * ATT_TILE_BYTES + i * 1024));
         }
     };
     {   // Q rows of this wave (hi, lo) into the second stage
-        const int64_t q_rows = min((int64_t)32, (int64_t)p.Nq - q0);
-        const unsigned q_bytes = q_rows > 0 ? (unsigned)(((q_rows - 1) * row_stride + 64) * 2) : 0u;
-        const uint4_t srd_qh = make_srd(p.Qh + qbase + (int64_t)q0 * row_stride, q_bytes);
-        const uint4_t srd_ql = make_srd(p.Ql + qbase + (int64_t)q0 * row_stride, q_bytes);
-        const unsigned dstq = lds0 + (unsigned)(4 * X3_TILE_BYTES + wave * 8192);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rr = i * 8 + (lane >> 3);
-            const int cch = (lane & 7) ^ ((rr >> 1) & 7);
-            const unsigned vo = (unsigned)(((int64_t)rr * row_stride + cch * 8) * 2);
-            dma16_buf_to_lds(vo, srd_qh, 0u, __builtin_amdgcn_readfirstlane(dstq + i * 1024));
-            dma16_buf_to_lds(vo, srd_ql, 0u, __builtin_amdgcn_readfirstlane(dstq + 4096 + i * 1024));
-        }
+        const unsigned dstq = lds0 + (unsigned)(4 * ATT_TILE_BYTES + wave * 8192);
+        att_q_rows_to_lds(p.Qh + qbase + (int64_t)q0 * row_stride, row_stride, (int64_t)p.Nq - q0, dstq, lane);
+        att_q_rows_to_lds(p.Ql + qbase + (int64_t)q0 * row_stride, row_stride, (int64_t)p.Nq - q0, dstq + 4096, lane);
     }
     int r_off[4];
-#pragma unroll
-    for (int st = 0; st < 4; ++st) r_off[st] = tile_swz(l31, 2 * st + hi);
+    att_frag_offsets(r_off, l31, hi);
 
     issue_tile(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -176,24 +163,24 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
     bf16x8_t qh[4], ql[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        qh[s] = *reinterpret_cast<const bf16x8_t*>(smem + 4 * X3_TILE_BYTES + wave * 8192 + r_off[s]);
-        ql[s] = *reinterpret_cast<const bf16x8_t*>(smem + 4 * X3_TILE_BYTES + wave * 8192 + 4096 + r_off[s]);
+        qh[s] = *reinterpret_cast<const bf16x8_t*>(smem + 4 * ATT_TILE_BYTES + wave * 8192 + r_off[s]);
+        ql[s] = *reinterpret_cast<const bf16x8_t*>(smem + 4 * ATT_TILE_BYTES + wave * 8192 + 4096 + r_off[s]);
     }
     __syncthreads();
 
     float16_t o[2];
     o[0] = (float16_t)(0.f);
     o[1] = (float16_t)(0.f);
-    float m_run = -1e30f;      // running max, in the exp2 domain (Q carries scale * log2 e)
+    float m_run = ATT_MASKED;  // running max, in the exp2 domain (Q carries scale * log2 e)
     float l_run = 0.f;
     const int nt = (p.Nk + 63) / 64;
     for (int t = 0; t < nt; ++t) {
         const int buf = t & 1;
         if (t + 1 < nt) issue_tile(t + 1, buf ^ 1);
-        const char* skh = smem + buf * 4 * X3_TILE_BYTES;
-        const char* skl = skh + X3_TILE_BYTES;
-        const char* svh = skh + 2 * X3_TILE_BYTES;
-        const char* svl = skh + 3 * X3_TILE_BYTES;
+        const char* skh = smem + buf * 4 * ATT_TILE_BYTES;
+        const char* skl = skh + ATT_TILE_BYTES;
+        const char* svh = skh + 2 * ATT_TILE_BYTES;
+        const char* svl = skh + 3 * ATT_TILE_BYTES;
 
         float16_t s[2];
 #pragma unroll
@@ -208,65 +195,19 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
                 s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh[st], s[kb], 0, 0, 0);
             }
         }
-        if (t == nt - 1 && (p.Nk & 63)) {       // ragged last tile: keys >= Nk (zero K rows, zero VT pads) leave the softmax
-            const int k0 = t * 64;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= p.Nk) s[kb][r] = -1e30f;
-        }
-        float mt = s[0][0];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s[kb][r]);
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        // deferred rescale as in the bf16 kernel: the old running max is kept while no query of the wave grew by more than 2^8 (P <= 256;
-        // the hi / lo split of P is floating point, so its RELATIVE accuracy does not depend on the scale), the O / l rescale then
-        // runs on a wave-uniform branch
-        if (__any(mt - m_run > 8.0f)) {
-            const float m_new = fmaxf(m_run, mt);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-        }
-        float psum = 0.f;
-        bf16x8_t ph[4], pl[4];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                float e[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    e[j] = __builtin_amdgcn_exp2f(s[kb][hf * 8 + j] - m_run);
-                    psum += e[j];
-                }
-                union { bf16x8_t v; unsigned u[4]; } a, c;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    a.u[j] = pack_bf16x2(e[2 * j], e[2 * j + 1]);
-                    c.u[j] = pack_bf16x2(e[2 * j] - __uint_as_float(a.u[j] << 16), e[2 * j + 1] - __uint_as_float(a.u[j] & 0xffff0000u));
-                }
-                ph[kb * 2 + hf] = a.v;
-                pl[kb * 2 + hf] = c.v;
-            }
-        }
-        l_run += psum;
+        // ragged last tile: keys >= Nk (zero K rows, zero VT pads) leave the softmax
+        if (t == nt - 1 && (p.Nk & 63)) att_mask_tail(s, t * ATT_KV_TILE, p.Nk, hi);
+        AttProbsBf16x3 pr;       // fp32 statistics: the row sums take the UNROUNDED P
+        att_softmax_step(s, m_run, l_run, o, 1.0f, pr);
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const bf16x8_t vh = *reinterpret_cast<const bf16x8_t*>(svh + r_off[g] + db * (32 * 128));
                 const bf16x8_t vl = *reinterpret_cast<const bf16x8_t*>(svl + r_off[g] + db * (32 * 128));
-                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph[g], o[db], 0, 0, 0);
-                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl[g], o[db], 0, 0, 0);
-                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph[g], o[db], 0, 0, 0);
+                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, pr.ph[g], o[db], 0, 0, 0);
+                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pr.pl[g], o[db], 0, 0, 0);
+                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pr.ph[g], o[db], 0, 0, 0);
             }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -275,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(X3Params p) {
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
     const int q = q0 + l31;
-    if (p.lse && q < p.Nq && hi == 0) p.lse[((int64_t)b * p.H + h) * p.Nq + q] = m_run * 0.69314718055994530942f + logf(l_tot);
+    att_store_lse(p.lse, (int64_t)b * p.H + h, p.Nq, q, hi, m_run, ATT_LN2, l_tot);
     // bounce the wave's 32 x 64 fp32 outputs through its private 8 KiB of the ring: every store instruction writes 4 whole 256-B rows
     char* ob = smem + wave * 8192;
 #pragma unroll
@@ -325,7 +266,7 @@ extern "C" int uc_attention_fwd_x3(const float* Q, const float* K, const float* 
     bf16_t *Qh = w, *Ql = Qh + nQ, *Kh = Ql + nQ, *Kl = Kh + nK, *VTh = Kl + nK, *VTl = VTh + nV;
     const int64_t iq = nQ / 8, ik = nK / 8;
     const unsigned gq = (unsigned)std::min<int64_t>((iq + 255) / 256, 65535 * 16), gk = (unsigned)std::min<int64_t>((ik + 255) / 256, 65535 * 16);
-    hipLaunchKernelGGL(x3_split_rows_kernel, dim3(gq), dim3(256), 0, st, Q, Qh, Ql, Nq, H, q_sb, q_sn, q_sh, scale * 1.44269504088896340736f, iq,
+    hipLaunchKernelGGL(x3_split_rows_kernel, dim3(gq), dim3(256), 0, st, Q, Qh, Ql, Nq, H, q_sb, q_sn, q_sh, scale * ATT_LOG2E, iq,
                        q_pos, (const float2*)rope_table, rope_npos);
     hipLaunchKernelGGL(x3_split_rows_kernel, dim3(gk), dim3(256), 0, st, K, Kh, Kl, Nk, H, k_sb, k_sn, k_sh, 1.0f, ik, k_pos, (const float2*)rope_table, rope_npos);
     UC_REQUIRE(H <= 65535 && B <= 65535, "uc_attention_fwd_x3: B and H must fit a grid dimension");
