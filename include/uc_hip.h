@@ -64,8 +64,10 @@ const char* uc_last_error(void);
  *   19: the MoGe head's channels-last passes — uc_group_norm_nhwc (+ _bwd, two _ws_bytes queries), uc_replicate_pad_nhwc (+ _bwd),
  *       uc_crop_add_nhwc, uc_crop_embed_nhwc, uc_resize_bilinear_nhwc (+ _bwd) added (nothing existing changed).
  *   20: the streaming steps of the non-image input encoders — uc_unshuffle_rows (+ _bwd), uc_act, uc_ln_pe_ln,
- *       uc_ln_param_grads (+ _ws_bytes) added (nothing existing changed). */
-#define UC_ABI_VERSION 20
+ *       uc_ln_param_grads (+ _ws_bytes) added (nothing existing changed).
+ *   21: the fused ViT stem of the Perception Encoder — uc_vit_stem, uc_vit_stem_bwd, uc_vit_stem_ws_bytes added (nothing existing
+ *       changed). */
+#define UC_ABI_VERSION 21
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -752,6 +754,28 @@ int uc_ln_param_grads(const void* x, int x_dtype, const void* dy, int dy_dtype, 
                       float eps, uc_stream_t stream);
 int uc_ln_pe_ln(const void* x, int x_dtype, const float* gamma1, const float* beta1, float eps1, const float* pe, const float* gamma2,
                 const float* beta2, float eps2, void* y, int y_dtype, float* mid, int64_t B, int64_t N, int C, uc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * The stem of a ViT whose token assembly ends in a LayerNorm (Perception Encoder: ln_pre(cat(class_embedding, conv1(x)) + posemb)),
+ * csrc/vit_stem.hip.  With T = hw + (cls != NULL), ncls = T - hw:
+ *   uc_vit_stem:       z[b, t, :] = (t < ncls ? cls : tok[b, t - ncls, :]) + pos[t, :],   y[b, t, :] = LN(z[b, t, :]) gamma + beta.
+ *                      tok [B, hw, C] (UC_F32 | UC_BF16): the patch GEMM's output; cls fp32 [C] or NULL (no class token); pos fp32 [T, C]
+ *                      or NULL; gamma, beta fp32 [C], both NULL: no LayerNorm (y = z); y [B, T, C] (UC_F32 | UC_BF16); stats (optional,
+ *                      fp32 [B T, 2]): (mean, rstd) of every row, which the backward needs.  One pass, one wavefront per row, eight
+ *                      channels per work item: C % 8 == 0, C <= 2048, every pointer 16-byte aligned.  Statistics in fp32, the mean
+ *                      first, then the squared deviations from it.
+ *   uc_vit_stem_bwd:   z is recomputed from tok, cls and pos; dz = the LayerNorm's backward of dy [B, T, C] (UC_F32 | UC_BF16) (dy itself
+ *                      without a norm); dtok[b, i] = dz[b, ncls + i] (in tok's dtype), dpos[t] = sum_b dz[b, t], dcls = dpos[0],
+ *                      dgamma = sum dy x^, dbeta = sum dy (all fp32, overwritten).  Every output may be NULL.  All sums are two-stage in
+ *                      a fixed order through ws — per 8 images x 8 tokens ascending, then the partials ascending — without atomics: the
+ *                      same bits on every run.  ws: caller-provided, uc_vit_stem_ws_bytes(B, T, C) bytes, 16-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+int uc_vit_stem(const void* tok, int tok_dtype, const float* cls, const float* pos, const float* gamma, const float* beta, float eps, void* y,
+                int y_dtype, float* stats, int64_t B, int64_t hw, int C, uc_stream_t stream);
+int64_t uc_vit_stem_ws_bytes(int64_t B, int64_t T, int64_t C);
+int uc_vit_stem_bwd(const void* dy, int dy_dtype, const void* tok, int tok_dtype, const float* cls, const float* pos, const float* gamma,
+                    const float* stats, void* dtok, float* dcls, float* dpos, float* dgamma, float* dbeta, float* ws, int64_t B, int64_t hw, int C,
+                    uc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -174,12 +174,15 @@ SIGNATURES = {
     "uc_ln_param_grads_ws_bytes": [i64, i64],
     "uc_ln_param_grads": [vp, i32, vp, i32, vp, vp, vp, i64, i32, f32, vp],
     "uc_ln_pe_ln": [vp, i32, vp, vp, f32, vp, vp, vp, f32, vp, i32, vp, i64, i64, i32, vp],
+    "uc_vit_stem": [vp, i32, vp, vp, vp, vp, f32, vp, i32, vp, i64, i64, i32, vp],
+    "uc_vit_stem_ws_bytes": [i64, i64, i64],
+    "uc_vit_stem_bwd": [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, vp],
 }
 
 _lib = None
 
 
-ABI_VERSION = 20   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 21   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

@@ -110,7 +110,7 @@ def _sink_aware(cls):
 
 
 def _sinkable(param, rows: int, cols: int) -> bool:
-    g = param.grad
+    g = param.grad if param.is_leaf else None      # (rows gathered from a parameter — the Perception Encoder's in_proj — own no buffer)
     return (_grad_sink and _grad_sink_gate and g is not None and g.dtype == torch.float32 and g.is_contiguous()
             and g.numel() == rows * cols and param.requires_grad)
 
@@ -1998,3 +1998,37 @@ def ln_pe_ln(x2d, B: int, N: int, ln1, pe, ln2, out_dtype=torch.float32):
         return LnPeLnFn.apply(x2d, pe, p1[0], p1[1], p2[0], p2[1], B, N, a1[2] if a1 else 0.0, a2[2] if a2 else 0.0, out_dtype)
     pe_ = None if pe is None else (pe if pe.dtype == torch.float32 and pe.is_contiguous() else pe.float().contiguous())
     return ops.ln_pe_ln(_c(x2d), B, N, a1, pe_, a2, out_dtype)
+
+
+@_sink_aware
+class VitStemFn(Function):
+    """y = LN(cat(cls, tok) + pos) in one kernel (uc_vit_stem) and its adjoint in one (uc_vit_stem_bwd): the token gradient, and the
+    gradients of the class embedding, the position table and the norm's parameters from fixed-order sums."""
+
+    @staticmethod
+    def forward(ctx, tok, cls, pos, gamma, beta, eps, out_dtype):
+        tok = _c(tok)
+        if tok.dtype not in (torch.float32, torch.bfloat16):
+            raise UcHipError("vit_stem: the patch tokens are fp32 or bf16")
+        f = lambda t: None if t is None else t.detach().float().contiguous()      # noqa: E731
+        cls_, pos_, g_, b_ = f(cls), f(pos), f(gamma), f(beta)
+        y, stats = ops.vit_stem(tok, cls_, pos_, None if g_ is None else (g_, b_, eps), out_dtype, want_stats=True)
+        ctx.save_for_backward(tok, cls_, pos_, g_, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        tok, cls_, pos_, g_, stats = ctx.saved_tensors
+        dtok, dcls, dpos, dg, db = ops.vit_stem_bwd(_c(dy), tok, cls_, pos_, g_, stats, need_dtok=ctx.needs_input_grad[0])
+        return dtok, dcls, dpos, dg, db, None, None
+
+
+def vit_stem(tok, cls, pos, ln, out_dtype=torch.float32):
+    """LN(cat(cls, tok) + pos): tok [B, hw, C]; cls [C] or None; pos [hw + (cls is not None), C] or None; ln an nn.LayerNorm,
+    nn.Identity or None.  Returns [B, T, C] in out_dtype."""
+    a = _ln_args(ln)
+    p = (ln.weight, ln.bias) if a is not None else (None, None)
+    if grad_needed(tok, cls, pos, *p):
+        return VitStemFn.apply(tok, cls, pos, p[0], p[1], a[2] if a else 0.0, out_dtype)
+    f = lambda t: None if t is None else (t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous())      # noqa: E731
+    return ops.vit_stem(_c(tok), f(cls), f(pos), a, out_dtype)

@@ -7,6 +7,7 @@ from .dinov2 import DINOv2Encoder, DINOv2IntermediateFeatureReturner
 from .global_rep_encoder import GlobalRepresentationEncoder
 from .image_normalizations import IMAGE_NORMALIZATION_DICT  # noqa: F401
 from .patch_embedder import PatchEmbedder
+from .perception_encoder import PerceptionEncoder, PerceptionEncoderIntermediateFeatureReturner
 
 ENCODER_CONFIGS = {
     "croco": {"class": CroCoEncoder, "intermediate_feature_returner_class": CroCoIntermediateFeatureReturner,
@@ -16,6 +17,8 @@ ENCODER_CONFIGS = {
                "supported_models": ["DINOv2", "DINOv2-Registers", "DINOv2-Depth-Anythingv2"]},
     "global_rep_encoder": {"class": GlobalRepresentationEncoder, "supported_models": ["Global-Representation-Encoder"]},
     "patch_embedder": {"class": PatchEmbedder, "supported_models": ["Patch-Embedder"]},
+    "perception_encoder": {"class": PerceptionEncoder, "intermediate_feature_returner_class": PerceptionEncoderIntermediateFeatureReturner,
+                           "supported_models": ["Perception Encoder Core", "Preception Encoder Spatial"]},
 }
 
 

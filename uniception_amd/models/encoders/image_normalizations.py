@@ -18,5 +18,6 @@ _TABLE = {
     "dust3r": ([0.5, 0.5, 0.5], [0.5, 0.5, 0.5]),
     "dinov2": _IMAGENET,
     "patch_embedder": _IMAGENET,
+    "perception_encoder": ([0.5] * 3, [0.5] * 3),
 }
 IMAGE_NORMALIZATION_DICT = {k: ImageNormalization(mean=torch.tensor(m), std=torch.tensor(s)) for k, (m, s) in _TABLE.items()}

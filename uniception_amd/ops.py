@@ -1432,3 +1432,54 @@ def ln_param_grads(x: torch.Tensor, dy: torch.Tensor, eps: float):
     _lib.check(lib.uc_ln_param_grads(x.data_ptr(), _dt(x.dtype), dy.data_ptr(), _dt(dy.dtype), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), rows, Cn,
                                      float(eps), _stream()), "uc_ln_param_grads")
     return dg, db
+
+
+# --------------------------------------------------------------------------------------------
+# the fused ViT stem (csrc/vit_stem.hip): class token + position table + LayerNorm in one pass, and its backward
+# --------------------------------------------------------------------------------------------
+def _stem_check(tok, cls, pos, gamma):
+    _need_gpu(tok, cls, pos, gamma)
+    assert tok.dim() == 3 and tok.is_contiguous() and tok.dtype in (torch.float32, torch.bfloat16)
+    B, hw, Cn = tok.shape
+    T = hw + (cls is not None)
+    for t, shape in ((cls, (Cn,)), (pos, (T, Cn)), (gamma, (Cn,))):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape)
+    return B, hw, Cn, T
+
+
+def vit_stem(tok: torch.Tensor, cls: Optional[torch.Tensor], pos: Optional[torch.Tensor], ln: Optional[Tuple[torch.Tensor, torch.Tensor, float]],
+             out_dtype: torch.dtype, want_stats: bool = False):
+    """y [B, T, C] = LN(z), z[b, t] = (t < ncls ? cls : tok[b, t - ncls]) + pos[t], T = hw + ncls, ncls = (cls is not None).
+    tok [B, hw, C] fp32 | bf16; cls fp32 [C] or None; pos fp32 [T, C] or None; ln: (gamma, beta, eps) fp32 or None (y = z).  Returns y,
+    or (y, stats) with want_stats: fp32 [B*T, 2] (mean, rstd) of every row, which vit_stem_bwd needs."""
+    g, b, eps = ln if ln is not None else (None, None, 0.0)
+    B, hw, Cn, T = _stem_check(tok, cls, pos, g)
+    _need_gpu(b)
+    assert b is None or (b.dtype == torch.float32 and b.is_contiguous() and b.numel() == Cn)
+    y = torch.empty((B, T, Cn), dtype=out_dtype, device=tok.device)
+    stats = torch.empty((B * T, 2), dtype=torch.float32, device=tok.device) if (want_stats and ln is not None) else None
+    _lib.check(_lib.load().uc_vit_stem(tok.data_ptr(), _dt(tok.dtype), _p(cls), _p(pos), _p(g), _p(b), float(eps), y.data_ptr(), _dt(out_dtype),
+                                       _p(stats), B, hw, Cn, _stream()), "uc_vit_stem")
+    return (y, stats) if want_stats else y
+
+
+def vit_stem_bwd(dy: torch.Tensor, tok: torch.Tensor, cls: Optional[torch.Tensor], pos: Optional[torch.Tensor], gamma: Optional[torch.Tensor],
+                 stats: Optional[torch.Tensor], need_dtok: bool = True):
+    """(dtok, dcls, dpos, dgamma, dbeta) of vit_stem for the cotangent dy [B, T, C] (fp32 | bf16): dtok in tok's dtype (None unless
+    need_dtok), the others fp32 and None where the forward had no such input.  Every sum runs in a fixed order: the same bits on
+    every call."""
+    B, hw, Cn, T = _stem_check(tok, cls, pos, gamma)
+    _need_gpu(dy, stats)
+    assert dy.is_contiguous() and tuple(dy.shape) == (B, T, Cn) and dy.dtype in (torch.float32, torch.bfloat16)
+    assert gamma is None or (stats is not None and stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 2 * B * T)
+    dev = tok.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
+    dtok = torch.empty_like(tok) if need_dtok else None
+    dcls = new(Cn) if cls is not None else None
+    dpos = new(T, Cn) if pos is not None else None
+    dg, db = (new(Cn), new(Cn)) if gamma is not None else (None, None)
+    lib = _lib.load()
+    ws = new(max(4, lib.uc_vit_stem_ws_bytes(B, T, Cn) // 4))
+    _lib.check(lib.uc_vit_stem_bwd(dy.data_ptr(), _dt(dy.dtype), tok.data_ptr(), _dt(tok.dtype), _p(cls), _p(pos), _p(gamma), _p(stats), _p(dtok),
+                                   _p(dcls), _p(dpos), _p(dg), _p(db), ws.data_ptr(), B, hw, Cn, _stream()), "uc_vit_stem_bwd")
+    return dtok, dcls, dpos, dg, db

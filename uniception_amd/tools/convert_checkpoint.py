@@ -23,6 +23,11 @@ Real checkpoints cannot be fetched in the build environment; the maps are exerci
 checkpoints (tests/test_convert_checkpoint.py: round trip through `uniception_to_original`, strict load, equal outputs).
 
     python -m uniception_amd.tools.convert_checkpoint ORIGINAL.pth OUT.pth [--per-module-dir DIR]
+
+--mode perception_encoder --pe-config PE-Core-L14-336: an original Perception Encoder checkpoint (the bare state_dict, or under
+"state_dict" / "weights", with optional "module." and "visual." prefixes; of a CLIP checkpoint only the "visual." entries are kept —
+the prefix handling of the reference's VisionTransformer.load_ckpt) -> the {"model": {"model." + key: tensor}} file that
+PerceptionEncoder(pretrained_checkpoint_path=...) loads.  A missing or unexpected key is an error that names it.
 """
 import argparse
 import os
@@ -171,13 +176,49 @@ def load_original_checkpoint(model: torch.nn.Module, original_sd: Dict[str, torc
     return res
 
 
+def perception_encoder_keys(config_name: str) -> Dict[str, Tuple[int, ...]]:
+    "{key: shape} of the vision tower `config_name`, built on the meta device (nothing is allocated)"
+    from ..models.libs.perception_encoder.vision_encoder.pe import VisionTransformer
+    with torch.device("meta"):
+        tower = VisionTransformer.from_config(config_name)
+    return {k: tuple(v.shape) for k, v in tower.state_dict().items()}
+
+
+def perception_encoder_to_uniception(ckpt: Dict, config_name: str) -> Dict[str, torch.Tensor]:
+    """The state_dict of PerceptionEncoder (keys under "model.") from an original PE checkpoint dict; KeyError naming the first
+    missing / unexpected key, ValueError for a shape that does not fit `config_name`."""
+    sd = ckpt.get("state_dict", ckpt.get("weights", ckpt))
+    sd = {k.replace("module.", ""): v for k, v in sd.items()}
+    if any(k.startswith("visual.") for k in sd):
+        sd = {k.replace("visual.", ""): v for k, v in sd.items() if "visual" in k}
+    want = perception_encoder_keys(config_name)
+    for k in want:
+        if k not in sd:
+            raise KeyError(f"missing key {k}: the checkpoint is not a {config_name} vision tower")
+    for k, v in sd.items():
+        if k not in want:
+            raise KeyError(f"unexpected key {k} for a {config_name} vision tower")
+        if tuple(v.shape) != want[k]:
+            raise ValueError(f"{k} has shape {tuple(v.shape)}, {config_name} expects {want[k]}")
+    return {"model." + k: sd[k] for k in want}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("original")
     ap.add_argument("out")
+    ap.add_argument("--mode", default="dust3r", choices=("dust3r", "perception_encoder"))
+    ap.add_argument("--pe-config", default=None, help="perception_encoder mode: the vision tower's config name, e.g. PE-Core-L14-336")
     ap.add_argument("--per-module-dir", default=None, help="also write encoder / info_sharing / head checkpoints there")
     a = ap.parse_args(argv)
     ckpt = torch.load(a.original, map_location="cpu", weights_only=False)
+    if a.mode == "perception_encoder":
+        if not a.pe_config:
+            ap.error("--mode perception_encoder needs --pe-config")
+        converted = perception_encoder_to_uniception(ckpt, a.pe_config)
+        torch.save({"model": converted}, a.out)
+        print(f"wrote {a.out}: {len(converted)} entries of {a.pe_config}")
+        return
     sd = ckpt["model"] if "model" in ckpt else ckpt
     converted, dropped = original_to_uniception(sd)
     for k, why in dropped.items():
