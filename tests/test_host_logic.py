@@ -220,10 +220,184 @@ def test_round6_host_logic_of_the_training_options():
     att = Attention(128, latent_attn_dim=256, num_heads=4, qkv_bias=True)
     assert att.qkv.weight.shape == (768, 128) and att.proj.weight.shape == (128, 256) and att.head_dim == 64 and att.scale == 64 ** -0.5
     blk = CrossAttentionBlock(dim=64, num_heads=1, init_values=0.1)
-    assert {"ls1.gamma", "ls2.gamma", "ls3.gamma"} <= set(blk.state_dict()) and blk._gammas()[0] is blk.ls1.gamma
-    assert CrossAttentionBlock(dim=64, num_heads=1)._gammas() == (None, None, None)
+    from uniception_amd.models.utils.sublayers import gamma_of
+    assert {"ls1.gamma", "ls2.gamma", "ls3.gamma"} <= set(blk.state_dict())
+    assert all(gamma_of(ls) is ls.gamma for ls in (blk.ls1, blk.ls2, blk.ls3))
+    bare = CrossAttentionBlock(dim=64, num_heads=1)
+    assert tuple(gamma_of(ls) for ls in (bare.ls1, bare.ls2, bare.ls3)) == (None, None, None)
     seg = DPTSegmentationProcessor(32, 5, hidden_dim=16, use_bn=True)
     assert {"conv.1.running_mean", "conv.1.weight"} <= set(seg.state_dict()) and seg.conv[0].bias is None
     feat = DPTFeature(patch_size=16, hooks=[0, 1, 2, 3], input_feature_dims=[32, 32, 32, 32], layer_dims=[16, 32, 64, 64], feature_dim=32, use_bn=True)
     keys = set(feat.state_dict())
     assert any(k.endswith("refinenet1.resConfUnit1.bn1.running_var") for k in keys) and not any(k.endswith("resConfUnit1.conv1.bias") for k in keys)
+
+
+def test_every_block_is_a_list_of_sublayer_runner_calls(monkeypatch):
+    """models/utils/sublayers.py: the seven block classes hand modules and numbers to one set of runners, which decide training or
+    inference.  The sub-layer entry points are replaced by recorders that return a fresh stream (the differential sub-layers, which
+    have one path for both, included), every block runs on CPU tensors at dim 128, 2 heads, with and without LayerScale.
+    With gradients: only autograd.*_sublayer fire, in sub-layer order, on the stream the previous one returned, with the LayerScale
+    parameter itself as gamma, and no folded weight is built.  Under no_grad: only engine.* fire, each behind engine.ln_operand on the
+    stream the previous sub-layer returned, with that fold, emit_ln and the residual, and a folded (W, b) exactly when there is a
+    LayerScale.  Train mode under no_grad with any rate > 0 is refused.  The masks come from autograd.make_drops / attn_dropout looked
+    up at call time, once per sub-layer, in each block's generator order."""
+    from uniception_amd import autograd, engine
+    from uniception_amd.models.encoders.dinov2 import _Block
+    from uniception_amd.models.libs.croco.blocks import Block
+    from uniception_amd.models.libs.perception_encoder.vision_encoder.pe import ResidualAttentionBlock
+    from uniception_amd.models.utils.transformer_blocks import (CrossAttentionBlock, DiffCrossAttentionBlock, DiffSelfAttentionBlock,
+                                                                SelfAttentionBlock)
+    C, H, B, N, Ny, dt = 128, 2, 2, 8, 6, torch.float32
+    log, built = [], []
+
+    def auto(name):
+        def f(x2d, *a, gamma=None, drops=None, attn_drop=None, **kw):
+            log.append(dict(name=name, x=x2d, gamma=gamma, drops=drops, attn_drop=attn_drop, out=x2d.clone()))
+            return log[-1]["out"]
+        return f
+
+    def eng(name, residual_at, wb, folds):
+        def f(*a, **kw):
+            log.append(dict(name=name, h=a[0], x=a[residual_at], out_dtype=a[residual_at + 1], wb=kw.get(wb),
+                            folds=[kw.get(k) for k in folds], emit_ln=kw.get("emit_ln"), out=a[residual_at].clone()))
+            return log[-1]["out"]
+        return f
+
+    def ln_operand(x2d, ln, dt_):
+        log.append(dict(name="ln_operand", x=x2d, ln=ln))
+        return x2d, ("fold", ln)
+
+    real_wb = engine.layerscale_lin_weights
+    for name in ("self_attn_sublayer", "cross_attn_sublayer", "mlp_sublayer", "swiglu_sublayer", "diff_self_attn_sublayer",
+                 "diff_cross_attn_sublayer"):
+        monkeypatch.setattr(autograd, name, auto(name))
+    monkeypatch.setattr(engine, "self_attention", eng("self_attention", 9, "proj_wb", ("fold",)))
+    monkeypatch.setattr(engine, "cross_attention", eng("cross_attention", 14, "proj_wb", ("fold_q", "fold_kv")))
+    monkeypatch.setattr(engine, "mlp", eng("mlp", 4, "fc2_wb", ("fold",)))
+    monkeypatch.setattr(engine, "mlp_swiglu", eng("mlp_swiglu", 3, "w3_wb", ("fold",)))
+    monkeypatch.setattr(engine, "ln_operand", ln_operand)
+    monkeypatch.setattr(engine, "layerscale_lin_weights", lambda *a: built.append(a) or real_wb(*a))
+
+    def pe_block(ls):
+        blk = ResidualAttentionBlock(C, H, ls_init_value=0.1 if ls else None)
+        for m in (blk.ls_1, blk.ls_2) if ls else ():
+            m.init_tensors()
+        return blk
+
+    kw = dict(dim=C, num_heads=H)
+    one = lambda blk, x, y: blk.forward_tokens(x, B, N, None, dt)
+    two = lambda blk, x, y: blk.forward_tokens(x, y, B, N, Ny, None, None, dt)
+    enc = lambda blk, x, y: blk.forward_tokens(x, B, N, dt)
+    sa, ca, ml, sw, ds, dc = ("self_attn_sublayer", "cross_attn_sublayer", "mlp_sublayer", "swiglu_sublayer", "diff_self_attn_sublayer",
+                              "diff_cross_attn_sublayer")
+    # (name, build(ls), LayerScale options, call, LayerScale attributes, sub-layers with gradients, sub-layers without)
+    blocks = [
+        ("Block", lambda ls: Block(C, H), (False,), one, (None, None), [sa, ml], ["self_attention", "mlp"]),
+        ("SelfAttentionBlock", lambda ls: SelfAttentionBlock(init_values=0.1 if ls else None, **kw), (False, True), one, ("ls1", "ls2"),
+         [sa, ml], ["self_attention", "mlp"]),
+        ("CrossAttentionBlock", lambda ls: CrossAttentionBlock(init_values=0.1 if ls else None, **kw), (False, True), two,
+         ("ls1", "ls2", "ls3"), [sa, ca, ml], ["self_attention", "cross_attention", "mlp"]),
+        ("CrossAttentionBlock/raw y", lambda ls: CrossAttentionBlock(init_values=0.1 if ls else None, norm_cross_tokens=False, **kw),
+         (False, True), two, ("ls1", "ls2", "ls3"), [sa, ca, ml], ["self_attention", "cross_attention", "mlp"]),
+        ("DiffSelfAttentionBlock", lambda ls: DiffSelfAttentionBlock(depth=1, init_values=0.1 if ls else None, **kw), (False, True), one,
+         ("ls1", "ls2"), [ds, ml], [ds, "mlp"]),
+        ("DiffCrossAttentionBlock", lambda ls: DiffCrossAttentionBlock(depth=1, init_values=0.1 if ls else None, **kw), (False, True), two,
+         ("ls1", "ls2", "ls3"), [sa, dc, ml], ["self_attention", dc, "mlp"]),
+        ("dinov2 _Block", lambda ls: _Block(C, H), (True,), enc, ("ls1", "ls2"), [sa, ml], ["self_attention", "mlp"]),
+        ("dinov2 _Block/swiglu", lambda ls: _Block(C, H, swiglu=True), (True,), enc, ("ls1", "ls2"), [sa, sw], ["self_attention", "mlp_swiglu"]),
+        ("ResidualAttentionBlock", pe_block, (False, True), enc, ("ls_1", "ls_2"), [sa, ml], ["self_attention", "mlp"]),
+    ]
+    for name, build, ls_options, call, ls_attrs, with_grad, without in blocks:
+        for ls in ls_options:
+            blk = build(ls).eval()
+            gammas = [getattr(getattr(blk, a), "gamma") if (a and ls) else None for a in ls_attrs]
+            x, y = torch.randn(B * N, C), torch.randn(B * Ny, C)
+            # ---- with gradients
+            log.clear(), built.clear()
+            out = call(blk, x.requires_grad_(True), y)
+            assert [e["name"] for e in log] == with_grad and not built, (name, ls, [e["name"] for e in log], len(built))
+            prev = x
+            for e, g in zip(log, gammas):
+                assert e["x"] is prev and e["gamma"] is g and e["drops"] is None and e["attn_drop"] is None, (name, ls, e["name"])
+                prev = e["out"]
+            assert out is prev
+            # ---- without
+            log.clear(), built.clear()
+            with torch.no_grad():
+                out = call(blk, x.detach(), y)
+            x0 = prev = log[0]["x"]
+            i = 0
+            for sub, g in zip(without, gammas):
+                if sub in (ds, dc):
+                    e = log[i]
+                    i += 1
+                    assert e["name"] == sub and e["x"] is prev and e["gamma"] is g and e["drops"] is None, (name, ls, sub)
+                else:
+                    raw_y = sub == "cross_attention" and "raw y" in name
+                    n_ln = 2 if sub == "cross_attention" and not raw_y else 1
+                    lns, e = log[i:i + n_ln], log[i + n_ln]
+                    i += n_ln + 1
+                    assert all(l["name"] == "ln_operand" for l in lns) and lns[-1]["x"] is prev, (name, ls, sub)
+                    assert e["name"] == sub and e["h"] is prev and e["x"] is prev and e["out_dtype"] == prev.dtype and e["emit_ln"] is True
+                    folds = [("fold", l["ln"]) for l in reversed(lns)] + ([None] if raw_y else [])
+                    assert e["folds"] == folds, (name, ls, sub)
+                    if sub == "cross_attention" and not raw_y:
+                        assert lns[0]["x"] is y and lns[0]["ln"] is blk.norm_y and lns[1]["ln"] is blk.norm2
+                    assert (e["wb"] is not None) == (g is not None), (name, ls, sub)
+                prev = e["out"]
+            assert i == len(log) and out is prev and x0.data_ptr() == x.data_ptr(), (name, ls)
+            assert len(built) == sum(g is not None and s not in (ds, dc) for s, g in zip(without, gammas)), (name, ls)
+
+    # ---- the masks: autograd.make_drops / attn_dropout through the module attribute, once per sub-layer, in the block's order
+    drawn = []
+
+    def make_drops(training, device, B_, N_, C_, p_out=0.0, p_path=0.0, hidden=0, p_mid=0.0, scale_by_keep=True):
+        drawn.append(("drops", training, p_out, p_path, p_mid, hidden))
+        return drawn[-1]
+
+    def attn_dropout(training, p):
+        drawn.append(("seed", training, p))
+        return drawn[-1]
+
+    monkeypatch.setattr(autograd, "make_drops", make_drops)
+    monkeypatch.setattr(autograd, "attn_dropout", attn_dropout)
+    hid = 4 * C
+    d_sa, d_ca, d_ml = ("drops", True, 0.11, 0.3, 0.0, 0), ("drops", True, 0.12, 0.3, 0.0, 0), ("drops", True, 0.14, 0.3, 0.13, hid)
+    s_sa, s_ca = ("seed", True, 0.21), ("seed", True, 0.22)
+    orders = [
+        (Block(C, H, drop_path=0.3), one, [s_sa, d_sa, d_ml], [(d_sa, s_sa), (d_ml, None)]),
+        (SelfAttentionBlock(drop_path=0.3, **kw), one, [s_sa, d_sa, d_ml], [(d_sa, s_sa), (d_ml, None)]),
+        (CrossAttentionBlock(drop_path=0.3, **kw), two, [s_sa, s_ca, d_sa, d_ca, d_ml], [(d_sa, s_sa), (d_ca, s_ca), (d_ml, None)]),
+        (DiffSelfAttentionBlock(depth=1, drop_path=0.3, **kw), one, [d_sa, d_ml], [(d_sa, None), (d_ml, None)]),
+        (DiffCrossAttentionBlock(depth=1, drop_path=0.3, **kw), two, [d_ca, s_sa, d_sa, d_ml], [(d_sa, s_sa), (d_ca, None), (d_ml, None)]),
+    ]
+    for blk, call, order, per_sublayer in orders:
+        blk.train()
+        diff_self, diff_cross = isinstance(blk, DiffSelfAttentionBlock), isinstance(blk, DiffCrossAttentionBlock)
+        blk.attn.proj_drop.p, blk.mlp.drop1.p, blk.mlp.drop2.p = 0.11, 0.13, 0.14
+        if not diff_self:
+            blk.attn.attn_drop.p = 0.21
+            if hasattr(blk.attn, "dropout_p"):
+                blk.attn.dropout_p = 0.21
+        if hasattr(blk, "cross_attn"):
+            blk.cross_attn.proj_drop.p = 0.12
+            if not diff_cross:
+                blk.cross_attn.attn_drop.p = 0.22
+        log.clear(), drawn.clear()
+        call(blk, torch.randn(B * N, C, requires_grad=True), torch.randn(B * Ny, C))
+        assert drawn == order, (type(blk).__name__, drawn)
+        assert [(e["drops"], e["attn_drop"]) for e in log] == per_sublayer, type(blk).__name__
+
+    # ---- train mode without gradients: any rate > 0 is refused
+    makers = [lambda **o: Block(C, H, drop=o.get("proj_drop", 0.0), attn_drop=o.get("attn_drop", 0.0), drop_path=o.get("drop_path", 0.0)),
+              lambda **o: SelfAttentionBlock(**kw, **o), lambda **o: CrossAttentionBlock(**kw, **o),
+              lambda **o: DiffSelfAttentionBlock(depth=1, **kw, **o), lambda **o: DiffCrossAttentionBlock(depth=1, **kw, **o)]
+    for make, call in zip(makers, (one, one, two, one, two)):
+        with torch.no_grad():
+            call(make().train(), torch.randn(B * N, C), torch.randn(B * Ny, C))           # rate 0 in train mode: runs
+        for option in ("proj_drop", "attn_drop", "drop_path"):
+            blk = make(**{option: 0.1})
+            with torch.no_grad():
+                call(blk.eval(), torch.randn(B * N, C), torch.randn(B * Ny, C))           # eval mode: runs
+                with pytest.raises(UcHipError):
+                    call(blk.train(), torch.randn(B * N, C), torch.randn(B * Ny, C))

@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import autograd, engine, ops
+from ..utils import sublayers
 from ..utils.intermediate_feature_return import IntermediateFeatureReturner, feature_take_indices
 from .base import UniCeptionViTEncoderBase, ViTEncoderInput, ViTEncoderOutput
 
@@ -80,24 +81,14 @@ class _Block(nn.Module):
         self.ls2 = _LayerScale(dim)
 
     def forward_tokens(self, x2d, B, N, dt):
-        if autograd.grad_needed(x2d, *self.parameters()):
-            x2d = autograd.self_attn_sublayer(x2d, self.norm1, self.attn.qkv, self.attn.proj, B, N, self.attn.num_heads, None, None,
-                                              self.attn.scale, dt, gamma=self.ls1.gamma)
-            if isinstance(self.mlp, _SwiGLUFFN):
-                return autograd.swiglu_sublayer(x2d, self.norm2, self.mlp.w12, self.mlp.w3, dt, gamma=self.ls2.gamma)
-            return autograd.mlp_sublayer(x2d, self.norm2, self.mlp.fc1, self.mlp.fc2, "gelu", dt, gamma=self.ls2.gamma)
-        # (the same pipeline as utils/transformer_blocks.SelfAttentionBlock: LayerNorms folded into the QKV / fc1 GEMMs once a producer
-        # GEMM has left the row statistics — from the first proj on —, LayerScale folded into the proj / fc2 weights)
-        h, fold = engine.ln_operand(x2d, self.norm1, dt)
-        x2d = engine.self_attention(h, B, N, self.attn.qkv, self.attn.proj, self.attn.num_heads, None, None, self.attn.scale,
-                                    x2d, x2d.dtype, proj_wb=engine.layerscale_lin_weights(self.attn.proj, self.ls1.gamma, dt),
-                                    fold=fold, emit_ln=True)
-        h, fold = engine.ln_operand(x2d, self.norm2, dt)
-        if isinstance(self.mlp, _SwiGLUFFN):
-            return engine.mlp_swiglu(h, self.mlp.w12, self.mlp.w3, x2d, x2d.dtype,
-                                     w3_wb=engine.layerscale_lin_weights(self.mlp.w3, self.ls2.gamma, dt), fold=fold, emit_ln=True)
-        return engine.mlp(h, self.mlp.fc1, self.mlp.fc2, "gelu", x2d, x2d.dtype,
-                          fc2_wb=engine.layerscale_lin_weights(self.mlp.fc2, self.ls2.gamma, dt), fold=fold, emit_ln=True)
+        # (the same sub-layers as utils/transformer_blocks.SelfAttentionBlock, without a positional encoding and always with LayerScale)
+        a, mlp = self.attn, self.mlp
+        train = autograd.grad_needed(x2d, *self.parameters())
+        x2d = sublayers.self_attn(x2d, self.norm1, a.qkv, a.proj, B, N, a.num_heads, None, None, a.scale, dt, train=train,
+                                  gamma=sublayers.gamma_of(self.ls1))
+        if isinstance(mlp, _SwiGLUFFN):
+            return sublayers.swiglu(x2d, self.norm2, mlp.w12, mlp.w3, dt, train=train, gamma=sublayers.gamma_of(self.ls2))
+        return sublayers.mlp(x2d, self.norm2, mlp.fc1, mlp.fc2, mlp.act, dt, train=train, gamma=sublayers.gamma_of(self.ls2))
 
 
 class _PatchEmbed(nn.Module):

@@ -12,7 +12,9 @@ import torch
 import torch.nn as nn
 
 from .... import autograd, engine
+from ...utils import sublayers
 from ...utils.config import use_fused_attn
+from ...utils.sublayers import as_dt
 
 use_torch_attn = use_fused_attn()
 
@@ -48,22 +50,6 @@ class DropPath(nn.Module):
         return f"drop_prob={round(self.drop_prob, 3):0.3f}"
 
 
-def _check_no_dropout(module, *ps):
-    if module.training and any(p > 0.0 for p in ps):
-        raise engine.UcHipError("dropout > 0 in training mode is not supported by the HIP path")
-
-
-def _drop_path_rate(m):
-    "(rate, scale_by_keep) of a block's drop_path module (nn.Identity: 0)"
-    return (m.drop_prob, m.scale_by_keep) if isinstance(m, DropPath) else (0.0, True)
-
-
-def _check_attn_drop(module, p):
-    "Kept for callers outside the blocks: attention dropout runs inside the sub-layer Functions since round 6 (autograd.attn_dropout)."
-    if module.training and p > 0.0 and not torch.is_grad_enabled():
-        raise engine.UcHipError("attn_drop > 0 in train mode without gradients has no HIP form (the inference kernels apply no dropout)")
-
-
 def _as_2d(x):
     B, N, C = x.shape
     if x.dtype not in (torch.float32, torch.bfloat16):
@@ -86,17 +72,13 @@ class Mlp(nn.Module):
         self.fc2 = nn.Linear(hidden_features, out_features, bias=bias[1])
         self.drop2 = nn.Dropout(drop_probs[1])
 
-    def _run(self, h2d, residual, out_dtype, fold=None, emit_ln=False, fc2_wb=None):
-        _check_no_dropout(self, self.drop1.p, self.drop2.p)
-        return engine.mlp(h2d, self.fc1, self.fc2, engine.act_name(self.act), residual, out_dtype, fc2_wb=fc2_wb, fold=fold, emit_ln=emit_ln)
-
     def forward(self, x):
         engine.require_inference(x, self.fc1.weight)
+        sublayers.refuse_drops(self.training, False, self.drop1.p, self.drop2.p)
         dt = engine.compute_dtype()
         shp = x.shape
-        x2 = x.reshape(-1, shp[-1])
-        h = x2 if x2.dtype == dt else engine.ops.convert(x2.contiguous(), dt)
-        return self._run(h.contiguous(), None, dt).view(*shp[:-1], -1)
+        h = as_dt(x.reshape(-1, shp[-1]).contiguous(), dt)
+        return engine.mlp(h, self.fc1, self.fc2, engine.act_name(self.act), None, dt).view(*shp[:-1], -1)
 
 
 class Attention(nn.Module):
@@ -115,18 +97,13 @@ class Attention(nn.Module):
         self.torch_attn = torch_attn
         self.dropout_p = attn_drop
 
-    def _run(self, h2d, B, N, xpos, residual, out_dtype, fold=None, emit_ln=False):
-        _check_no_dropout(self, self.dropout_p, self.proj_drop.p)
-        return engine.self_attention(h2d, B, N, self.qkv, self.proj, self.num_heads, self.rope, xpos, self.scale,
-                                     residual, out_dtype, fold=fold, emit_ln=emit_ln)
-
     def forward(self, x, xpos):
         engine.require_inference(x, self.qkv.weight)
+        sublayers.refuse_drops(self.training, False, self.dropout_p, self.proj_drop.p)
         B, N, C = x.shape
         dt = engine.compute_dtype()
-        x2 = _as_2d(x)
-        h = x2 if x2.dtype == dt else engine.ops.convert(x2, dt)
-        return self._run(h, B, N, xpos, None, dt).view(B, N, C)
+        return engine.self_attention(as_dt(_as_2d(x), dt), B, N, self.qkv, self.proj, self.num_heads, self.rope, xpos, self.scale,
+                                     None, dt).view(B, N, C)
 
 
 class Block(nn.Module):
@@ -144,24 +121,15 @@ class Block(nn.Module):
 
     def forward_tokens(self, x2d, B, N, xpos, dt):
         """[B*N, C] residual stream in, new residual stream out (same dtype)."""
-        if autograd.grad_needed(x2d, *self.parameters()):
-            # dropout (round 5): proj_drop / the Mlp's drops / DropPath as masks through the sub-layer Functions (autograd.make_drops)
-            ad = autograd.attn_dropout(self.training, self.attn.dropout_p)      # (round 6: inside the attention kernels, forward and backward)
-            C = x2d.shape[1]
-            pp, sbk = _drop_path_rate(self.drop_path)
-            d1 = autograd.make_drops(self.training, x2d.device, B, N, C, p_out=self.attn.proj_drop.p, p_path=pp, scale_by_keep=sbk)
-            d2 = autograd.make_drops(self.training, x2d.device, B, N, C, p_out=self.mlp.drop2.p, p_path=pp, hidden=self.mlp.fc1.out_features,
-                                     p_mid=self.mlp.drop1.p, scale_by_keep=sbk)
-            x2d = autograd.self_attn_sublayer(x2d, self.norm1, self.attn.qkv, self.attn.proj, B, N, self.attn.num_heads,
-                                              self.attn.rope, xpos, self.attn.scale, dt, drops=d1, attn_drop=ad)
-            return autograd.mlp_sublayer(x2d, self.norm2, self.mlp.fc1, self.mlp.fc2, engine.act_name(self.mlp.act), dt, drops=d2)
-        if isinstance(self.drop_path, DropPath):
-            self.drop_path(x2d)  # (train mode without gradients: raises at rate > 0)
-        # LayerNorm -> GEMM pairs run fused when the stream carries its producer's bf16 twin + row statistics (engine.ln_operand)
-        h, fold = engine.ln_operand(x2d, self.norm1, dt)
-        x2d = self.attn._run(h, B, N, xpos, x2d, x2d.dtype, fold, True)
-        h, fold = engine.ln_operand(x2d, self.norm2, dt)
-        return self.mlp._run(h, x2d, x2d.dtype, fold, True)
+        sa, mlp, training = self.attn, self.mlp, self.training
+        train = autograd.grad_needed(x2d, *self.parameters())
+        # the masks, in this block's generator order: the attention kernels' seed, proj_drop + DropPath, the Mlp's drops + DropPath
+        ad = sublayers.attn_drop_for(training, train, sa.dropout_p)
+        d1 = sublayers.drops_for(training, train, x2d, B, N, sa.proj_drop.p, self.drop_path)
+        d2 = sublayers.drops_for(training, train, x2d, B, N, mlp.drop2.p, self.drop_path, mlp.drop1.p, mlp.fc1.out_features)
+        x2d = sublayers.self_attn(x2d, self.norm1, sa.qkv, sa.proj, B, N, sa.num_heads, sa.rope, xpos, sa.scale, dt, train=train,
+                                  drops=d1, attn_drop=ad)
+        return sublayers.mlp(x2d, self.norm2, mlp.fc1, mlp.fc2, mlp.act, dt, train=train, drops=d2)
 
     def forward(self, x, xpos):
         B, N, C = x.shape

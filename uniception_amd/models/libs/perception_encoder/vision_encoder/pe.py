@@ -25,6 +25,7 @@ from torch.nn.init import constant_, xavier_uniform_
 
 from ..... import autograd, engine, ops
 from ....libs.croco.pos_embed import RoPE2D
+from ....utils import sublayers
 from .config import PE_VISION_CONFIG
 
 HEAD_DIM = 64          # what the bf16 attention kernels take
@@ -140,17 +141,11 @@ class ResidualAttentionBlock(nn.Module):
                                               ("c_proj", nn.Linear(mlp_width, d_model))]))
 
     def forward_tokens(self, x2d, B, N, dt, pos=None):
-        a, act = self.attn, engine.act_name(self.mlp.gelu)
-        g1, g2 = getattr(self.ls_1, "gamma", None), getattr(self.ls_2, "gamma", None)
-        if autograd.grad_needed(x2d, *self.parameters()):
-            x2d = autograd.self_attn_sublayer(x2d, self.ln_1, a.in_proj(True), a.out_proj, B, N, a.num_heads, a.rope, pos, a.scale, dt, gamma=g1)
-            return autograd.mlp_sublayer(x2d, self.ln_2, self.mlp.c_fc, self.mlp.c_proj, act, dt, gamma=g2)
-        h, fold = engine.ln_operand(x2d, self.ln_1, dt)
-        x2d = engine.self_attention(h, B, N, a.in_proj(False), a.out_proj, a.num_heads, a.rope, pos, a.scale, x2d, x2d.dtype,
-                                    proj_wb=None if g1 is None else engine.layerscale_lin_weights(a.out_proj, g1, dt), fold=fold, emit_ln=True)
-        h, fold = engine.ln_operand(x2d, self.ln_2, dt)
-        return engine.mlp(h, self.mlp.c_fc, self.mlp.c_proj, act, x2d, x2d.dtype,
-                          fc2_wb=None if g2 is None else engine.layerscale_lin_weights(self.mlp.c_proj, g2, dt), fold=fold, emit_ln=True)
+        a, mlp = self.attn, self.mlp
+        train = autograd.grad_needed(x2d, *self.parameters())
+        x2d = sublayers.self_attn(x2d, self.ln_1, a.in_proj(train), a.out_proj, B, N, a.num_heads, a.rope, pos, a.scale, dt, train=train,
+                                  gamma=sublayers.gamma_of(self.ls_1))
+        return sublayers.mlp(x2d, self.ln_2, mlp.c_fc, mlp.c_proj, mlp.gelu, dt, train=train, gamma=sublayers.gamma_of(self.ls_2))
 
 
 class Transformer(nn.Module):

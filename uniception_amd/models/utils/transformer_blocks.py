@@ -14,8 +14,16 @@ import torch
 import torch.nn as nn
 
 from ... import autograd, engine
-from ..libs.croco.blocks import DropPath, Mlp, _as_2d, _check_attn_drop, _check_no_dropout, _drop_path_rate, to_2tuple  # noqa: F401
+from ..libs.croco.blocks import DropPath, Mlp, _as_2d, to_2tuple  # noqa: F401
+from . import sublayers
 from .config import use_fused_attn
+from .sublayers import as_dt
+
+
+def _std_mlp(mlp):
+    if not isinstance(mlp, Mlp):
+        raise engine.UcHipError("only the standard Mlp layer has a fused HIP pipeline")
+    return mlp
 
 
 def _softmax_scale_multiplier(module, n_tokens: int) -> float:
@@ -63,22 +71,16 @@ class Attention(nn.Module):
         self.base_token_count_for_entropy_scaling = base_token_count_for_entropy_scaling
         self.entropy_scaling_growth_factor = entropy_scaling_growth_factor
 
-    def _run(self, h2d, B, N, xpos, residual, out_dtype, fold=None, emit_ln=False, proj_wb=None):
-        _check_no_dropout(self, self.attn_drop.p, self.proj_drop.p)
-        if self.custom_positional_encoding is not None:
-            assert xpos is not None, "Positions of tokens (xpos) are a required input when using custom positional encoding"
-        scale = self.scale * _softmax_scale_multiplier(self, N)
-        return engine.self_attention(h2d, B, N, self.qkv, self.proj, self.num_heads, self.custom_positional_encoding, xpos,
-                                     scale, residual, out_dtype, proj_wb=proj_wb, fold=fold, emit_ln=emit_ln, q_norm=self.q_norm,
-                                     k_norm=self.k_norm)
-
     def forward(self, x: torch.Tensor, xpos: torch.Tensor = None) -> torch.Tensor:
         engine.require_inference(x, self.qkv.weight)
+        sublayers.refuse_drops(self.training, False, self.attn_drop.p, self.proj_drop.p)
+        if self.custom_positional_encoding is not None:
+            assert xpos is not None, "Positions of tokens (xpos) are a required input when using custom positional encoding"
         B, N, C = x.shape
         dt = engine.compute_dtype()
-        x2 = _as_2d(x)
-        h = x2 if x2.dtype == dt else engine.ops.convert(x2, dt)
-        return self._run(h, B, N, xpos, None, dt).view(B, N, C)
+        return engine.self_attention(as_dt(_as_2d(x), dt), B, N, self.qkv, self.proj, self.num_heads, self.custom_positional_encoding, xpos,
+                                     self.scale * _softmax_scale_multiplier(self, N), None, dt, q_norm=self.q_norm,
+                                     k_norm=self.k_norm).view(B, N, C)
 
 
 class CrossAttention(nn.Module):
@@ -108,32 +110,23 @@ class CrossAttention(nn.Module):
         self.base_token_count_for_entropy_scaling = base_token_count_for_entropy_scaling
         self.entropy_scaling_growth_factor = entropy_scaling_growth_factor
 
-    def _run(self, hq2d, hkv2d, B, Nq, Nk, qpos, kpos, residual, out_dtype, fold_q=None, fold_kv=None, emit_ln=False, hv2d=None,
-             proj_wb=None):
-        _check_no_dropout(self, self.attn_drop.p, self.proj_drop.p)
+    def forward(self, query, key, value, qpos=None, kpos=None):
+        engine.require_inference(query, key, value, self.projq.weight)
+        sublayers.refuse_drops(self.training, False, self.attn_drop.p, self.proj_drop.p)
         if self.custom_positional_encoding is not None:
             assert qpos is not None, "Positions of queries (qpos) are a required input when using custom positional encoding"
             assert kpos is not None, "Positions of keys (kpos) are a required input when using custom positional encoding"
-        scale = self.scale * _softmax_scale_multiplier(self, Nq)
-        return engine.cross_attention(hq2d, hkv2d, B, Nq, Nk, self.projq, self.projk, self.projv, self.proj, self.num_heads,
-                                      self.custom_positional_encoding, qpos, kpos, scale, residual, out_dtype,
-                                      fold_q=fold_q, fold_kv=fold_kv, emit_ln=emit_ln, q_norm=self.q_norm, k_norm=self.k_norm, hv2d=hv2d,
-                                      proj_wb=proj_wb)
-
-    def forward(self, query, key, value, qpos=None, kpos=None):
-        engine.require_inference(query, key, value, self.projq.weight)
         B, Nq, C = query.shape
         Nk = key.shape[1]
         dt = engine.compute_dtype()
-        q2, k2 = _as_2d(query), _as_2d(key)
-        hq = q2 if q2.dtype == dt else engine.ops.convert(q2, dt)
-        hk = k2 if k2.dtype == dt else engine.ops.convert(k2, dt)
+        hq, hk = as_dt(_as_2d(query), dt), as_dt(_as_2d(key), dt)
         hv = None
         if value is not key:      # (utils/transformer_blocks.py:341-348: projv runs on its own tokens)
             assert value.shape[1] == Nk, "key and value must have the same number of tokens"
-            v2 = _as_2d(value)
-            hv = v2 if v2.dtype == dt else engine.ops.convert(v2, dt)
-        return self._run(hq, hk, B, Nq, Nk, qpos, kpos, None, dt, hv2d=hv).view(B, Nq, C)
+            hv = as_dt(_as_2d(value), dt)
+        return engine.cross_attention(hq, hk, B, Nq, Nk, self.projq, self.projk, self.projv, self.proj, self.num_heads,
+                                      self.custom_positional_encoding, qpos, kpos, self.scale * _softmax_scale_multiplier(self, Nq), None, dt,
+                                      q_norm=self.q_norm, k_norm=self.k_norm, hv2d=hv).view(B, Nq, C)
 
 
 class LayerScale(nn.Module):
@@ -179,37 +172,18 @@ class SelfAttentionBlock(nn.Module):
 
     def forward_tokens(self, x2d, B, N, xpos, dt):
         """[B*N, C] fp32 residual stream in, new residual stream out; attention spans the N tokens of each of the B sequences."""
-        if not isinstance(self.mlp, Mlp):
-            raise engine.UcHipError("only the standard Mlp layer has a fused HIP pipeline")
+        sa, mlp, training = self.attn, _std_mlp(self.mlp), self.training
         if self.custom_positional_encoding is not None:
             assert xpos is not None, "Positions of tokens (xpos) are a required input when using custom positional encoding"
-        sa = self.attn
-        if autograd.grad_needed(x2d, *self.parameters()):   # HIP forward + HIP backward sub-layers
-            ad = autograd.attn_dropout(self.training, sa.attn_drop.p)       # (round 6: inside the attention kernels, forward and backward)
-            C = x2d.shape[1]
-            (p1, k1), (p2, k2) = _drop_path_rate(self.drop_path1), _drop_path_rate(self.drop_path2)
-            d1 = autograd.make_drops(self.training, x2d.device, B, N, C, p_out=sa.proj_drop.p, p_path=p1, scale_by_keep=k1)
-            d2 = autograd.make_drops(self.training, x2d.device, B, N, C, p_out=self.mlp.drop2.p, p_path=p2, hidden=self.mlp.fc1.out_features,
-                                     p_mid=self.mlp.drop1.p, scale_by_keep=k2)
-            g1 = None if isinstance(self.ls1, nn.Identity) else self.ls1.gamma       # LayerScale: folded weights forward, unfolded gradients
-            g2 = None if isinstance(self.ls2, nn.Identity) else self.ls2.gamma
-            x2d = autograd.self_attn_sublayer(x2d, self.norm1, sa.qkv, sa.proj, B, N, sa.num_heads, sa.custom_positional_encoding,
-                                              xpos, sa.scale * _softmax_scale_multiplier(sa, N), dt, gamma=g1, q_norm=sa.q_norm,
-                                              k_norm=sa.k_norm, drops=d1, attn_drop=ad)
-            return autograd.mlp_sublayer(x2d, self.norm2, self.mlp.fc1, self.mlp.fc2, engine.act_name(self.mlp.act), dt, gamma=g2, drops=d2)
-        _check_no_dropout(self, sa.attn_drop.p, sa.proj_drop.p, self.mlp.drop1.p, self.mlp.drop2.p)
-        for dp in (self.drop_path1, self.drop_path2):
-            if isinstance(dp, DropPath) and dp.drop_prob > 0 and self.training:
-                raise engine.UcHipError("DropPath with drop_prob > 0 in train mode without gradients has no HIP form")
-        proj_wb = None if isinstance(self.ls1, nn.Identity) else engine.layerscale_lin_weights(sa.proj, self.ls1.gamma, dt)
-        fc2_wb = None if isinstance(self.ls2, nn.Identity) else engine.layerscale_lin_weights(self.mlp.fc2, self.ls2.gamma, dt)
-        h, fold = engine.ln_operand(x2d, self.norm1, dt)
-        x2d = engine.self_attention(h, B, N, sa.qkv, sa.proj, sa.num_heads, sa.custom_positional_encoding, xpos,
-                                    sa.scale * _softmax_scale_multiplier(sa, N), x2d, x2d.dtype, proj_wb=proj_wb, fold=fold, emit_ln=True,
-                                    q_norm=sa.q_norm, k_norm=sa.k_norm)
-        h, fold = engine.ln_operand(x2d, self.norm2, dt)
-        return engine.mlp(h, self.mlp.fc1, self.mlp.fc2, engine.act_name(self.mlp.act), x2d, x2d.dtype, fc2_wb=fc2_wb, fold=fold,
-                          emit_ln=True)
+        train = autograd.grad_needed(x2d, *self.parameters())
+        # the masks, in this block's generator order: the attention kernels' seed, proj_drop + DropPath, the Mlp's drops + DropPath
+        ad = sublayers.attn_drop_for(training, train, sa.attn_drop.p)
+        d1 = sublayers.drops_for(training, train, x2d, B, N, sa.proj_drop.p, self.drop_path1)
+        d2 = sublayers.drops_for(training, train, x2d, B, N, mlp.drop2.p, self.drop_path2, mlp.drop1.p, mlp.fc1.out_features)
+        x2d = sublayers.self_attn(x2d, self.norm1, sa.qkv, sa.proj, B, N, sa.num_heads, sa.custom_positional_encoding, xpos,
+                                  sa.scale * _softmax_scale_multiplier(sa, N), dt, train=train, gamma=sublayers.gamma_of(self.ls1),
+                                  q_norm=sa.q_norm, k_norm=sa.k_norm, drops=d1, attn_drop=ad)
+        return sublayers.mlp(x2d, self.norm2, mlp.fc1, mlp.fc2, mlp.act, dt, train=train, gamma=sublayers.gamma_of(self.ls2), drops=d2)
 
     def forward(self, x: torch.Tensor, xpos: torch.Tensor = None) -> torch.Tensor:
         B, N, C = x.shape
@@ -249,61 +223,27 @@ class CrossAttentionBlock(nn.Module):
         self.ls3 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
         self.drop_path3 = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
 
-    def _gammas(self):
-        "LayerScale parameters of the three sub-layers (None where init_values was None)."
-        return tuple(None if isinstance(ls, nn.Identity) else ls.gamma for ls in (self.ls1, self.ls2, self.ls3))
-
-    def _check_supported(self):
-        if not isinstance(self.mlp, Mlp):
-            raise engine.UcHipError("only the standard Mlp layer has a fused HIP pipeline")
-
     def forward_tokens(self, x2d, y2d, B, Nx, Ny, xpos, ypos, dt):
         """x2d [B*Nx, C] residual stream, y2d [B*Ny, C] other-view tokens (previous depth) -> new x2d."""
-        self._check_supported()
-        if self.custom_positional_encoding is not None:
+        sa, ca, mlp, training = self.attn, self.cross_attn, _std_mlp(self.mlp), self.training
+        rope = self.custom_positional_encoding
+        if rope is not None:
             assert xpos is not None, "Positions of tokens (xpos) are a required input when using custom positional encoding"
             assert ypos is not None, "Positions of cross tokens (ypos) are a required input when using custom positional encoding"
-        if autograd.grad_needed(x2d, y2d, *self.parameters()):
-            return self._forward_tokens_train(x2d, y2d, B, Nx, Ny, xpos, ypos, dt)
-        for dp in (self.drop_path1, self.drop_path2, self.drop_path3):
-            if isinstance(dp, DropPath) and dp.drop_prob > 0 and self.training:
-                raise engine.UcHipError("DropPath with drop_prob > 0 in train mode without gradients has no HIP form")
-        # LayerNorm -> GEMM pairs run fused when a stream carries its producer's bf16 twin + row statistics (engine.ln_operand)
-        g1, g2, g3 = self._gammas()        # LayerScale (utils/transformer_blocks.py:584-647): folded into proj / fc2, no kernel work
-        wb1 = None if g1 is None else engine.layerscale_lin_weights(self.attn.proj, g1, dt)
-        wb2 = None if g2 is None else engine.layerscale_lin_weights(self.cross_attn.proj, g2, dt)
-        wb3 = None if g3 is None else engine.layerscale_lin_weights(self.mlp.fc2, g3, dt)
-        h, fold = engine.ln_operand(x2d, self.norm1, dt)
-        x2d = self.attn._run(h, B, Nx, xpos, x2d, x2d.dtype, fold, True, proj_wb=wb1)
-        if isinstance(self.norm_y, nn.Identity):
-            yn, fold_y = (y2d if y2d.dtype == dt else engine.ops.convert(y2d, dt)), None
-        else:
-            yn, fold_y = engine.ln_operand(y2d, self.norm_y, dt)
-        h, fold = engine.ln_operand(x2d, self.norm2, dt)
-        x2d = self.cross_attn._run(h, yn, B, Nx, Ny, xpos, ypos, x2d, x2d.dtype, fold, fold_y, True, proj_wb=wb2)
-        h, fold = engine.ln_operand(x2d, self.norm3, dt)
-        return self.mlp._run(h, x2d, x2d.dtype, fold, True, fc2_wb=wb3)
-
-    def _forward_tokens_train(self, x2d, y2d, B, Nx, Ny, xpos, ypos, dt):
-        """Same three sub-layers as autograd Functions (HIP forward + HIP backward)."""
-        sa, ca = self.attn, self.cross_attn
-        ad1 = autograd.attn_dropout(self.training, sa.attn_drop.p)          # (round 6: inside the attention kernels, forward and backward)
-        ad2 = autograd.attn_dropout(self.training, ca.attn_drop.p)
-        C, dev = x2d.shape[1], x2d.device
-        (p1, k1), (p2, k2), (p3, k3) = (_drop_path_rate(m) for m in (self.drop_path1, self.drop_path2, self.drop_path3))
-        d1 = autograd.make_drops(self.training, dev, B, Nx, C, p_out=sa.proj_drop.p, p_path=p1, scale_by_keep=k1)
-        d2 = autograd.make_drops(self.training, dev, B, Nx, C, p_out=ca.proj_drop.p, p_path=p2, scale_by_keep=k2)
-        d3 = autograd.make_drops(self.training, dev, B, Nx, C, p_out=self.mlp.drop2.p, p_path=p3, hidden=self.mlp.fc1.out_features,
-                                 p_mid=self.mlp.drop1.p, scale_by_keep=k3)
-        rope = self.custom_positional_encoding
-        g1, g2, g3 = self._gammas()
-        x2d = autograd.self_attn_sublayer(x2d, self.norm1, sa.qkv, sa.proj, B, Nx, sa.num_heads, rope, xpos,
-                                          sa.scale * _softmax_scale_multiplier(sa, Nx), dt, gamma=g1, q_norm=sa.q_norm, k_norm=sa.k_norm,
-                                          drops=d1, attn_drop=ad1)
-        lny = None if isinstance(self.norm_y, nn.Identity) else self.norm_y
-        x2d = autograd.cross_attn_sublayer(x2d, y2d, self.norm2, lny, ca, B, Nx, Ny, ca.num_heads, rope, xpos, ypos,
-                                           ca.scale * _softmax_scale_multiplier(ca, Nx), dt, gamma=g2, drops=d2, attn_drop=ad2)
-        return autograd.mlp_sublayer(x2d, self.norm3, self.mlp.fc1, self.mlp.fc2, engine.act_name(self.mlp.act), dt, gamma=g3, drops=d3)
+        train = autograd.grad_needed(x2d, y2d, *self.parameters())
+        # the masks, in this block's generator order: both attention seeds, then the three sub-layers' output masks
+        ad1 = sublayers.attn_drop_for(training, train, sa.attn_drop.p)
+        ad2 = sublayers.attn_drop_for(training, train, ca.attn_drop.p)
+        d1 = sublayers.drops_for(training, train, x2d, B, Nx, sa.proj_drop.p, self.drop_path1)
+        d2 = sublayers.drops_for(training, train, x2d, B, Nx, ca.proj_drop.p, self.drop_path2)
+        d3 = sublayers.drops_for(training, train, x2d, B, Nx, mlp.drop2.p, self.drop_path3, mlp.drop1.p, mlp.fc1.out_features)
+        x2d = sublayers.self_attn(x2d, self.norm1, sa.qkv, sa.proj, B, Nx, sa.num_heads, rope, xpos,
+                                  sa.scale * _softmax_scale_multiplier(sa, Nx), dt, train=train, gamma=sublayers.gamma_of(self.ls1),
+                                  q_norm=sa.q_norm, k_norm=sa.k_norm, drops=d1, attn_drop=ad1)
+        x2d = sublayers.cross_attn(x2d, y2d, self.norm2, self.norm_y, ca, B, Nx, Ny, rope, xpos, ypos,
+                                   ca.scale * _softmax_scale_multiplier(ca, Nx), dt, train=train, gamma=sublayers.gamma_of(self.ls2),
+                                   drops=d2, attn_drop=ad2)
+        return sublayers.mlp(x2d, self.norm3, mlp.fc1, mlp.fc2, mlp.act, dt, train=train, gamma=sublayers.gamma_of(self.ls3), drops=d3)
 
     def forward(self, x, y, xpos=None, ypos=None):
         B, Nx, C = x.shape
@@ -448,37 +388,22 @@ class DiffSelfAttentionBlock(SelfAttentionBlock):
                                   proj_drop=proj_drop, norm_layer=norm_layer, custom_positional_encoding=custom_positional_encoding)
 
     def forward_tokens(self, x2d, B, N, xpos, dt):
-        if not isinstance(self.mlp, Mlp):
-            raise engine.UcHipError("only the standard Mlp layer has a fused HIP pipeline")
-        sa = self.attn
+        sa, mlp, training = self.attn, _std_mlp(self.mlp), self.training
         engine.check_diff_layer(sa)
         if self.custom_positional_encoding is not None:
             assert xpos is not None, "Positions of tokens (xpos) are a required input when using custom positional encoding"
         train = autograd.grad_needed(x2d, *self.parameters())
-        if not train:
-            for dp in (self.drop_path1, self.drop_path2):
-                if isinstance(dp, DropPath) and dp.drop_prob > 0 and self.training:
-                    raise engine.UcHipError("DropPath with drop_prob > 0 in train mode without gradients has no HIP form")
-            _check_no_dropout(self, sa.proj_drop.p, self.mlp.drop1.p, self.mlp.drop2.p)
-        C = x2d.shape[1]
-        g1 = None if isinstance(self.ls1, nn.Identity) else self.ls1.gamma
-        g2 = None if isinstance(self.ls2, nn.Identity) else self.ls2.gamma
-        (p1, k1), (p2, k2) = _drop_path_rate(self.drop_path1), _drop_path_rate(self.drop_path2)
-        d1 = autograd.make_drops(self.training and train, x2d.device, B, N, C, p_out=sa.proj_drop.p, p_path=p1, scale_by_keep=k1)
-        x2d = autograd.diff_self_attn_sublayer(x2d, self.norm1, sa, B, N, sa.custom_positional_encoding, xpos, dt, gamma=g1, drops=d1)
-        if train:
-            d2 = autograd.make_drops(self.training, x2d.device, B, N, C, p_out=self.mlp.drop2.p, p_path=p2, hidden=self.mlp.fc1.out_features,
-                                     p_mid=self.mlp.drop1.p, scale_by_keep=k2)
-            return autograd.mlp_sublayer(x2d, self.norm2, self.mlp.fc1, self.mlp.fc2, engine.act_name(self.mlp.act), dt, gamma=g2, drops=d2)
-        fc2_wb = None if g2 is None else engine.layerscale_lin_weights(self.mlp.fc2, g2, dt)
-        h, fold = engine.ln_operand(x2d, self.norm2, dt)
-        return engine.mlp(h, self.mlp.fc1, self.mlp.fc2, engine.act_name(self.mlp.act), x2d, x2d.dtype, fc2_wb=fc2_wb, fold=fold, emit_ln=True)
+        d1 = sublayers.drops_for(training, train, x2d, B, N, sa.proj_drop.p, self.drop_path1)
+        d2 = sublayers.drops_for(training, train, x2d, B, N, mlp.drop2.p, self.drop_path2, mlp.drop1.p, mlp.fc1.out_features)
+        x2d = autograd.diff_self_attn_sublayer(x2d, self.norm1, sa, B, N, sa.custom_positional_encoding, xpos, dt,
+                                               gamma=sublayers.gamma_of(self.ls1), drops=d1)
+        return sublayers.mlp(x2d, self.norm2, mlp.fc1, mlp.fc2, mlp.act, dt, train=train, gamma=sublayers.gamma_of(self.ls2), drops=d2)
 
 
 class DiffCrossAttentionBlock(CrossAttentionBlock):
     """Differential Cross-Attention Block (reference :997-1045): CrossAttentionBlock whose cross-attention is DiffCrossAttention.  The
-    plain self-attention (head_dim = dim / num_heads: 64 where the differential layer has 32 | 64) and the Mlp keep the parent's fused
-    sub-layers; the differential sub-layer is LayerNorm -> q / k / v GEMMs -> uc_rope2d -> the fused kernel -> proj."""
+    plain self-attention (head_dim = dim / num_heads: 64 where the differential layer has 32 | 64) and the Mlp are the runners'
+    sub-layers (sublayers.self_attn / sublayers.mlp); the differential sub-layer is LayerNorm -> q / k / v GEMMs -> uc_rope2d -> the fused kernel -> proj."""
 
     def __init__(self, dim: int, depth: int, num_heads: int, mlp_ratio: float = 4.0, qkv_bias: bool = False, qk_norm: bool = False,
                  proj_drop: float = 0.0, attn_drop: float = 0.0, init_values: Optional[float] = None, drop_path: float = 0.0,
@@ -492,37 +417,22 @@ class DiffCrossAttentionBlock(CrossAttentionBlock):
                                              custom_positional_encoding=custom_positional_encoding)
 
     def forward_tokens(self, x2d, y2d, B, Nx, Ny, xpos, ypos, dt):
-        self._check_supported()
-        sa, ca = self.attn, self.cross_attn
+        sa, ca, mlp, training = self.attn, self.cross_attn, _std_mlp(self.mlp), self.training
         engine.check_diff_layer(ca)      # (before the plain self-attention: an unsupported geometry is reported as the differential layer's)
         rope = self.custom_positional_encoding
         if rope is not None:
             assert xpos is not None, "Positions of tokens (xpos) are a required input when using custom positional encoding"
             assert ypos is not None, "Positions of cross tokens (ypos) are a required input when using custom positional encoding"
         train = autograd.grad_needed(x2d, y2d, *self.parameters())
-        g1, g2, g3 = self._gammas()
-        C, dev = x2d.shape[1], x2d.device
-        (p1, k1), (p2, k2), (p3, k3) = (_drop_path_rate(m) for m in (self.drop_path1, self.drop_path2, self.drop_path3))
+        # the masks, in this block's generator order: the differential sub-layer's first, then the attention seed and the other two
+        d2 = sublayers.drops_for(training, train, x2d, B, Nx, ca.proj_drop.p, self.drop_path2)
+        ad1 = sublayers.attn_drop_for(training, train, sa.attn_drop.p)
+        d1 = sublayers.drops_for(training, train, x2d, B, Nx, sa.proj_drop.p, self.drop_path1)
+        d3 = sublayers.drops_for(training, train, x2d, B, Nx, mlp.drop2.p, self.drop_path3, mlp.drop1.p, mlp.fc1.out_features)
+        x2d = sublayers.self_attn(x2d, self.norm1, sa.qkv, sa.proj, B, Nx, sa.num_heads, rope, xpos,
+                                  sa.scale * _softmax_scale_multiplier(sa, Nx), dt, train=train, gamma=sublayers.gamma_of(self.ls1),
+                                  q_norm=sa.q_norm, k_norm=sa.k_norm, drops=d1, attn_drop=ad1)
         lny = None if isinstance(self.norm_y, nn.Identity) else self.norm_y
-        d2 = autograd.make_drops(self.training and train, dev, B, Nx, C, p_out=ca.proj_drop.p, p_path=p2, scale_by_keep=k2)
-        if train:
-            ad1 = autograd.attn_dropout(self.training, sa.attn_drop.p)
-            d1 = autograd.make_drops(self.training, dev, B, Nx, C, p_out=sa.proj_drop.p, p_path=p1, scale_by_keep=k1)
-            d3 = autograd.make_drops(self.training, dev, B, Nx, C, p_out=self.mlp.drop2.p, p_path=p3, hidden=self.mlp.fc1.out_features,
-                                     p_mid=self.mlp.drop1.p, scale_by_keep=k3)
-            x2d = autograd.self_attn_sublayer(x2d, self.norm1, sa.qkv, sa.proj, B, Nx, sa.num_heads, rope, xpos,
-                                              sa.scale * _softmax_scale_multiplier(sa, Nx), dt, gamma=g1, q_norm=sa.q_norm, k_norm=sa.k_norm,
-                                              drops=d1, attn_drop=ad1)
-            x2d = autograd.diff_cross_attn_sublayer(x2d, y2d, self.norm2, lny, ca, B, Nx, Ny, rope, xpos, ypos, dt, gamma=g2, drops=d2)
-            return autograd.mlp_sublayer(x2d, self.norm3, self.mlp.fc1, self.mlp.fc2, engine.act_name(self.mlp.act), dt, gamma=g3, drops=d3)
-        for dp in (self.drop_path1, self.drop_path2, self.drop_path3):
-            if isinstance(dp, DropPath) and dp.drop_prob > 0 and self.training:
-                raise engine.UcHipError("DropPath with drop_prob > 0 in train mode without gradients has no HIP form")
-        _check_no_dropout(self, ca.proj_drop.p)
-        wb1 = None if g1 is None else engine.layerscale_lin_weights(sa.proj, g1, dt)
-        wb3 = None if g3 is None else engine.layerscale_lin_weights(self.mlp.fc2, g3, dt)
-        h, fold = engine.ln_operand(x2d, self.norm1, dt)
-        x2d = sa._run(h, B, Nx, xpos, x2d, x2d.dtype, fold, True, proj_wb=wb1)
-        x2d = autograd.diff_cross_attn_sublayer(x2d, y2d, self.norm2, lny, ca, B, Nx, Ny, rope, xpos, ypos, dt, gamma=g2, drops=d2)
-        h, fold = engine.ln_operand(x2d, self.norm3, dt)
-        return self.mlp._run(h, x2d, x2d.dtype, fold, True, fc2_wb=wb3)
+        x2d = autograd.diff_cross_attn_sublayer(x2d, y2d, self.norm2, lny, ca, B, Nx, Ny, rope, xpos, ypos, dt,
+                                                gamma=sublayers.gamma_of(self.ls2), drops=d2)
+        return sublayers.mlp(x2d, self.norm3, mlp.fc1, mlp.fc2, mlp.act, dt, train=train, gamma=sublayers.gamma_of(self.ls3), drops=d3)
