@@ -33,6 +33,11 @@ tiles of row segments of one image, M % 512 == 0): every `conv_rows8 ...` signat
 and `t256x256 all side0 fuse0 vec1 relu_a0 slices0 cd1 od1 am1 stride1` (65 images of 16 x 16: one image per 256-row tile; every
 smaller map or odd side moves the launch to another tile).
 Outputs ops.gemm allocates itself (tail_out, stats_out) cannot carry a guard band; C, preact_out and vt_out do.
+
+Tile order: a witness is shrunk to the fewest row tiles its route allows (MIN_ROWS: two to four), and nothing makes the shrinker keep a
+full tile group next to a ragged last one (tiles_m % group_m != 0, group_m = 4) with more than one column tile — the `last` / dGmLast
+branch of the workgroup -> tile map that each of the five direct-to-LDS kernels carries.  The hand-written "tile_order" part of the
+fixture has one row per kernel with six row tiles and two or more column tiles (`load_tile_order`), checked like the others.
 """
 import json
 import math
@@ -82,9 +87,21 @@ def load_bench():
         return json.load(f)
 
 
+DERIVED_PARTS = ("routes", "nt")
+
+
 def load_witnesses():
+    "The derived parts of the fixture (what `derive_witnesses` returns)."
     with open(WITNESS_JSON) as f:
-        return json.load(f)
+        w = json.load(f)
+    return {part: w[part] for part in DERIVED_PARTS}
+
+
+def load_tile_order():
+    """The hand-written part of the fixture: {kernel: row}, one row per direct-to-LDS kernel with SIX row tiles — with the default
+    group_m = 4 one full tile group and a ragged one of two, which the shrinker does not aim for — and two or more column tiles.  A row may carry the knobs that force its kernel (gemm_variant, conv_rows); the plan driver reads them."""
+    with open(WITNESS_JSON) as f:
+        return json.load(f)["tile_order"]
 
 
 # ------------------------------------------------------------------------------------------ signature
@@ -546,6 +563,7 @@ if __name__ == "__main__":
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         w = derive_witnesses(build_driver(tmp))
+    w["tile_order"] = load_tile_order()      # hand-written: kept as it is
     with open(WITNESS_JSON, "w") as f:
         json.dump(w, f, indent=0, sort_keys=True)
         f.write("\n")

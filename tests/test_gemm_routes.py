@@ -60,6 +60,21 @@ def test_ragged_edges(plan, stored):
     assert all(s.startswith("conv_rows8 ") or s == "t256x256 all side0 fuse0 vec1 relu_a0 slices0 cd1 od1 am1 stride1" for s in unragged), unragged
 
 
+def test_tile_order_rows_have_a_full_and_a_ragged_tile_group_on_every_kernel(plan):
+    """The hand-written part of the fixture: one row per direct-to-LDS kernel, planned onto that kernel with six row tiles (group_m = 4:
+    one full tile group and a ragged one of two) and at least two column tiles, within the reference budget."""
+    rows = R.load_tile_order()
+    assert set(rows) == {"t128x128_s3", "t256x256", "eight_wave", "four_wave", "conv_rows", "conv_rows8", "conv_rows8_flat"}
+    for kernel, row in rows.items():
+        assert row == R.normalize(row), kernel
+        p = dict(zip(R.PLAN_FIELDS, plan([row])[0].split()))
+        assert p["kernel"] == kernel, (kernel, p)
+        assert int(p["tiles_m"]) == 6 and int(p["tiles_n"]) >= 2 and int(p["slices"]) == 1, (kernel, p)
+        assert "gemm_group_m" not in row      # the default: 4 row panels per group, 6 % 4 != 0
+        assert 2 <= row["K"] // 64 <= 9, kernel
+        assert R.ref_flop(row) <= R.REF_BUDGET_FLOP, kernel
+
+
 def test_vt_positions_are_the_literal_formula():
     for ntok in (35, 64, 449):
         want = [16 * (n // 16) + (((n % 16) >> 2) & 1) * 8 + ((n % 16) & 3) + 4 * ((n % 16) >> 3) for n in range(ntok)]

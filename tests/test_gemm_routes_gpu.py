@@ -126,6 +126,29 @@ def _compare(label, row, t, outs, guards, tile):
         assert bool(torch.isnan(gd).all()), f"route [{label}]: the guard band behind {name} was written"
 
 
+TILE_ORDER = R.load_tile_order()
+
+
+@pytest.mark.parametrize("kernel", sorted(TILE_ORDER))
+def test_tile_order_with_a_ragged_last_tile_group(gpu, plan, kernel):
+    """Six row tiles with group_m = 4 — a full tile group and a ragged one of two — on every direct-to-LDS kernel, two or more column
+    tiles: every output element against fp64.  C starts as NaN: a tile never written, or written from another tile's place, fails."""
+    from uniception_amd import ops
+    row = TILE_ORDER[kernel]
+    for k in KNOBS:
+        if k in row:
+            ops.tuning_set(k, row[k])           # (reset after every test: conftest.py)
+    t = R.make_operands(row, gpu, seed=200 + sorted(TILE_ORDER).index(kernel))
+    outs, guards, captured, sat = _launch(ops, row, t, gpu)
+    assert len(captured) == 1
+    knobs = _live_knobs(ops)
+    line = plan([{**captured[0], **knobs}])[0]
+    p = dict(zip(R.PLAN_FIELDS, line.split()))
+    assert p["kernel"] == kernel and int(p["tiles_m"]) == 6 and int(p["tiles_n"]) >= 2, line
+    assert knobs.get("gemm_group_m", 4) == 4 and sat == 0
+    _compare("tile order " + kernel, row, t, outs, guards, R.TILE[kernel])
+
+
 @pytest.mark.parametrize("part,label", CASES, ids=[f"{p}-{i:02d}-{s.replace(' ', '_')}" for i, (p, s) in enumerate(CASES)])
 def test_route_against_fp64(gpu, plan, part, label):
     from uniception_amd import ops

@@ -1,4 +1,5 @@
-// Parameters and family launchers of the direct-to-LDS bf16 GEMM kernels (gemm_glds_kernel.h), shared with the uc_gemm dispatcher.
+// Parameters and family launchers of the direct-to-LDS bf16 GEMM kernels (gemm_glds_kernel.h; their epilogues: gemm_glds_epilogue.h,
+// what they share around the K-loop: gemm_glds_tile.h), shared with the uc_gemm dispatcher.
 #pragma once
 #include "common.h"
 #include "gemm_plan.h"
@@ -58,8 +59,7 @@ struct GldsParams {
     int group_m;  // row panels per L2-sharing tile group (tile traversal order)
     uc_fastdiv dNwg, dPerGroup, dGm, dGmLast;   // exact fast division by tiles_m*tiles_n, group_m*tiles_n, group_m, tiles_m % group_m
     int vec_ok;   // C / residual / bias satisfy the alignment needed by the 4-wide vector epilogue
-    // implicit-GEMM 3x3 convolution over an NHWC image (a_mode == UC_A_CONV3X3): K = 9*Cin, Cin % 64 == 0
-    int dbg;      // diagnostics only (UC_GEMM_DBG): 1 skip the in-loop DMA, 2 skip the in-loop barrier, 4 no epilogue, 8 one K-step, 16 generic epilogue only, 32 (eight-wave kernel) no wait for the DMA, 64 (conv) A tiles staged for tap 0 only, 128 / 256 (fp32 residual epilogue) no residual read / no twin write
+    int dbg;     // diagnostics only (UC_GEMM_DBG): 1 skip the in-loop DMA, 2 skip the in-loop barrier, 4 no epilogue, 8 one K-step, 16 generic epilogue only, 32 (eight-wave kernel) no wait for the DMA, 64 (conv) A tiles staged for tap 0 only, 128 / 256 (fp32 residual epilogue) no residual read / no twin write
     int stagger;  // experiment: 100-MHz ticks of start delay per phase group for the first round of workgroups (0 = off)
     int side_lds; // (eight-wave kernel, BF16 family) the tile's row statistics / column sums / bias / RoPE positions are
                   // DMA-staged into 8 KiB of LDS behind the ring at kernel start: the epilogue's first loads are LDS reads, not an exposed L2 / HBM round trip
@@ -67,6 +67,7 @@ struct GldsParams {
     unsigned long long* trace;   // diagnostics (UC_GEMM_TRACE): per-workgroup {start, loop start, loop end, end} 100-MHz ticks + HW id
     int* sat_flag; // fp16 outputs: set to 1 (atomic or) when a value beyond +-65504 was saturated; NULL: not reported
     int f16;      // operands / 16-bit outputs / 16-bit residuals are fp16 instead of bf16 (the heads' TF32-class mode): EPI_ALL family only
+    // implicit-GEMM 3x3 convolution over an NHWC image (a_mode == UC_A_CONV3X3): K = 9*Cin, Cin % 64 == 0
     int a_mode, relu_a;
     int cH, cW, cCin, cStride, cHo, cWo;
     uc_fastdiv dWo, dHo, dHWo, dCin;   // exact fast division by cWo, cHo, cHo*cWo, cCin (conv index math)
