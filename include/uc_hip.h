@@ -66,8 +66,10 @@ const char* uc_last_error(void);
  *   20: the streaming steps of the non-image input encoders — uc_unshuffle_rows (+ _bwd), uc_act, uc_ln_pe_ln,
  *       uc_ln_param_grads (+ _ws_bytes) added (nothing existing changed).
  *   21: the fused ViT stem of the Perception Encoder — uc_vit_stem, uc_vit_stem_bwd, uc_vit_stem_ws_bytes added (nothing existing
- *       changed). */
-#define UC_ABI_VERSION 21
+ *       changed).
+ *   22: uc_attention_fwd / uc_attention_bwd take head_dim 80 and 96 in bf16 and head_dim <= 96 in fp32; uc_assemble_prefix
+ *       added (nothing existing changed). */
+#define UC_ABI_VERSION 22
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -277,12 +279,13 @@ int uc_attention_fwd_x3(const float* Q, const float* K, const float* V, float* O
  *        they are interleaved with its keys, and the groups up to Npad) must hold finite values — the kernel multiplies
  *        them by probability 0.  uc_vt_pack writes zeros there; a caller that lets uc_gemm fill VT clears
  *        positions 16*(Nk/16) .. Npad of every row first.
- * UC_BF16 requires D == 64; UC_F32 supports D <= 64.
+ * UC_BF16 requires D == 64, 80 or 96; UC_F32 supports D <= 96.  At D > 64 there is no dropout (drop_p must be 0) and the backward
+ * takes no RoPE positions; any other head_dim is refused with a message naming it, before any launch.
  * ---------------------------------------------------------------------------------- */
 enum uc_v_layout { UC_V_ROWMAJOR = 0, UC_V_PACKED_T = 1 };
 
 typedef struct uc_attention_desc {
-    int dtype;           /* UC_BF16 (packed VT, head_dim 64) or UC_F32 (row-major V, head_dim <= 64) */
+    int dtype;           /* UC_BF16 (packed VT, head_dim 64, 80 or 96) or UC_F32 (row-major V, head_dim <= 96) */
     int v_layout;        /* uc_v_layout */
     int B, H, Nq, Nk, D;
     const void* Q;
@@ -419,6 +422,11 @@ int uc_assemble_tokens(const float* tok, const float* cls, const float* reg, con
                        int R, int D, uc_stream_t stream);
 int uc_token_slice(const float* src, float* dst, int B, int Ns, int Nd, int src_off, int dst_off, int n, int D,
                    uc_stream_t stream);
+/* Token assembly with a multi-row prefix (Pixio: eight class tokens, encoders/pixio.py:469-477): out[b] = [prefix | tok[b] + pos],
+ * tok fp32 [B,hw,D], prefix fp32 [P,D] (class tokens + their position rows), pos fp32 [hw,D] (the patch rows of the table),
+ * out [B,P+hw,D] in out_dtype (UC_F32 or UC_BF16: the residual stream's dtype, written once).  D % 4 == 0. */
+int uc_assemble_prefix(const float* tok, const float* prefix, const float* pos, void* out, int out_dtype, int B, int hw, int P,
+                       int D, uc_stream_t stream);
 
 /* ====================================================================================
  * Training path (backward of the same hot path; config 3 of BASELINE.json).
@@ -530,11 +538,11 @@ int uc_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, 
              float weight_decay, int step, float grad_scale, uc_stream_t stream);
 
 /* Attention backward (forward: uc_attention_fwd, which must have been called with a non-NULL lse), bf16 or fp32.
- *   bf16: Q,K,V,O,dO as [B,N,H,64] strided views, dQ [B,Nq,H,64], dK, dV [B,Nk,H,64] (own strides, e.g. slices of one fused dqkv
- *   buffer).  All operands are row-major: the transposed MFMA operands are formed inside the kernels with LDS transpose-reads.
- *   fp32 (verification mode): the same math on row-major fp32 operands, head_dim D <= 64, no packed transposes needed; no RoPE. */
+ *   bf16: Q,K,V,O,dO as [B,N,H,D] strided views, dQ [B,Nq,H,D], dK, dV [B,Nk,H,D] (own strides, e.g. slices of one fused dqkv
+ *   buffer), D = 64, or 80 / 96 (no RoPE positions, no dropout there).  All operands are row-major: the transposed MFMA operands are formed inside the kernels with LDS transpose-reads.
+ *   fp32 (verification mode): the same math on row-major fp32 operands, head_dim D <= 96, no packed transposes needed; no RoPE. */
 typedef struct uc_attention_bwd_desc {
-    int dtype;           /* UC_BF16 (D == 64) or UC_F32 (D <= 64) */
+    int dtype;           /* UC_BF16 (D == 64, 80 or 96) or UC_F32 (D <= 96) */
     int B, H, Nq, Nk, D;
     const void* Q;
     const void* K;

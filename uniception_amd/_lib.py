@@ -129,6 +129,7 @@ SIGNATURES = {
     "uc_adaptor_program": [vp, i64, i64, i64, vp, i32, i32, i32, i32, vp, i32, vp],
     "uc_assemble_tokens": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "uc_token_slice": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "uc_assemble_prefix": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "uc_layernorm_bwd": [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i64, i32, f32, vp],
     "uc_gemm_tn": [C.POINTER(GemmTnDesc), vp],
     "uc_gemm_tn_query": [C.POINTER(GemmTnDesc), C.POINTER(i32), C.POINTER(i32)],
@@ -182,7 +183,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 21   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 22   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

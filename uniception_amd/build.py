@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libuc_hip.so")
 SOURCES = ["error.hip", "rope_norm.hip", "gemm.hip", "gemm_glds_dense_bf16.hip", "gemm_glds_dense_f32.hip", "gemm_glds_dense_bs.hip", "gemm_glds_dense_all.hip", "gemm_glds_conv.hip", "gemm_glds_conv_f16.hip", "gemm_glds_dense_all_f16.hip", "gemm_tn.hip", "attention.hip", "attention_x3.hip", "attention_fp8.hip",
-           "attention_bwd.hip", "attention_diff.hip", "elementwise.hip", "train.hip", "dpt_bwd.hip", "pool.hip", "groupnorm.hip", "pad_resize.hip", "input_encoders.hip", "vit_stem.hip"]
+           "attention_bwd.hip", "attention_wide.hip", "attention_diff.hip", "elementwise.hip", "train.hip", "dpt_bwd.hip", "pool.hip", "groupnorm.hip", "pad_resize.hip", "input_encoders.hip", "vit_stem.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-inline-asm"]
 
 
@@ -148,9 +148,16 @@ def check_glds4_agprs(fp=None, verbose=True):
         if r["scratch"] != 0 or r["vgpr_spills"] != 0:
             raise RuntimeError(f"[uniception_amd.build] {name}: {r}: the 64-row attention backward kernels must compile without scratch or spills "
                                "(a spill of an asm MFMA's result is read before it is written) — set UC_ATTN_BWD64=0 at run time and report")
+    wide = chk.check_p64("attention_wide.hip", "attnw_(fwd|bwd_dq|bwd_dkv)_kernel")
+    if len(wide) < 6:
+        raise RuntimeError(f"[uniception_amd.build] found {len(wide)} wide-head attention kernels in attention_wide.hip (expected 6)")
+    for name, r in wide.items():
+        if r["scratch"] != 0 or r["vgpr_spills"] != 0:
+            raise RuntimeError(f"[uniception_amd.build] {name}: {r}: the head_dim 80 / 96 attention kernels must compile without scratch or spills")
     if verbose:
         print(f"[uniception_amd.build] generated-code proofs: {n} gemm_bf16_glds4_kernel instantiations clean, {len(p64)} attn_bf16_p64_kernel "
-              f"instantiations without scratch / spills / AGPRs, {len(b64)} 64-row attention backward kernels without scratch / spills", flush=True)
+              f"instantiations without scratch / spills / AGPRs, {len(b64)} 64-row attention backward kernels without scratch / spills, "
+              f"{len(wide)} wide-head attention kernels without scratch / spills", flush=True)
     if not skip4:
         with open(mark, "w") as f:
             f.write(fp)

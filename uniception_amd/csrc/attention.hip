@@ -10,6 +10,7 @@
 #include "knobs.h"
 #include "attention_p64.h"
 #include "attention_plan.h"
+#include "attention_wide.h"
 #include <stdlib.h>
 
 struct AttnParams {
@@ -682,6 +683,20 @@ static void launch_attn_dma4_dbg(int dbg, dim3 grid, hipStream_t st, const AttnP
 }
 #endif
 
+// the fp32 verification kernel at DMAX 96 for uc_attention_fwd_wide (64 < head_dim <= 96, no dropout)
+int uc_attention_f32_96_launch(const uc_attention_desc& d, const AttnWideFwdPlan& plan, uc_stream_t stream) {
+    AttnParams p = {};
+    p.Q = d.Q; p.K = d.K; p.V = d.V; p.O = d.O; p.B = d.B; p.H = d.H; p.Nq = d.Nq; p.Nk = d.Nk; p.D = d.D;
+    p.q_sb = d.q_sb; p.q_sn = d.q_sn; p.q_sh = d.q_sh; p.k_sb = d.k_sb; p.k_sn = d.k_sn; p.k_sh = d.k_sh;
+    p.v_sb = d.v_sb; p.v_sn = d.v_sn; p.v_sh = d.v_sh; p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh;
+    p.scale = d.scale;
+    p.lse = d.lse;
+    p.drop = uc_make_dropout(0.f, 0ull);
+    hipLaunchKernelGGL((attn_f32_kernel<96>), dim3(plan.grid[0], plan.grid[1], plan.grid[2]), dim3(plan.block), 0, (hipStream_t)stream, p);
+    UC_CHECK_LAUNCH("uc_attention_fwd");
+    return UC_OK;
+}
+
 // uc_attention_fwd: validate, fill AttnParams, snapshot the knobs, plan the launch (attention_plan.h) and carry the plan out
 extern "C" int uc_attention_fwd(const uc_attention_desc* desc, uc_stream_t stream) {
     UC_REQUIRE(desc, "uc_attention_fwd: null descriptor");
@@ -695,8 +710,9 @@ extern "C" int uc_attention_fwd(const uc_attention_desc* desc, uc_stream_t strea
     UC_REQUIRE(Q && K && V && O, "%s: null pointer", fn);
     UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0, "%s: bad shape", fn);
     UC_REQUIRE(H <= 65535 && B <= 65535, "%s: B and H must fit a grid dimension", fn);
+    if (D > 64) return uc_attention_fwd_wide(d, stream);   // head_dim 80 / 96 (bf16), <= 96 (fp32): attention_wide_plan.h
     if (dtype == UC_BF16) {
-        UC_REQUIRE(D == 64, "%s(bf16): head_dim must be 64 (got %d)", fn, D);
+        UC_REQUIRE(D == 64, "%s(bf16): head_dim must be 64 (got %d); 80 and 96 run the wide-head kernels", fn, D);
         UC_REQUIRE(d.v_layout == UC_V_PACKED_T, "%s(bf16): V must be in the packed VT layout (uc_vt_pack)", fn);
         UC_REQUIRE(d.q_sb % 8 == 0 && d.q_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sb % 8 == 0 && d.k_sn % 8 == 0 && d.k_sh % 8 == 0,
                    "%s(bf16): Q/K strides must be multiples of 8 elements", fn);

@@ -20,6 +20,7 @@
 #include "mma_tile.h"
 #include "knobs.h"
 #include "attention_plan.h"
+#include "attention_wide.h"
 #include <math.h>
 
 struct AttnBwdParams {
@@ -419,7 +420,7 @@ static int attention_bwd_impl(const uc_attention_bwd_desc& d, uc_stream_t stream
     UC_REQUIRE((d.rope_qpos == nullptr) == (d.rope_kpos == nullptr), "uc_attention_bwd: rope_qpos and rope_kpos go together");
     UC_REQUIRE(!d.rope_qpos || (d.rope_base > 0.f && d.rope_f0 != 0.f), "uc_attention_bwd: the inverse RoPE needs base > 0 and F0 != 0");
     UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && B <= 65535 && H <= 65535, "uc_attention_bwd: bad shape");
-    UC_REQUIRE(d.D == 64, "uc_attention_bwd(bf16): head_dim must be 64 (got %d)", d.D);
+    UC_REQUIRE(d.D == 64, "uc_attention_bwd(bf16): head_dim must be 64 (got %d); 80 and 96 run the wide-head kernels", d.D);
     UC_REQUIRE(d.q_sn % 8 == 0 && d.k_sn % 8 == 0 && d.v_sn % 8 == 0 && d.o_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sh % 8 == 0 &&
                    d.v_sh % 8 == 0 && d.o_sh % 8 == 0 && d.q_sb % 8 == 0 && d.k_sb % 8 == 0 && d.v_sb % 8 == 0 && d.o_sb % 8 == 0,
                "uc_attention_bwd: input strides must be multiples of 8 elements");
@@ -622,19 +623,36 @@ __global__ __launch_bounds__(128) void attn_bwd_dkv_f32_kernel(AttnBwdF32Params 
     }
 }
 
+static AttnBwdF32Params attention_bwd_f32_params(const uc_attention_bwd_desc& d) {
+    AttnBwdF32Params p;
+    p.Q = (const float*)d.Q; p.K = (const float*)d.K; p.V = (const float*)d.V; p.O = (const float*)d.O; p.dO = (const float*)d.dO;
+    p.LSE = d.LSE; p.dQ = (float*)d.dQ; p.dK = (float*)d.dK; p.dV = (float*)d.dV; p.delta = d.delta;
+    p.B = d.B; p.H = d.H; p.Nq = d.Nq; p.Nk = d.Nk; p.D = d.D;
+    p.q_sb = d.q_sb; p.q_sn = d.q_sn; p.q_sh = d.q_sh; p.k_sb = d.k_sb; p.k_sn = d.k_sn; p.k_sh = d.k_sh; p.v_sb = d.v_sb; p.v_sn = d.v_sn;
+    p.v_sh = d.v_sh; p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh; p.dq_sb = d.dq_sb; p.dq_sn = d.dq_sn; p.dq_sh = d.dq_sh;
+    p.dk_sb = d.dk_sb; p.dk_sn = d.dk_sn; p.dk_sh = d.dk_sh; p.dv_sb = d.dv_sb; p.dv_sn = d.dv_sn; p.dv_sh = d.dv_sh; p.scale = d.scale;
+    p.drop = uc_make_dropout(d.drop_p, d.drop_p != 0.f ? d.seed : 0ull);
+    return p;
+}
+
+// the fp32 verification kernels at DMAX 96 for uc_attention_bwd_wide (64 < head_dim <= 96, no dropout, no RoPE)
+int uc_attention_bwd_f32_96_launch(const uc_attention_bwd_desc& d, const AttnWideBwdPlan& plan, uc_stream_t stream) {
+    const AttnBwdF32Params p = attention_bwd_f32_params(d);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 gq(plan.dq_grid[0], plan.dq_grid[1], plan.dq_grid[2]), gkv(plan.dkv_grid[0], plan.dkv_grid[1], plan.dkv_grid[2]);
+    hipLaunchKernelGGL(attn_delta_f32_kernel, dim3(plan.delta_grid), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<96>), gq, dim3(plan.block), 0, st, p);
+    hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<96>), gkv, dim3(plan.block), 0, st, p);
+    UC_CHECK_LAUNCH("uc_attention_bwd");
+    return UC_OK;
+}
+
 // the fp32 backward of uc_attention_bwd
 static int attention_bwd_f32_impl(const uc_attention_bwd_desc& d, uc_stream_t stream) {
     const int B = d.B, H = d.H, Nq = d.Nq, Nk = d.Nk, D = d.D;
     UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0 && D <= 64 && B <= 65535 && H <= 65535, "uc_attention_bwd(f32): bad shape (head_dim <= 64)");
     UC_REQUIRE(!d.rope_qpos && !d.rope_kpos, "uc_attention_bwd(f32): the fp32 backward takes no RoPE positions");
-    AttnBwdF32Params p;
-    p.Q = (const float*)d.Q; p.K = (const float*)d.K; p.V = (const float*)d.V; p.O = (const float*)d.O; p.dO = (const float*)d.dO;
-    p.LSE = d.LSE; p.dQ = (float*)d.dQ; p.dK = (float*)d.dK; p.dV = (float*)d.dV; p.delta = d.delta;
-    p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.D = D;
-    p.q_sb = d.q_sb; p.q_sn = d.q_sn; p.q_sh = d.q_sh; p.k_sb = d.k_sb; p.k_sn = d.k_sn; p.k_sh = d.k_sh; p.v_sb = d.v_sb; p.v_sn = d.v_sn;
-    p.v_sh = d.v_sh; p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh; p.dq_sb = d.dq_sb; p.dq_sn = d.dq_sn; p.dq_sh = d.dq_sh;
-    p.dk_sb = d.dk_sb; p.dk_sn = d.dk_sn; p.dk_sh = d.dk_sh; p.dv_sb = d.dv_sb; p.dv_sn = d.dv_sn; p.dv_sh = d.dv_sh; p.scale = d.scale;
-    p.drop = uc_make_dropout(d.drop_p, d.drop_p != 0.f ? d.seed : 0ull);
+    const AttnBwdF32Params p = attention_bwd_f32_params(d);
     const AttnBwdPlan plan = uc_attention_bwd_plan(d, AttnKnobs{});   // (the fp32 routing reads no knob)
     hipStream_t st = (hipStream_t)stream;
     const dim3 gq(plan.dq_grid[0], plan.dq_grid[1], plan.dq_grid[2]), gkv(plan.dkv_grid[0], plan.dkv_grid[1], plan.dkv_grid[2]);
@@ -661,6 +679,7 @@ extern "C" int uc_attention_bwd(const uc_attention_bwd_desc* desc, uc_stream_t s
     const uc_attention_bwd_desc& d = *desc;
     UC_REQUIRE(d.drop_p >= 0.f && d.drop_p < 1.f, "uc_attention_bwd: drop_p must be in [0, 1) (got %g)", (double)d.drop_p);
     UC_REQUIRE(d.Q && d.K && d.V && d.O && d.dO && d.LSE && d.dQ && d.dK && d.dV && d.delta, "uc_attention_bwd: null pointer");
+    if (d.D > 64) return uc_attention_bwd_wide(d, stream);   // head_dim 80 / 96 (bf16), <= 96 (fp32): attention_wide_plan.h
     if (d.dtype == UC_BF16) return attention_bwd_impl(d, stream);
     if (d.dtype == UC_F32) return attention_bwd_f32_impl(d, stream);
     uc_set_error("uc_attention_bwd: unsupported dtype %d", d.dtype);

@@ -588,6 +588,40 @@ extern "C" int uc_assemble_tokens(const float* tok, const float* cls, const floa
     return UC_OK;
 }
 
+// ... with a multi-row prefix and the stream's dtype (Pixio: eight class rows, width up to 3072): out[b] = [prefix rows | tok + pos].
+// prefix [P, D] and pos [hw, D] are fp32 (the class tokens with their position rows already added, the — possibly resized — patch rows
+// of the table); the output is written once, in fp32 or bf16.
+template <typename Tag>
+__global__ void assemble_prefix_kernel(const float* __restrict__ tok, const float* __restrict__ prefix, const float* __restrict__ pos,
+                                       typename Tag::storage* __restrict__ out, int hw, int P, int D4, int64_t items) {
+    const int Nt = P + hw;
+    for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (int64_t)gridDim.x * blockDim.x) {
+        const int d4 = (int)(it % D4);
+        const int n = (int)((it / D4) % Nt);
+        const int b = (int)(it / ((int64_t)D4 * Nt));
+        float4_t v;
+        if (n < P) {
+            v = vec_load4<F32Tag>(prefix + ((int64_t)n * D4 + d4) * 4);
+        } else {
+            const int i = n - P;
+            v = vec_load4<F32Tag>(tok + (((int64_t)b * hw + i) * D4 + d4) * 4) + vec_load4<F32Tag>(pos + ((int64_t)i * D4 + d4) * 4);
+        }
+        vec_store4<Tag>(out + it * 4, v);
+    }
+}
+
+extern "C" int uc_assemble_prefix(const float* tok, const float* prefix, const float* pos, void* out, int out_dtype, int B, int hw, int P,
+                                  int D, uc_stream_t stream) {
+    UC_REQUIRE(tok && prefix && pos && out, "uc_assemble_prefix: null pointer");
+    UC_REQUIRE(B > 0 && hw > 0 && P > 0 && D > 0 && D % 4 == 0, "uc_assemble_prefix: bad shape (D must be a multiple of 4)");
+    const int64_t items = (int64_t)B * (P + hw) * (D / 4);
+    UC_DISPATCH("uc_assemble_prefix", out_dtype,
+                hipLaunchKernelGGL(assemble_prefix_kernel<Tag>, dim3(EW_GRID(items)), dim3(256), 0, (hipStream_t)stream, tok, prefix, pos,
+                                   (typename Tag::storage*)out, hw, P, D / 4, items));
+    UC_CHECK_LAUNCH("uc_assemble_prefix");
+    return UC_OK;
+}
+
 __global__ void token_slice_kernel(const float* __restrict__ src, float* __restrict__ dst, int Ns, int Nd, int src_off, int dst_off,
                                    int n, int D4, int64_t items) {
     for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (int64_t)gridDim.x * blockDim.x) {

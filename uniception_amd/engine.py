@@ -640,7 +640,8 @@ def _pos2d(pos: torch.Tensor) -> torch.Tensor:
 VT_PACK_ODD: bool = os.environ.get("UNICEPTION_AMD_VT_PACK_ODD", "1") != "0"
 
 
-def attention_route(dtype: torch.dtype, head_dim: int, native_rope: bool, qk_norm: bool, separate_v: bool, n_keys: int) -> str:
+def attention_route(dtype: torch.dtype, head_dim: int, native_rope: bool, qk_norm: bool, separate_v: bool, n_keys: int,
+                    has_rope: bool = False) -> str:
     """Which pipeline an inference attention sub-layer runs (self_attention, cross_attention); plain values in, the route's name out.
     native_rope: no positional encoding, or the native RoPE-2D (is_native_rope) — not a foreign callable.  qk_norm: the layer
     normalises q / k over head_dim.  separate_v: the value tokens are not the key tokens.  n_keys: key tokens per sample.
@@ -651,7 +652,16 @@ def attention_route(dtype: torch.dtype, head_dim: int, native_rope: bool, qk_nor
       "vt_epilogue"  the default: the GEMM applies RoPE to q | k and writes V in the packed VT layout itself;
       "unfused"      everything the fused GEMM epilogues do not carry (fp32 and bf16x3 operands, a foreign rope callable, qk_norm —
                      it runs BEFORE the positional encoding —, separate value tokens): plain GEMMs, then _unfused_attention.
-    The three fused routes need bf16 operands and head_dim 64; bf16 with another head_dim has no kernel and raises."""
+      "wide"         bf16 at head_dim 80 / 96 (csrc/attention_wide.hip), with or without attention_precision("fp8") — fp8 has no wide
+                     kernel: plain QKV GEMM(s) with bias, uc_vt_pack of V, uc_attention_fwd.  has_rope: the layer has a positional
+                     encoding at all (native or not); the wide kernels have neither a RoPE nor a qk_norm form, and both raise.
+    The three fused routes need bf16 operands and head_dim 64; bf16 with a head_dim outside 64 / 80 / 96 has no kernel and raises."""
+    if dtype == torch.bfloat16 and head_dim in ops.WIDE_HEAD_DIMS:
+        if qk_norm:
+            raise UcHipError(f"qk_norm has no HIP path at head_dim {head_dim} in bf16 (head_dim 64 only); use fp32 precision for this model")
+        if has_rope or not native_rope:
+            raise UcHipError(f"RoPE has no HIP path at head_dim {head_dim} (the rotation kernels are head_dim 64); this model cannot run")
+        return "wide"
     if dtype == torch.bfloat16 and head_dim == 64 and native_rope and not qk_norm and not separate_v:
         if _fp8_attention():
             return "fp8"
@@ -737,8 +747,8 @@ def self_attention(h2d: torch.Tensor, B: int, N: int, qkv: nn.Linear, proj: nn.L
     Cd = qkv.out_features // 3          # width of q / k / v: the model width, or `latent_attn_dim` (utils/transformer_blocks.py:178-199)
     Dh = Cd // num_heads
     wq, bq, lnq = _folded(qkv, fold, dtype)
-    route = attention_route(dtype, Dh, rope is None or is_native_rope(rope), _has_norm(q_norm, k_norm), False, N)
-    if route == "unfused":
+    route = attention_route(dtype, Dh, rope is None or is_native_rope(rope), _has_norm(q_norm, k_norm), False, N, has_rope=rope is not None)
+    if route in ("unfused", "wide"):      # ("wide": bf16 q, k, v of the plain GEMM -> uc_vt_pack -> the wide-head kernel, in _attention_generic)
         t = ops.gemm(h2d, wq, bq, ln=lnq).view(B, N, 3, num_heads, Dh)
         o = _unfused_attention(t[:, :, 0], t[:, :, 1], t[:, :, 2], q_norm, k_norm, rope, pos, pos, scale)
     elif route == "vt_epilogue":
@@ -811,9 +821,10 @@ def cross_attention(hq2d: torch.Tensor, hkv2d: torch.Tensor, B: int, Nq: int, Nk
     dtype = hq2d.dtype
     Cd = hq2d.shape[1]
     Dh = Cd // num_heads
-    route = attention_route(dtype, Dh, rope is None or is_native_rope(rope), _has_norm(q_norm, k_norm), hv2d is not None, Nk)
+    route = attention_route(dtype, Dh, rope is None or is_native_rope(rope), _has_norm(q_norm, k_norm), hv2d is not None, Nk,
+                            has_rope=rope is not None)
     wq, bq, lnq = _folded(projq, fold_q, dtype)
-    if route == "unfused" and (hv2d is not None or _has_norm(q_norm, k_norm)):
+    if route in ("unfused", "wide") and (hv2d is not None or _has_norm(q_norm, k_norm)):
         # options the fused [Wk; Wv] GEMM does not carry: q, k, v from three GEMMs (the query / key LayerNorm folds still apply)
         if hv2d is not None and fold_kv is not None:
             raise UcHipError("a folded key LayerNorm cannot serve separate value tokens")
@@ -834,7 +845,7 @@ def cross_attention(hq2d: torch.Tensor, hkv2d: torch.Tensor, B: int, Nq: int, Nk
     else:
         wkv, bkv, cskv = ln_kv_weights(projk, projv, fold_kv[1], dtype)
         lnkv = (fold_kv[0], cskv)
-    if route == "unfused":
+    if route in ("unfused", "wide"):
         q = ops.gemm(hq2d, wq, bq, ln=lnq).view(B, Nq, num_heads, Dh)
         kv = ops.gemm(hkv2d, wkv, bkv, ln=lnkv).view(B, Nk, 2, num_heads, Dh)
         o = _unfused_attention(q, kv[:, :, 0], kv[:, :, 1], None, None, rope, qpos, kpos, scale)

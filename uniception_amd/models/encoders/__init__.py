@@ -8,6 +8,7 @@ from .global_rep_encoder import GlobalRepresentationEncoder
 from .image_normalizations import IMAGE_NORMALIZATION_DICT  # noqa: F401
 from .patch_embedder import PatchEmbedder
 from .perception_encoder import PerceptionEncoder, PerceptionEncoderIntermediateFeatureReturner
+from .pixio import PixioEncoder
 
 ENCODER_CONFIGS = {
     "croco": {"class": CroCoEncoder, "intermediate_feature_returner_class": CroCoIntermediateFeatureReturner,
@@ -19,6 +20,7 @@ ENCODER_CONFIGS = {
     "patch_embedder": {"class": PatchEmbedder, "supported_models": ["Patch-Embedder"]},
     "perception_encoder": {"class": PerceptionEncoder, "intermediate_feature_returner_class": PerceptionEncoderIntermediateFeatureReturner,
                            "supported_models": ["Perception Encoder Core", "Preception Encoder Spatial"]},
+    "pixio": {"class": PixioEncoder, "supported_models": ["Pixio-Encoder"]},
 }
 
 

@@ -19,5 +19,6 @@ _TABLE = {
     "dinov2": _IMAGENET,
     "patch_embedder": _IMAGENET,
     "perception_encoder": ([0.5] * 3, [0.5] * 3),
+    "pixio": _IMAGENET,
 }
 IMAGE_NORMALIZATION_DICT = {k: ImageNormalization(mean=torch.tensor(m), std=torch.tensor(s)) for k, (m, s) in _TABLE.items()}

@@ -589,6 +589,10 @@ def attention_fp8(q: torch.Tensor, k: torch.Tensor, vt8: torch.Tensor, scale: fl
     return out
 
 
+# head dims beyond 64 that the bf16 attention kernels serve (csrc/attention_wide.hip); fp32 runs every head_dim up to the last one
+WIDE_HEAD_DIMS = (80, 96)
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, v_packed: bool = False,
               out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None, dropout=None) -> torch.Tensor:
     """q [B,Nq,H,D], k [B,Nk,H,D] strided views (stride(3)==1); v same, or packed VT [B,H,D,Npad] when v_packed.
@@ -802,6 +806,19 @@ def assemble_tokens(tok: torch.Tensor, cls: torch.Tensor, reg: Optional[torch.Te
     out = torch.empty((B, 1 + R + hw, D), dtype=torch.float32, device=tok.device)
     _lib.check(_lib.load().uc_assemble_tokens(tok.data_ptr(), cls.data_ptr(), _p(reg), pos.data_ptr(), out.data_ptr(), B, hw, R, D,
                                               _stream()), "uc_assemble_tokens")
+    return out
+
+
+def assemble_prefix(tok: torch.Tensor, prefix: torch.Tensor, pos: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+    """tok fp32 [B,hw,D], prefix fp32 [P,D], pos fp32 [hw,D] -> [B, P+hw, D] = [prefix | tok+pos] in out_dtype (fp32 / bf16), one pass."""
+    _need_gpu(tok, prefix, pos)
+    B, hw, D = tok.shape
+    for t in (tok, prefix, pos):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert prefix.dim() == 2 and prefix.shape[1] == D and pos.shape == (hw, D)
+    out = torch.empty((B, prefix.shape[0] + hw, D), dtype=out_dtype, device=tok.device)
+    _lib.check(_lib.load().uc_assemble_prefix(tok.data_ptr(), prefix.data_ptr(), pos.data_ptr(), out.data_ptr(), _dt(out_dtype), B, hw,
+                                              prefix.shape[0], D, _stream()), "uc_assemble_prefix")
     return out
 
 
@@ -1055,7 +1072,7 @@ def attention_drop_mask(B: int, H: int, Nq: int, Nk: int, p: float, seed: int, d
 
 
 def attention_bwd(q, k, v, o, do, lse, scale: float, out=None, rope=None, dropout=None):
-    """q,o,do [B,Nq,H,64]; k,v [B,Nk,H,64] bf16 views (unit last stride); lse fp32 [B,H,Nq].
+    """q,o,do [B,Nq,H,D]; k,v [B,Nk,H,D] (bf16: D = 64, or 80 / 96 on the wide-head kernels; fp32: D <= 96) views (unit last stride); lse fp32 [B,H,Nq].
     dropout = the forward's (p, seed) when it dropped attention probabilities (the kernels re-evaluate the mask).
     Returns dq, dk, dv ([B,N,H,64] bf16): fresh contiguous tensors, or the three views passed as `out`
     (e.g. slices of one fused dqkv buffer).
@@ -1065,8 +1082,10 @@ def attention_bwd(q, k, v, o, do, lse, scale: float, out=None, rope=None, dropou
     B, Nq, H, D = q.shape
     Nk = k.shape[1]
     dt = q.dtype
-    if not ((dt == torch.bfloat16 and D == 64) or (dt == torch.float32 and D <= 64)):
-        raise UcHipError("attention backward needs bf16 with head_dim 64, or fp32 with head_dim <= 64")
+    if not ((dt == torch.bfloat16 and D in (64,) + WIDE_HEAD_DIMS) or (dt == torch.float32 and D <= WIDE_HEAD_DIMS[-1])):
+        raise UcHipError(f"attention backward needs bf16 with head_dim 64, 80 or 96, or fp32 with head_dim <= 96 (got {D})")
+    if D > 64 and (rope is not None or (dropout is not None and float(dropout[0]) > 0.0)):
+        raise UcHipError(f"attention backward at head_dim {D}: the inverse RoPE and attention dropout exist at head_dim <= 64 only")
     assert lse.dtype == torch.float32 and lse.is_contiguous()
     if do.stride() != o.stride() or o.stride(3) != 1:
         o, do = o.contiguous(), do.contiguous()
