@@ -97,6 +97,12 @@ DROP_P, DROP_SEED = 0.25, 0x1234_5678_9ABC_DEF1
 FWD_KERNELS = ("reg128", "dma4", "dma8", "rs8", "p64", "p64_tail", "reg128_drop", "f32_32", "f32_64", "f32_32_drop", "f32_64_drop", "dma4_dbg")
 DQ_KERNELS = ("dq32", "dq64", "dq32_drop", "f32_dq32", "f32_dq64")
 DKV_KERNELS = ("dkv32", "dkv64", "dkv32_drop", "f32_dkv32", "f32_dkv64")
+# the head_dim > 64 kernels the same plan and driver name (they follow the ones above in the enums of attention_plan.h): witnessed in
+# tests/attention_wide_routes.py, whose bound differs from this file's
+WIDE_FWD_KERNELS = ("bf16_80", "bf16_96", "f32_96")
+WIDE_DQ_KERNELS = ("dq80", "dq96", "f32_dq96")
+WIDE_DKV_KERNELS = ("dkv80", "dkv96", "f32_dkv96")
+REFUSALS = ("dtype", "bf16_head_dim", "f32_head_dim", "dropout", "rope_f32", "rope_head_dim", "bwd_grid")      # `refused <reason>`
 REQUANT_FWD = ("p64", "p64_tail")      # forward kernels that re-round scale log2(e) Q to bf16
 KNOBS = {"p64": "attn_p64", "bwd64": "attn_bwd64", "role_split": "attn_role_split"}      # driver name -> tuning knob
 
@@ -208,6 +214,8 @@ def driver_row(w, cus=256):
         row.update(v_layout=1 if w["dtype"] == BF16 else 0, O=4096)
     if w["drop"]:
         row["drop"] = 1
+    if w["rope"] and w["fn"] == "bwd":
+        row["rope"] = 1
     row.update(w["knobs"])
     row["cus"] = cus
     return row
@@ -230,6 +238,8 @@ def spy(fn_name, ctypes_fields):
                 rec[name] = int(getattr(d, name) or 0)
         if float(d.drop_p) != 0.0:
             rec["drop"] = 1
+        if getattr(d, "rope_qpos", None) or getattr(d, "rope_kpos", None):      # (the backward descriptor only)
+            rec["rope"] = 1
         captured.append(rec)
         return real(desc_ref, stream)
 

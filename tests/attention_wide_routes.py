@@ -1,6 +1,6 @@
 """Route audit of uc_attention_fwd / uc_attention_bwd at head_dim > 64 (uniception_amd/csrc/attention_wide.hip and the fp32 verification
-kernels at DMAX 96), by the method of tests/attention_routes.py: one witness per kernel the wide plan
-(uniception_amd/csrc/attention_wide_plan.h) can choose, the fp64 reference of every output and the per-element bound.
+kernels at DMAX 96), by the method of tests/attention_routes.py and with its plan driver and kernel names: one witness per kernel the plan
+(uniception_amd/csrc/attention_plan.h) can choose at head_dim > 64, the fp64 reference of every output and the per-element bound.
 tests/test_attention_wide_plan.py pins the plans and runs the bound's self-check on the CPU; tests/test_attention_wide_gpu.py launches
 every witness, proves the kernel it took and compares every element.
 
@@ -28,18 +28,11 @@ every bf16 witness, and each seeded fault (FAULTS) leaves it (tests/test_attenti
 MEASURED on an MI355X (pytest -m gpu -s tests/test_attention_wide_gpu.py prints one line per witness: worst err / bound per output):
 see DESIGN.md section 14.
 """
-import os
-import shutil
-import subprocess
-
 import torch
 
 from tests.attention_routes import (BF16, F32, FWD_FIELDS, BWD_FIELDS, LOG2E, ROOT, U_OUT, CHUNK_ELEMS, _bh, _un_bh, _rb, _w, c_sum,   # noqa: F401
-                                    check, driver_row, make_operands, place, ratio, route_of, shape_for, spike_position, spy)
-
-FWD_KERNELS = ("bf16_80", "bf16_96", "f32_96")
-DQ_KERNELS = ("dq80", "dq96", "f32_dq96")
-DKV_KERNELS = ("dkv80", "dkv96", "f32_dkv96")
+                                    build_driver, check, driver_row, make_operands, place, ratio, route_of, shape_for, spike_position, spy)
+from tests.attention_routes import WIDE_FWD_KERNELS as FWD_KERNELS, WIDE_DQ_KERNELS as DQ_KERNELS, WIDE_DKV_KERNELS as DKV_KERNELS   # noqa: F401
 
 WITNESSES = {}
 for _D in (80, 96):
@@ -56,22 +49,6 @@ SEEDS = {n: i for i, n in enumerate(sorted(WITNESSES))}
 # the model shapes whose plans tests/test_attention_wide_plan.py pins next to the witnesses': (B, H, N, D), self-attention, fused qkv
 MODEL_SHAPES = {"pixio_h16_256": (32, 16, 264, 80), "pixio_h16_512": (32, 16, 1032, 80),
                 "pixio_5b16_256": (32, 32, 264, 96), "pixio_5b16_512": (32, 32, 1032, 96)}
-
-
-def build_driver(tmpdir):
-    "Compile tests/attention_wide_plan_driver.cpp with the system C++ compiler into tmpdir; returns run(rows) -> plan lines."
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
-    assert cxx, "a C++ compiler is needed to build tests/attention_wide_plan_driver.cpp"
-    exe = os.path.join(str(tmpdir), "attention_wide_plan_driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "uniception_amd", "csrc"), os.path.join(ROOT, "tests", "attention_wide_plan_driver.cpp"), "-o", exe])
-
-    def run(rows):
-        lines = [" ".join(f"{k}={v}" for k, v in row.items()) for row in rows]
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
-        assert len(out) == len(rows)
-        return out
-    return run
 
 
 def model_rows(name):

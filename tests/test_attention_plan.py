@@ -1,16 +1,18 @@
-"""CPU: the attention routing (uniception_amd/csrc/attention_plan.h) — which kernel, grid and workgroup size a forward or backward
-launch gets.
+"""CPU: the attention routing (uniception_amd/csrc/attention_plan.h) — whether a forward or backward launch is served and which
+kernel, grid and workgroup size it gets.
 
-tests/attention_plan_driver.cpp is compiled with the system C++ compiler against the host-only header and fed one descriptor + knob
-snapshot per line.  Expected plans: forward `kernel grid_x grid_y grid_z block nqt fixup_grid`, backward `dq dq_grid dkv dkv_grid`,
-as the routing had them when it was written inline in uc_attention_fwd, attention_bwd_impl and attention_bwd_f32_impl; the bench rows
-agree with the kernel traces of the bench configurations.  O is an integer address: 4096 is 256-byte aligned, 4104 8-byte aligned."""
+tests/attention_plan_driver.cpp is compiled with the system C++ compiler against the host-only header (tests/attention_routes.py
+build_driver) and fed one descriptor + knob snapshot per line.  Expected plans: `refused <reason>`, or forward
+`kernel grid_x grid_y grid_z block nqt fixup_grid`, backward `dq dq_grid dkv dkv_grid`, as the routing had them when it was written
+inline in uc_attention_fwd, attention_bwd_impl and attention_bwd_f32_impl (head_dim <= 64) and in the head_dim > 64 entry functions;
+the bench rows agree with the kernel traces of the bench configurations.  O is an integer address: 4096 is 256-byte aligned, 4104
+8-byte aligned."""
 import json
 import os
-import shutil
-import subprocess
 
 import pytest
+
+from tests import attention_routes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # every distinct bf16 attention launch of the bench configurations, recorded from their ABI calls: {config: [[row, expected plan], ...]}
@@ -90,6 +92,23 @@ FWD_RULES = {
  "f32_d33": (fwd(2, 4, 300, dtype=F32, D=33), "f32_64 3 4 2 128 0 0"),
  "f32_d32_drop": (fwd(2, 4, 300, dtype=F32, D=32, drop=1), "f32_32_drop 3 4 2 128 0 0"),
  "f32_d64_drop": (fwd(2, 4, 300, dtype=F32, drop=1), "f32_64_drop 3 4 2 128 0 0"),
+ # the served set.  fp32: every head_dim up to 96, the DMAX 96 instantiation above 64
+ "f32_d64": (fwd(2, 4, 300, dtype=F32, D=64), "f32_64 3 4 2 128 0 0"),
+ "f32_d65": (fwd(2, 4, 300, dtype=F32, D=65), "f32_96 3 4 2 128 0 0"),
+ "f32_d96": (fwd(2, 4, 300, dtype=F32, D=96), "f32_96 3 4 2 128 0 0"),
+ "f32_d97": (fwd(2, 4, 300, dtype=F32, D=97), "refused f32_head_dim"),
+ # bf16: head_dim 64, 80 or 96; 80 / 96 take one workgroup per 128 queries of a (batch, head)
+ "bf16_d64": (fwd(2, 4, 300), "dma4 24 1 1 256 3 0"),
+ "bf16_d72": (fwd(2, 4, 300, D=72), "refused bf16_head_dim"),
+ "bf16_d80": (fwd(2, 4, 300, D=80), "bf16_80 3 4 2 256 0 0"),
+ "bf16_d96": (fwd(2, 4, 300, D=96), "bf16_96 3 4 2 256 0 0"),
+ "bf16_d112": (fwd(2, 4, 300, D=112), "refused bf16_head_dim"),
+ "dtype_f16": (fwd(2, 4, 300, dtype=2), "refused dtype"),
+ # dropout: head_dim <= 64 only (served: drop_bf16, f32_d64_drop above)
+ "drop_bf16_d80": (fwd(2, 4, 300, D=80, drop=1), "refused dropout"),
+ "drop_f32_d80": (fwd(2, 4, 300, dtype=F32, D=80, drop=1), "refused dropout"),
+ # the head_dim > 64 plans read no knob
+ "bf16_d80_knobs_ignored": (fwd(2, 4, 300, D=80, p64=2, bwd64=2, role_split=1, cus=8), "bf16_80 3 4 2 256 0 0"),
 }
 BWD_RULES = {
  "train_step": (bwd(64, 16, 1024), "dq64 256 dkv64 256"),
@@ -118,24 +137,40 @@ BWD_RULES = {
  "f32_d33": (bwd(2, 4, 300, 200, dtype=F32, D=33), "f32_dq64 3,4,2 f32_dkv64 2,4,2 128 10"),
  "f32_d64_drop": (bwd(2, 4, 300, 200, dtype=F32, drop=1), "f32_dq64 3,4,2 f32_dkv64 2,4,2 128 10"),
  "f32_knobs_ignored": (bwd(1, 1, 1, 129, dtype=F32, D=1, bwd64=2, cus=8), "f32_dq32 1,1,1 f32_dkv32 2,1,1 128 1"),
+ # the served set.  fp32: every head_dim up to 96, the DMAX 96 instantiations above 64
+ "f32_d64": (bwd(2, 4, 300, 200, dtype=F32, D=64), "f32_dq64 3,4,2 f32_dkv64 2,4,2 128 10"),
+ "f32_d65": (bwd(2, 4, 300, 200, dtype=F32, D=65), "f32_dq96 3,4,2 f32_dkv96 2,4,2 128 10"),
+ "f32_d96": (bwd(2, 4, 300, 200, dtype=F32, D=96), "f32_dq96 3,4,2 f32_dkv96 2,4,2 128 10"),
+ "f32_d97": (bwd(2, 4, 300, 200, dtype=F32, D=97), "refused f32_head_dim"),
+ # bf16: head_dim 64, 80 or 96; 80 / 96 take one workgroup per 128 queries / keys of a (batch, head) from 1-D grids
+ "bf16_d64": (bwd(2, 4, 300, 200, D=64), "dq32 24 dkv64 8"),      # (200 keys: a 256-key workgroup is mostly real)
+ "bf16_d72": (bwd(2, 4, 300, 200, D=72), "refused bf16_head_dim"),
+ "bf16_d80": (bwd(2, 4, 300, 200, D=80), "dq80 24 dkv80 16"),
+ "bf16_d96": (bwd(2, 4, 300, 200, D=96), "dq96 24 dkv96 16"),
+ "bf16_d112": (bwd(2, 4, 300, 200, D=112), "refused bf16_head_dim"),
+ "dtype_f16": (bwd(2, 4, 300, 200, dtype=2), "refused dtype"),
+ # dropout: head_dim <= 64 only (served: drop, f32_d64_drop above)
+ "drop_bf16_d80": (bwd(2, 4, 300, 200, D=80, drop=1), "refused dropout"),
+ "drop_f32_d80": (bwd(2, 4, 300, 200, dtype=F32, D=80, drop=1), "refused dropout"),
+ # RoPE positions (the inverse rotation in the kernels' epilogues): bf16 at head_dim 64 only, and no other routing
+ "rope_bf16_d64": (bwd(64, 16, 1024, rope=1), "dq64 256 dkv64 256"),
+ "rope_bf16_d96": (bwd(2, 4, 300, 200, D=96, rope=1), "refused rope_head_dim"),
+ "rope_f32_d64": (bwd(2, 4, 300, 200, dtype=F32, D=64, rope=1), "refused rope_f32"),
+ # bf16: ceil(Nq / 128) H B and ceil(Nk / 128) H B fit a 1-D grid (65535 x 32768 = 2^31 - 32768)
+ "grid_below_2p31": (bwd(65535, 32768, 128, bwd64=0), "dq32 2147450880 dkv32 2147450880"),
+ "grid_2p31_queries": (bwd(65535, 32769, 128, bwd64=0), "refused bwd_grid"),
+ "grid_2p31_keys": (bwd(65535, 16385, 128, 256, bwd64=0), "refused bwd_grid"),
+ "grid_below_2p31_d80": (bwd(65535, 32768, 128, D=80), "dq80 2147450880 dkv80 2147450880"),
+ "grid_2p31_d80": (bwd(65535, 32769, 128, D=80), "refused bwd_grid"),
+ "grid_f32_no_limit": (bwd(65535, 32769, 128, dtype=F32, D=32), "f32_dq32 1,32769,65535 f32_dkv32 1,32769,65535 128 1073758208"),
+ # the head_dim > 64 plans read no knob
+ "bf16_d80_knobs_ignored": (bwd(2, 4, 300, 200, D=80, p64=2, bwd64=2, role_split=1, cus=8), "dq80 24 dkv80 16"),
 }
 
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
-    assert cxx, "a C++ compiler is needed to build tests/attention_plan_driver.cpp"
-    exe = str(tmp_path_factory.mktemp("attention_plan") / "attention_plan_driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "uniception_amd", "csrc"), os.path.join(ROOT, "tests", "attention_plan_driver.cpp"),
-                           "-o", exe])
-
-    def run(rows):
-        lines = [" ".join(f"{k}={v}" for k, v in row.items()) for row in rows]
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
-        assert len(out) == len(rows)
-        return out
-    return run
+    return attention_routes.build_driver(tmp_path_factory.mktemp("attention_plan"))
 
 
 def check(plan, cases):

@@ -1,5 +1,5 @@
 """GPU: every kernel of the head_dim > 64 attention path (tests/attention_wide_routes.py WITNESSES) is launched at its witness shape through
-ops.attention / ops.attention_bwd, proven to have taken that kernel — the descriptor the wrapper passed goes to the wide plan driver — and
+ops.attention / ops.attention_bwd, proven to have taken that kernel — the descriptor the wrapper passed goes to the plan driver — and
 compared element by element with the fp64 reference under the derived bound.  Then: the refusals (before any launch), and the backward's
 bit reproducibility."""
 import pytest
@@ -69,7 +69,7 @@ def _operands(gpu, D, dtype, B=1, H=2, Nq=40, Nk=40):
 
 
 @pytest.mark.parametrize("dtype,D,what", [(torch.bfloat16, 112, "head_dim"), (torch.float32, 100, "head_dim"), (torch.bfloat16, 80, "dropout"),
-                                          (torch.bfloat16, 96, "rope")])
+                                          (torch.bfloat16, 96, "rope"), (torch.bfloat16, 72, "head_dim"), (torch.float32, 80, "dropout")])
 def test_refusals_come_before_any_launch_and_name_the_head_dim(gpu, dtype, D, what):
     """The C entry points are called directly (the wrappers' own checks aside): status != 0, the message names the head_dim, and the
     outputs — NaN before the call — are untouched."""

@@ -1,7 +1,9 @@
-"""CPU: the plan of every attention launch with head_dim > 64 (uniception_amd/csrc/attention_wide_plan.h, through
-tests/attention_wide_plan_driver.cpp built with the system compiler) — each GPU witness of tests/attention_wide_routes.py and the Pixio
-H/16 and 5B/16 shapes at 256 x 256 and 512 x 512 pinned line by line — and the self-check of the per-element bound those witnesses are
-held to: a CPU emulation of exactly the roundings the wide kernels perform stays inside it, each seeded fault leaves it."""
+"""CPU: the plan of every attention launch with head_dim > 64 (uniception_amd/csrc/attention_plan.h, through
+tests/attention_plan_driver.cpp built with the system compiler: the one plan and the one driver of every head_dim) — each GPU witness of
+tests/attention_wide_routes.py and the Pixio H/16 and 5B/16 shapes at 256 x 256 and 512 x 512 pinned line by line, the head dims without
+a kernel refused with their reason — and the self-check of the per-element bound those witnesses are held to: a CPU emulation of exactly
+the roundings the wide kernels perform stays inside it, each seeded fault leaves it.  (The rules of the served set, one row on each side:
+FWD_RULES / BWD_RULES of tests/test_attention_plan.py.)"""
 import pytest
 
 from tests import attention_wide_routes as R
@@ -13,16 +15,16 @@ def plan(tmp_path_factory):
 
 
 WITNESS_PLANS = {
-    "fwd80_ragged": "bf16_80 2 3 2 256", "fwd80_whole_tile": "bf16_80 2 3 2 256", "fwd80_tiny": "bf16_80 1 1 1 256",
-    "fwd96_ragged": "bf16_96 2 3 2 256", "fwd96_whole_tile": "bf16_96 2 3 2 256", "fwd96_tiny": "bf16_96 1 1 1 256",
+    "fwd80_ragged": "bf16_80 2 3 2 256 0 0", "fwd80_whole_tile": "bf16_80 2 3 2 256 0 0", "fwd80_tiny": "bf16_80 1 1 1 256 0 0",
+    "fwd96_ragged": "bf16_96 2 3 2 256 0 0", "fwd96_whole_tile": "bf16_96 2 3 2 256 0 0", "fwd96_tiny": "bf16_96 1 1 1 256 0 0",
     "bwd80_ragged": "dq80 12 dkv80 6", "bwd80_two_tiles": "dq80 8 dkv80 8",
     "bwd96_ragged": "dq96 12 dkv96 6", "bwd96_two_tiles": "dq96 8 dkv96 8",
-    "f32_fwd_72": "f32_96 2 2 2 128", "f32_fwd_80": "f32_96 2 2 2 128", "f32_fwd_96": "f32_96 2 2 2 128",
+    "f32_fwd_72": "f32_96 2 2 2 128 0 0", "f32_fwd_80": "f32_96 2 2 2 128 0 0", "f32_fwd_96": "f32_96 2 2 2 128 0 0",
     "f32_bwd_80": "f32_dq96 2,2,2 f32_dkv96 1,2,2 128 3", "f32_bwd_96": "f32_dq96 2,2,2 f32_dkv96 1,2,2 128 3",
 }
 MODEL_PLANS = {
-    "pixio_h16_256": ("bf16_80 3 16 32 256", "dq80 1536 dkv80 1536"), "pixio_h16_512": ("bf16_80 9 16 32 256", "dq80 4608 dkv80 4608"),
-    "pixio_5b16_256": ("bf16_96 3 32 32 256", "dq96 3072 dkv96 3072"), "pixio_5b16_512": ("bf16_96 9 32 32 256", "dq96 9216 dkv96 9216"),
+    "pixio_h16_256": ("bf16_80 3 16 32 256 0 0", "dq80 1536 dkv80 1536"), "pixio_h16_512": ("bf16_80 9 16 32 256 0 0", "dq80 4608 dkv80 4608"),
+    "pixio_5b16_256": ("bf16_96 3 32 32 256 0 0", "dq96 3072 dkv96 3072"), "pixio_5b16_512": ("bf16_96 9 32 32 256 0 0", "dq96 9216 dkv96 9216"),
 }
 
 
@@ -41,10 +43,16 @@ def test_the_pixio_shapes_have_their_pinned_plans(plan):
         assert tuple(plan(list(R.model_rows(n)))) == (fwd, bwd), n
 
 
+# head dims without a kernel are refused with their reason; head_dim 64, which the wide plan of old did not own, now gets its 64-wide plan
+OUTSIDE = {(R.BF16, 112): "refused bf16_head_dim", (R.BF16, 72): "refused bf16_head_dim", (R.BF16, 128): "refused bf16_head_dim",
+           (R.F32, 100): "refused f32_head_dim", (R.BF16, 64): "dma4 1 1 1 256 1 0", (R.F32, 64): "f32_64 1 1 1 128 0 0"}
+
+
 @pytest.mark.parametrize("dtype,D", [(R.BF16, 112), (R.BF16, 72), (R.BF16, 128), (R.F32, 100), (R.BF16, 64), (R.F32, 64)])
 def test_head_dims_outside_the_wide_path_are_refused(plan, dtype, D):
     w = R._w("fwd", "", (1, 1, 5, 3), dtype=dtype, D=D)
-    assert plan([R.driver_row(w)]) == ["refused"]
+    assert plan([R.driver_row(w)]) == [OUTSIDE[dtype, D]]
+    assert plan([R.driver_row({**w, "fn": "bwd"})])[0].split()[0] == ("refused" if D != 64 else "dq32" if dtype == R.BF16 else "f32_dq64")
 
 
 # ------------------------------------------------------------------------------------------ the bound, without a GPU

@@ -340,24 +340,9 @@ def _qknorm_bwd(view4, norm, dn):
     return dpre.view(pre.shape), dg, db
 
 
-def _wide_head_checks(dt, Dh, rope, qn, kn, adrop):
-    """bf16 at head_dim 80 / 96 runs the wide-head kernels (plain GEMM, uc_vt_pack, forward with lse, uc_attention_bwd), which have no
-    dropout, qk_norm or RoPE form: each of them raises here, naming the head_dim, before anything is launched."""
-    if dt != torch.bfloat16 or Dh not in ops.WIDE_HEAD_DIMS:
-        return
-    if adrop is not None:
-        raise UcHipError(f"attn_drop > 0 has no HIP path at head_dim {Dh} (attention dropout is head_dim <= 64 only)")
-    if qn is not None or kn is not None:
-        raise UcHipError(f"qk_norm has no HIP training path at head_dim {Dh} in bf16 (head_dim 64 only)")
-    if rope is not None:
-        raise UcHipError(f"RoPE has no HIP path at head_dim {Dh} (the rotation kernels are head_dim 64)")
-
-
 def _attention_fwd(q, k, v, scale, lse, dropout=None):
+    ops.attention_served(q.dtype, q.shape[-1], dropout=dropout is not None)
     if q.dtype == torch.bfloat16:
-        if q.shape[-1] != 64 and q.shape[-1] not in ops.WIDE_HEAD_DIMS:
-            raise UcHipError(f"bf16 attention needs head_dim 64 (got {q.shape[-1]})")
-        _wide_head_checks(q.dtype, q.shape[-1], None, None, None, dropout)
         return ops.attention(q, k, ops.vt_pack(v), scale, v_packed=True, lse=lse, dropout=dropout)
     return ops.attention(q, k, v, scale, lse=lse, dropout=dropout)
 
@@ -567,9 +552,7 @@ def _rope_in_gemm(rope, qn, kn, dt, Dh) -> bool:
     "Does the q / k GEMM's epilogue rotate its output (bf16 with a rope and no qk_norm)?  Else _prep_qk rotates behind the GEMM."
     if qn is not None or kn is not None or dt != torch.bfloat16 or rope is None:
         return False
-    _wide_head_checks(dt, Dh, rope, qn, kn, None)
-    if Dh != 64:
-        raise UcHipError(f"bf16 attention needs head_dim 64 (got {Dh})")
+    ops.attention_served(dt, Dh, rope=True)
     return True
 
 
@@ -647,7 +630,7 @@ class SelfAttnSubLayerFn(Function):
         Ca = qkv.out_features // 3          # width of q / k / v: C, or the layer's latent_attn_dim (utils/transformer_blocks.py:178-199)
         Dh = Ca // H
         _check_rope(rope)
-        _wide_head_checks(dt, Dh, rope, qn, kn, adrop)
+        ops.attention_served(dt, Dh, dropout=adrop is not None, rope=rope is not None, qk_norm=qn is not None or kn is not None)
         g, bta = engine.ln_params(ln)
         h = ops.layernorm(x2d, g, bta, ln.eps, dt)
         wq, bq = engine.lin_weights(qkv, dt)
@@ -722,7 +705,7 @@ class CrossAttnSubLayerFn(Function):
         Mq, C = x2d.shape
         Dh = C // H
         _check_rope(rope)
-        _wide_head_checks(dt, Dh, rope, qn, kn, adrop)
+        ops.attention_served(dt, Dh, dropout=adrop is not None, rope=rope is not None, qk_norm=qn is not None or kn is not None)
         g, bta = engine.ln_params(ln)
         hq = ops.layernorm(x2d, g, bta, ln.eps, dt)
         if lny is not None:

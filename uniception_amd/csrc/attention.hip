@@ -683,49 +683,36 @@ static void launch_attn_dma4_dbg(int dbg, dim3 grid, hipStream_t st, const AttnP
 }
 #endif
 
-// the fp32 verification kernel at DMAX 96 for uc_attention_fwd_wide (64 < head_dim <= 96, no dropout)
-int uc_attention_f32_96_launch(const uc_attention_desc& d, const AttnWideFwdPlan& plan, uc_stream_t stream) {
-    AttnParams p = {};
-    p.Q = d.Q; p.K = d.K; p.V = d.V; p.O = d.O; p.B = d.B; p.H = d.H; p.Nq = d.Nq; p.Nk = d.Nk; p.D = d.D;
-    p.q_sb = d.q_sb; p.q_sn = d.q_sn; p.q_sh = d.q_sh; p.k_sb = d.k_sb; p.k_sn = d.k_sn; p.k_sh = d.k_sh;
-    p.v_sb = d.v_sb; p.v_sn = d.v_sn; p.v_sh = d.v_sh; p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh;
-    p.scale = d.scale;
-    p.lse = d.lse;
-    p.drop = uc_make_dropout(0.f, 0ull);
-    hipLaunchKernelGGL((attn_f32_kernel<96>), dim3(plan.grid[0], plan.grid[1], plan.grid[2]), dim3(plan.block), 0, (hipStream_t)stream, p);
-    UC_CHECK_LAUNCH("uc_attention_fwd");
+// what the kernels of a served forward need of the operands' layout: the bf16 kernels of every head_dim (16-byte row loads of Q / K,
+// packed VT, 8-byte stores of O) alike, the fp32 ones a row-major V
+static int attention_fwd_layout(const uc_attention_desc& d, const char* fn) {
+    if (d.dtype == UC_F32) {
+        UC_REQUIRE(d.v_layout == UC_V_ROWMAJOR, "%s(f32): V must be row-major", fn);
+        return UC_OK;
+    }
+    UC_REQUIRE(d.v_layout == UC_V_PACKED_T, "%s(bf16): V must be in the packed VT layout (uc_vt_pack)", fn);
+    UC_REQUIRE(d.q_sb % 8 == 0 && d.q_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sb % 8 == 0 && d.k_sn % 8 == 0 && d.k_sh % 8 == 0,
+               "%s(bf16): Q/K strides must be multiples of 8 elements", fn);
+    UC_REQUIRE(d.o_sb % 4 == 0 && d.o_sn % 4 == 0 && d.o_sh % 4 == 0, "%s(bf16): O strides must be multiples of 4", fn);
+    UC_REQUIRE(((uintptr_t)d.Q % 16 == 0) && ((uintptr_t)d.K % 16 == 0) && ((uintptr_t)d.V % 16 == 0) && ((uintptr_t)d.O % 8 == 0),
+               "%s(bf16): pointer alignment", fn);
     return UC_OK;
 }
 
-// uc_attention_fwd: validate, fill AttnParams, snapshot the knobs, plan the launch (attention_plan.h) and carry the plan out
+// uc_attention_fwd: check the arguments, snapshot the knobs, plan the launch once (attention_plan.h: a refusal or a kernel with its
+// grid), check the layout the served kernels need, fill AttnParams and carry the plan out
 extern "C" int uc_attention_fwd(const uc_attention_desc* desc, uc_stream_t stream) {
     UC_REQUIRE(desc, "uc_attention_fwd: null descriptor");
     const uc_attention_desc& d = *desc;
     const char* fn = "uc_attention_fwd";
     const void *Q = d.Q, *K = d.K, *V = d.V;
     void* O = d.O;
-    const int dtype = d.dtype, B = d.B, H = d.H, Nq = d.Nq, Nk = d.Nk, D = d.D;
+    const int B = d.B, H = d.H, Nq = d.Nq, Nk = d.Nk, D = d.D;
     UC_REQUIRE(d.drop_p >= 0.f && d.drop_p < 1.f, "%s: drop_p must be in [0, 1) (got %g)", fn, (double)d.drop_p);
     const bool drop = d.drop_p != 0.f;
     UC_REQUIRE(Q && K && V && O, "%s: null pointer", fn);
     UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0, "%s: bad shape", fn);
     UC_REQUIRE(H <= 65535 && B <= 65535, "%s: B and H must fit a grid dimension", fn);
-    if (D > 64) return uc_attention_fwd_wide(d, stream);   // head_dim 80 / 96 (bf16), <= 96 (fp32): attention_wide_plan.h
-    if (dtype == UC_BF16) {
-        UC_REQUIRE(D == 64, "%s(bf16): head_dim must be 64 (got %d); 80 and 96 run the wide-head kernels", fn, D);
-        UC_REQUIRE(d.v_layout == UC_V_PACKED_T, "%s(bf16): V must be in the packed VT layout (uc_vt_pack)", fn);
-        UC_REQUIRE(d.q_sb % 8 == 0 && d.q_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sb % 8 == 0 && d.k_sn % 8 == 0 && d.k_sh % 8 == 0,
-                   "%s(bf16): Q/K strides must be multiples of 8 elements", fn);
-        UC_REQUIRE(d.o_sb % 4 == 0 && d.o_sn % 4 == 0 && d.o_sh % 4 == 0, "%s(bf16): O strides must be multiples of 4", fn);
-        UC_REQUIRE(((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0) && ((uintptr_t)O % 8 == 0),
-                   "%s(bf16): pointer alignment", fn);
-    } else if (dtype == UC_F32) {
-        UC_REQUIRE(d.v_layout == UC_V_ROWMAJOR, "%s(f32): V must be row-major", fn);
-        UC_REQUIRE(D <= 64, "%s(f32): head_dim must be <= 64 (got %d)", fn, D);
-    } else {
-        uc_set_error("%s: unsupported dtype %d", fn, dtype);
-        return UC_ERR_BAD_ARG;
-    }
     // the knob snapshot: uc_knobs() first (it stores the environment's initial values of the run-time switchable ones)
     const UcKnobs& kn = uc_knobs();
     AttnKnobs knobs = {};
@@ -736,6 +723,11 @@ extern "C" int uc_attention_fwd(const uc_attention_desc* desc, uc_stream_t strea
     knobs.dbg = kn.attn_dbg;
 #endif
     const AttnFwdPlan plan = uc_attention_fwd_plan(d, knobs);
+    if (plan.refused) {
+        uc_set_error(uc_attention_refusal_format(plan.refused), fn, plan.refused == UC_AR_DTYPE ? d.dtype : D);
+        return UC_ERR_BAD_ARG;
+    }
+    if (const int bad = attention_fwd_layout(d, fn)) return bad;
 
     AttnParams p;
     p.Q = Q; p.K = K; p.V = V; p.O = O; p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.D = D;
@@ -772,8 +764,11 @@ extern "C" int uc_attention_fwd(const uc_attention_desc* desc, uc_stream_t strea
         case UC_AF_REG128_DROP: hipLaunchKernelGGL(attn_bf16_drop_kernel, grid, block, 0, st, p); break;
         case UC_AF_F32_32: hipLaunchKernelGGL((attn_f32_kernel<32>), grid, block, 0, st, p); break;
         case UC_AF_F32_64: hipLaunchKernelGGL((attn_f32_kernel<64>), grid, block, 0, st, p); break;
+        case UC_AF_F32_96: hipLaunchKernelGGL((attn_f32_kernel<96>), grid, block, 0, st, p); break;
         case UC_AF_F32_32_DROP: hipLaunchKernelGGL((attn_f32_kernel<32, true>), grid, block, 0, st, p); break;
         case UC_AF_F32_64_DROP: hipLaunchKernelGGL((attn_f32_kernel<64, true>), grid, block, 0, st, p); break;
+        case UC_AF_BF16_80:
+        case UC_AF_BF16_96: return uc_attention_wide_fwd_launch(d, plan, stream);   // (its kernels take AttnWideParams: attention_wide.hip)
         case UC_AF_DMA4_DBG:
 #ifdef UC_DIAG
             launch_attn_dma4_dbg(plan.dbg, grid, st, p);
@@ -783,3 +778,4 @@ extern "C" int uc_attention_fwd(const uc_attention_desc* desc, uc_stream_t strea
     UC_CHECK_LAUNCH(fn);
     return UC_OK;
 }
+

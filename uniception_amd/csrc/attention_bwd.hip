@@ -414,25 +414,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
 
 #include "attention_bwd64.h"
 
-// the bf16 backward of uc_attention_bwd (which has checked the pointers and drop_p)
-static int attention_bwd_impl(const uc_attention_bwd_desc& d, uc_stream_t stream) {
-    const int B = d.B, H = d.H, Nq = d.Nq, Nk = d.Nk;
-    UC_REQUIRE((d.rope_qpos == nullptr) == (d.rope_kpos == nullptr), "uc_attention_bwd: rope_qpos and rope_kpos go together");
-    UC_REQUIRE(!d.rope_qpos || (d.rope_base > 0.f && d.rope_f0 != 0.f), "uc_attention_bwd: the inverse RoPE needs base > 0 and F0 != 0");
-    UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && B <= 65535 && H <= 65535, "uc_attention_bwd: bad shape");
-    UC_REQUIRE(d.D == 64, "uc_attention_bwd(bf16): head_dim must be 64 (got %d); 80 and 96 run the wide-head kernels", d.D);
-    UC_REQUIRE(d.q_sn % 8 == 0 && d.k_sn % 8 == 0 && d.v_sn % 8 == 0 && d.o_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sh % 8 == 0 &&
-                   d.v_sh % 8 == 0 && d.o_sh % 8 == 0 && d.q_sb % 8 == 0 && d.k_sb % 8 == 0 && d.v_sb % 8 == 0 && d.o_sb % 8 == 0,
-               "uc_attention_bwd: input strides must be multiples of 8 elements");
-    UC_REQUIRE(d.dq_sn % 4 == 0 && d.dk_sn % 4 == 0 && d.dv_sn % 4 == 0 && d.dq_sh % 4 == 0 && d.dk_sh % 4 == 0 && d.dv_sh % 4 == 0 &&
-                   d.dq_sb % 4 == 0 && d.dk_sb % 4 == 0 && d.dv_sb % 4 == 0,
-               "uc_attention_bwd: output strides must be multiples of 4 elements");
+// the parameters of the bf16 head_dim 64 kernels (uc_attention_bwd)
+static AttnBwdParams attention_bwd_params(const uc_attention_bwd_desc& d) {
     AttnBwdParams p;
     p.Q = (const bf16_t*)d.Q; p.K = (const bf16_t*)d.K; p.V = (const bf16_t*)d.V; p.O = (const bf16_t*)d.O; p.dO = (const bf16_t*)d.dO;
     p.LSE = d.LSE; p.delta = d.delta; p.aux = d.delta;
-    p.nq_pad = (Nq + 127) / 128 * 128;
+    p.nq_pad = (d.Nq + 127) / 128 * 128;
     p.dQ = (bf16_t*)d.dQ; p.dK = (bf16_t*)d.dK; p.dV = (bf16_t*)d.dV;
-    p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk;
+    p.B = d.B; p.H = d.H; p.Nq = d.Nq; p.Nk = d.Nk;
     p.q_sb = d.q_sb; p.q_sn = d.q_sn; p.q_sh = d.q_sh; p.k_sb = d.k_sb; p.k_sn = d.k_sn; p.k_sh = d.k_sh; p.v_sb = d.v_sb; p.v_sn = d.v_sn;
     p.v_sh = d.v_sh; p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh; p.dq_sb = d.dq_sb; p.dq_sn = d.dq_sn; p.dq_sh = d.dq_sh;
     p.dk_sb = d.dk_sb; p.dk_sn = d.dk_sn; p.dk_sh = d.dk_sh; p.dv_sb = d.dv_sb; p.dv_sn = d.dv_sn; p.dv_sh = d.dv_sh; p.scale = d.scale;
@@ -440,28 +429,7 @@ static int attention_bwd_impl(const uc_attention_bwd_desc& d, uc_stream_t stream
     p.rope_turn0 = d.rope_qpos ? (float)((double)d.rope_f0 / 6.283185307179586476925) : 0.f;
     p.rope_ratio = d.rope_qpos ? (float)pow((double)d.rope_base, -1.0 / 16.0) : 1.f;
     p.drop = uc_make_dropout(d.drop_p, d.drop_p != 0.f ? d.seed : 0ull);
-    // the knob snapshot: uc_knobs() first (it stores the environment's initial values of the run-time switchable ones)
-    (void)uc_knobs();
-    AttnKnobs knobs = {};
-    knobs.bwd64 = g_uc_attn_bwd64.load(std::memory_order_relaxed);
-    knobs.cus = uc_num_cus();
-    const AttnBwdPlan plan = uc_attention_bwd_plan(d, knobs);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 gq(plan.dq_grid[0]), gkv(plan.dkv_grid[0]), block(plan.block);
-    switch (plan.dq) {
-        case UC_AB_DQ32: hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, gq, block, 0, st, p); break;
-        case UC_AB_DQ64: hipLaunchKernelGGL(attn_bwd_dq64_kernel, gq, block, 0, st, p); break;
-        case UC_AB_DQ32_DROP: hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, gq, block, 0, st, p); break;
-        default: break;   // (the fp32 kernels: attention_bwd_f32_impl)
-    }
-    switch (plan.dkv) {
-        case UC_AB_DKV32: hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, gkv, block, 0, st, p); break;
-        case UC_AB_DKV64: hipLaunchKernelGGL(attn_bwd_dkv64_kernel, gkv, block, 0, st, p); break;
-        case UC_AB_DKV32_DROP: hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, gkv, block, 0, st, p); break;
-        default: break;
-    }
-    UC_CHECK_LAUNCH("uc_attention_bwd");
-    return UC_OK;
+    return p;
 }
 
 // =================================================================================================================
@@ -635,53 +603,75 @@ static AttnBwdF32Params attention_bwd_f32_params(const uc_attention_bwd_desc& d)
     return p;
 }
 
-// the fp32 verification kernels at DMAX 96 for uc_attention_bwd_wide (64 < head_dim <= 96, no dropout, no RoPE)
-int uc_attention_bwd_f32_96_launch(const uc_attention_bwd_desc& d, const AttnWideBwdPlan& plan, uc_stream_t stream) {
-    const AttnBwdF32Params p = attention_bwd_f32_params(d);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 gq(plan.dq_grid[0], plan.dq_grid[1], plan.dq_grid[2]), gkv(plan.dkv_grid[0], plan.dkv_grid[1], plan.dkv_grid[2]);
-    hipLaunchKernelGGL(attn_delta_f32_kernel, dim3(plan.delta_grid), dim3(256), 0, st, p);
-    hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<96>), gq, dim3(plan.block), 0, st, p);
-    hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<96>), gkv, dim3(plan.block), 0, st, p);
-    UC_CHECK_LAUNCH("uc_attention_bwd");
-    return UC_OK;
-}
-
-// the fp32 backward of uc_attention_bwd
-static int attention_bwd_f32_impl(const uc_attention_bwd_desc& d, uc_stream_t stream) {
-    const int B = d.B, H = d.H, Nq = d.Nq, Nk = d.Nk, D = d.D;
-    UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0 && D <= 64 && B <= 65535 && H <= 65535, "uc_attention_bwd(f32): bad shape (head_dim <= 64)");
-    UC_REQUIRE(!d.rope_qpos && !d.rope_kpos, "uc_attention_bwd(f32): the fp32 backward takes no RoPE positions");
-    const AttnBwdF32Params p = attention_bwd_f32_params(d);
-    const AttnBwdPlan plan = uc_attention_bwd_plan(d, AttnKnobs{});   // (the fp32 routing reads no knob)
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 gq(plan.dq_grid[0], plan.dq_grid[1], plan.dq_grid[2]), gkv(plan.dkv_grid[0], plan.dkv_grid[1], plan.dkv_grid[2]);
-    const dim3 block(plan.block);
-    hipLaunchKernelGGL(attn_delta_f32_kernel, dim3(plan.delta_grid), dim3(256), 0, st, p);
-    switch (plan.dq) {
-        case UC_AB_F32_DQ32: hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<32>), gq, block, 0, st, p); break;
-        case UC_AB_F32_DQ64: hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<64>), gq, block, 0, st, p); break;
-        default: break;   // (the bf16 kernels: attention_bwd_impl)
-    }
-    switch (plan.dkv) {
-        case UC_AB_F32_DKV32: hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<32>), gkv, block, 0, st, p); break;
-        case UC_AB_F32_DKV64: hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<64>), gkv, block, 0, st, p); break;
-        default: break;
-    }
-    UC_CHECK_LAUNCH("uc_attention_bwd");
+// what the bf16 kernels of a served backward need of the operands' layout (the fp32 kernels address single elements: nothing).  RoPE
+// positions reach this point at head_dim 64 only (attention_plan.h).  The pointer-alignment test keeps the reach it always had, the
+// head_dim 80 / 96 kernels: whether the head_dim 64 kernels tolerate less has not been shown either way.
+static int attention_bwd_layout(const uc_attention_bwd_desc& d, const char* fn) {
+    if (d.dtype == UC_F32) return UC_OK;
+    UC_REQUIRE((d.rope_qpos == nullptr) == (d.rope_kpos == nullptr), "%s: rope_qpos and rope_kpos go together", fn);
+    UC_REQUIRE(!d.rope_qpos || (d.rope_base > 0.f && d.rope_f0 != 0.f), "%s: the inverse RoPE needs base > 0 and F0 != 0", fn);
+    UC_REQUIRE(d.q_sn % 8 == 0 && d.k_sn % 8 == 0 && d.v_sn % 8 == 0 && d.o_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sh % 8 == 0 &&
+                   d.v_sh % 8 == 0 && d.o_sh % 8 == 0 && d.q_sb % 8 == 0 && d.k_sb % 8 == 0 && d.v_sb % 8 == 0 && d.o_sb % 8 == 0,
+               "%s: input strides must be multiples of 8 elements", fn);
+    UC_REQUIRE(d.dq_sn % 4 == 0 && d.dk_sn % 4 == 0 && d.dv_sn % 4 == 0 && d.dq_sh % 4 == 0 && d.dk_sh % 4 == 0 && d.dv_sh % 4 == 0 &&
+                   d.dq_sb % 4 == 0 && d.dk_sb % 4 == 0 && d.dv_sb % 4 == 0,
+               "%s: output strides must be multiples of 4 elements", fn);
+    if (d.D > 64)
+        UC_REQUIRE(((uintptr_t)d.Q % 16 == 0) && ((uintptr_t)d.K % 16 == 0) && ((uintptr_t)d.V % 16 == 0) && ((uintptr_t)d.O % 16 == 0) &&
+                       ((uintptr_t)d.dO % 16 == 0) && ((uintptr_t)d.dQ % 8 == 0) && ((uintptr_t)d.dK % 8 == 0) && ((uintptr_t)d.dV % 8 == 0),
+                   "%s(bf16): pointer alignment", fn);
     return UC_OK;
 }
 
 // Attention backward, bf16 or fp32, with dropout when drop_p > 0 (O is then the forward's dropped output, LSE that of the undropped
-// scores)
+// scores): check the arguments, snapshot the knobs, plan the launch once (attention_plan.h: a refusal or the two kernels with their
+// grids), check the layout the served kernels need, fill the parameters and carry the plan out
 extern "C" int uc_attention_bwd(const uc_attention_bwd_desc* desc, uc_stream_t stream) {
     UC_REQUIRE(desc, "uc_attention_bwd: null descriptor");
     const uc_attention_bwd_desc& d = *desc;
-    UC_REQUIRE(d.drop_p >= 0.f && d.drop_p < 1.f, "uc_attention_bwd: drop_p must be in [0, 1) (got %g)", (double)d.drop_p);
-    UC_REQUIRE(d.Q && d.K && d.V && d.O && d.dO && d.LSE && d.dQ && d.dK && d.dV && d.delta, "uc_attention_bwd: null pointer");
-    if (d.D > 64) return uc_attention_bwd_wide(d, stream);   // head_dim 80 / 96 (bf16), <= 96 (fp32): attention_wide_plan.h
-    if (d.dtype == UC_BF16) return attention_bwd_impl(d, stream);
-    if (d.dtype == UC_F32) return attention_bwd_f32_impl(d, stream);
-    uc_set_error("uc_attention_bwd: unsupported dtype %d", d.dtype);
-    return UC_ERR_BAD_ARG;
+    const char* fn = "uc_attention_bwd";
+    UC_REQUIRE(d.drop_p >= 0.f && d.drop_p < 1.f, "%s: drop_p must be in [0, 1) (got %g)", fn, (double)d.drop_p);
+    UC_REQUIRE(d.Q && d.K && d.V && d.O && d.dO && d.LSE && d.dQ && d.dK && d.dV && d.delta, "%s: null pointer", fn);
+    UC_REQUIRE(d.B > 0 && d.H > 0 && d.Nq > 0 && d.Nk > 0 && d.D > 0 && d.B <= 65535 && d.H <= 65535, "%s: bad shape", fn);
+    // the knob snapshot: uc_knobs() first (it stores the environment's initial values of the run-time switchable ones)
+    (void)uc_knobs();
+    AttnKnobs knobs = {};
+    knobs.bwd64 = g_uc_attn_bwd64.load(std::memory_order_relaxed);
+    knobs.cus = uc_num_cus();
+    const AttnBwdPlan plan = uc_attention_bwd_plan(d, knobs);
+    if (plan.refused) {
+        uc_set_error(uc_attention_refusal_format(plan.refused), fn, plan.refused == UC_AR_DTYPE ? d.dtype : d.D);
+        return UC_ERR_BAD_ARG;
+    }
+    if (const int bad = attention_bwd_layout(d, fn)) return bad;
+
+    // (each kernel family reads its own struct; filling the one a launch does not use costs a few stores)
+    const AttnBwdParams p = attention_bwd_params(d);
+    const AttnBwdF32Params pf = attention_bwd_f32_params(d);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 gq(plan.dq_grid[0], plan.dq_grid[1], plan.dq_grid[2]), gkv(plan.dkv_grid[0], plan.dkv_grid[1], plan.dkv_grid[2]);
+    const dim3 block(plan.block);
+    if (plan.delta_grid) hipLaunchKernelGGL(attn_delta_f32_kernel, dim3(plan.delta_grid), dim3(256), 0, st, pf);
+    switch (plan.dq) {
+        case UC_AB_DQ32: hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, gq, block, 0, st, p); break;
+        case UC_AB_DQ64: hipLaunchKernelGGL(attn_bwd_dq64_kernel, gq, block, 0, st, p); break;
+        case UC_AB_DQ32_DROP: hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, gq, block, 0, st, p); break;
+        case UC_AB_F32_DQ32: hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<32>), gq, block, 0, st, pf); break;
+        case UC_AB_F32_DQ64: hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<64>), gq, block, 0, st, pf); break;
+        case UC_AB_F32_DQ96: hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<96>), gq, block, 0, st, pf); break;
+        case UC_AB_DQ80:
+        case UC_AB_DQ96: return uc_attention_wide_bwd_launch(d, plan, stream);   // dQ and dK / dV (AttnWideBwdParams: attention_wide.hip)
+    }
+    switch (plan.dkv) {
+        case UC_AB_DKV32: hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, gkv, block, 0, st, p); break;
+        case UC_AB_DKV64: hipLaunchKernelGGL(attn_bwd_dkv64_kernel, gkv, block, 0, st, p); break;
+        case UC_AB_DKV32_DROP: hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, gkv, block, 0, st, p); break;
+        case UC_AB_F32_DKV32: hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<32>), gkv, block, 0, st, pf); break;
+        case UC_AB_F32_DKV64: hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<64>), gkv, block, 0, st, pf); break;
+        case UC_AB_F32_DKV96: hipLaunchKernelGGL((attn_bwd_dkv_f32_kernel<96>), gkv, block, 0, st, pf); break;
+        case UC_AB_DKV80:
+        case UC_AB_DKV96: break;   // (launched with their dQ kernels above)
+    }
+    UC_CHECK_LAUNCH(fn);
+    return UC_OK;
 }

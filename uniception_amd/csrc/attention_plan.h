@@ -1,13 +1,45 @@
-// Routing of one attention forward / backward launch (uc_attention_fwd, uc_attention_bwd; bf16 and fp32, with and without dropout): which
-// kernel, grid and workgroup size a launch gets.
+// Routing of one attention forward / backward launch (uc_attention_fwd, uc_attention_bwd; bf16 and fp32, every head_dim, with and
+// without dropout): whether the launch is served at all and, if it is, which kernel, grid and workgroup size it gets.  The plans are
+// total: every descriptor that passed the entry points' null / shape / drop_p checks gets either a refusal reason or a launch, and
+// nothing else in the library decides which dtype, head_dim, dropout and RoPE combinations exist.
 //
 // Host-only, header-only and pure: no HIP header and no global state, so the system C++ compiler builds it
-// (tests/test_attention_plan.py).  The entry points read every knob once into an AttnKnobs snapshot and call the plan once; they
-// carry it out and decide nothing.  A knob switched at run time (uc_tuning_set) therefore takes effect between launches, never
-// inside one.
+// (tests/test_attention_plan.py, tests/test_attention_wide_plan.py).  The entry points read every knob once into an AttnKnobs
+// snapshot and call the plan once; they carry it out and decide nothing.  A knob switched at run time (uc_tuning_set) therefore
+// takes effect between launches, never inside one.  The head_dim > 64 kernels (attention_wide.hip, and the fp32 verification
+// kernels at DMAX 96) read no knob: their plan is a function of the descriptor alone.
 #pragma once
 #include <stdint.h>
 #include "../../include/uc_hip.h"
+
+constexpr int UC_ATTN_WIDE_MAX_D = 96;   // the largest head_dim any kernel serves
+
+// why a launch is refused; 0: it is served.  One message per reason (uc_attention_refusal_format).
+enum AttnRefusal {
+    UC_AR_SERVED = 0,
+    UC_AR_DTYPE,         // dtype is neither UC_BF16 nor UC_F32
+    UC_AR_BF16_HEAD_DIM, // bf16: head_dim must be 64, 80 or 96
+    UC_AR_F32_HEAD_DIM,  // fp32: head_dim must be <= UC_ATTN_WIDE_MAX_D
+    UC_AR_DROPOUT,       // attention dropout exists at head_dim <= 64 only
+    UC_AR_ROPE_F32,      // backward RoPE positions: the fp32 backward has no inverse rotation
+    UC_AR_ROPE_HEAD_DIM, // backward RoPE positions: the bf16 inverse rotation is head_dim 64 only
+    UC_AR_BWD_GRID,      // bf16 backward: ceil(Nq / 128) H B or ceil(Nk / 128) H B does not fit a 1-D grid (>= 2^31)
+};
+
+// the message of a refusal as a printf format of (entry point's name, int): the int is the dtype for UC_AR_DTYPE, the head_dim otherwise
+static inline const char* uc_attention_refusal_format(AttnRefusal r) {
+    static const char* const TEXT[] = {
+        "%s: served (head_dim %d)",
+        "%s: unsupported dtype %d",
+        "%s(bf16): head_dim must be 64, 80 or 96 (got %d)",
+        "%s(f32): head_dim must be <= 96 (got %d)",
+        "%s: attention dropout is not available at head_dim %d (head_dim <= 64 only)",
+        "%s(f32): the fp32 backward takes no RoPE positions (head_dim %d)",
+        "%s: the inverse RoPE is not available at head_dim %d (bf16 at head_dim 64 only)",
+        "%s: too many 128-row tiles for one grid (head_dim %d)",
+    };
+    return TEXT[r];
+}
 
 enum AttnFwdKernel {
     UC_AF_REG128,        // attn_bf16_kernel: register-staged, 128 queries per workgroup, grid (query tiles, H, B)
@@ -22,6 +54,9 @@ enum AttnFwdKernel {
     UC_AF_F32_32_DROP,   // attn_f32_kernel<32, true>
     UC_AF_F32_64_DROP,   // attn_f32_kernel<64, true>
     UC_AF_DMA4_DBG,      // attn_bf16_dma_kernel<4, dbg>: diag build only (UC_ATTN_DBG, wrong results)
+    UC_AF_BF16_80,       // attnw_fwd_kernel<80> (attention_wide.hip): four waves, 128 queries per workgroup, grid (query tiles, H, B)
+    UC_AF_BF16_96,       // attnw_fwd_kernel<96>
+    UC_AF_F32_96,        // attn_f32_kernel<96>: 64 < head_dim <= 96 (no dropout form)
 };
 
 enum AttnDqKernel {
@@ -30,6 +65,9 @@ enum AttnDqKernel {
     UC_AB_DQ32_DROP,     // attn_bwd_dq_kernel<true>
     UC_AB_F32_DQ32,      // attn_bwd_dq_f32_kernel<32>: fp32 verification kernel (dropout a run-time test), head_dim <= 32, grid (query tiles, H, B)
     UC_AB_F32_DQ64,      // attn_bwd_dq_f32_kernel<64>: head_dim <= 64
+    UC_AB_DQ80,          // attnw_bwd_dq_kernel<80> (attention_wide.hip): 128 queries per workgroup, 1-D grid
+    UC_AB_DQ96,          // attnw_bwd_dq_kernel<96>
+    UC_AB_F32_DQ96,      // attn_bwd_dq_f32_kernel<96>: 64 < head_dim <= 96
 };
 
 enum AttnDkvKernel {
@@ -38,6 +76,9 @@ enum AttnDkvKernel {
     UC_AB_DKV32_DROP,    // attn_bwd_dkv_kernel<true>
     UC_AB_F32_DKV32,     // attn_bwd_dkv_f32_kernel<32>: grid (key tiles, H, B)
     UC_AB_F32_DKV64,     // attn_bwd_dkv_f32_kernel<64>
+    UC_AB_DKV80,         // attnw_bwd_dkv_kernel<80> (attention_wide.hip): 128 keys per workgroup, 1-D grid
+    UC_AB_DKV96,         // attnw_bwd_dkv_kernel<96>
+    UC_AB_F32_DKV96,     // attn_bwd_dkv_f32_kernel<96>
 };
 
 // every knob the routing reads, read once per launch
@@ -49,7 +90,9 @@ struct AttnKnobs {
     int dbg;          // UC_ATTN_DBG anatomy switches (diag build only; 0 in the release build)
 };
 
+// (a refused plan — refused != 0 — has every other field zero)
 struct AttnFwdPlan {
+    AttnRefusal refused;
     AttnFwdKernel kernel;
     unsigned grid[3];   // x, y, z
     int block;          // threads per workgroup
@@ -59,6 +102,7 @@ struct AttnFwdPlan {
 };
 
 struct AttnBwdPlan {
+    AttnRefusal refused;
     AttnDqKernel dq;
     AttnDkvKernel dkv;
     unsigned dq_grid[3], dkv_grid[3];   // x, y, z (bf16: 1-D)
@@ -66,13 +110,32 @@ struct AttnBwdPlan {
     unsigned delta_grid;                // fp32: attn_delta_f32_kernel's 1-D grid of 256 threads, launched first; else 0
 };
 
-// (the plans read only the shape, strides, dtype, v_layout, the output's address and drop_p of the descriptor)
+// THE served set: which dtype, head_dim, dropout and backward-RoPE combinations have a kernel (rope: the backward got positions)
+static inline AttnRefusal uc_attention_refusal(int dtype, int D, bool drop, bool rope) {
+    if (dtype != UC_BF16 && dtype != UC_F32) return UC_AR_DTYPE;
+    if (dtype == UC_BF16 && D != 64 && D != 80 && D != 96) return UC_AR_BF16_HEAD_DIM;
+    if (dtype == UC_F32 && D > UC_ATTN_WIDE_MAX_D) return UC_AR_F32_HEAD_DIM;
+    if (drop && D > 64) return UC_AR_DROPOUT;
+    if (rope && dtype == UC_F32) return UC_AR_ROPE_F32;
+    if (rope && D != 64) return UC_AR_ROPE_HEAD_DIM;
+    return UC_AR_SERVED;
+}
+
+// (the plans read only the shape, strides, dtype, v_layout, the output's address, drop_p and — backward — whether there are RoPE
+//  positions of the descriptor)
 static inline AttnFwdPlan uc_attention_fwd_plan(const uc_attention_desc& d, const AttnKnobs& k) {
     AttnFwdPlan plan = {};
+    plan.refused = uc_attention_refusal(d.dtype, d.D, d.drop_p != 0.f, false);
+    if (plan.refused) return plan;
     plan.block = 256;
     // the grid of the register-staged and fp32 kernels: one workgroup per 128 queries of a (batch, head)
     plan.grid[0] = (unsigned)((d.Nq + 127) / 128); plan.grid[1] = (unsigned)d.H; plan.grid[2] = (unsigned)d.B;
     const bool drop = d.drop_p != 0.f;
+    if (d.D > 64) {   // one workgroup per 128 queries here too; no knob is read
+        plan.kernel = d.dtype == UC_F32 ? UC_AF_F32_96 : d.D == 80 ? UC_AF_BF16_80 : UC_AF_BF16_96;
+        if (d.dtype == UC_F32) plan.block = 128;
+        return plan;
+    }
     if (d.dtype == UC_F32) {
         plan.kernel = d.D <= 32 ? (drop ? UC_AF_F32_32_DROP : UC_AF_F32_32) : (drop ? UC_AF_F32_64_DROP : UC_AF_F32_64);
         plan.block = 128;
@@ -138,10 +201,17 @@ static inline AttnFwdPlan uc_attention_fwd_plan(const uc_attention_desc& d, cons
 static inline AttnBwdPlan uc_attention_bwd_plan(const uc_attention_bwd_desc& d, const AttnKnobs& k) {
     AttnBwdPlan plan = {};
     const int Nq = d.Nq, Nk = d.Nk, H = d.H, B = d.B;
+    plan.refused = uc_attention_refusal(d.dtype, d.D, d.drop_p != 0.f, d.rope_qpos || d.rope_kpos);
+    // every bf16 backward kernel takes its 128-row tiles from a 1-D grid (the persistent 64-row kernels count theirs from the same
+    // product): it must fit one.  (Only the head_dim 80 / 96 entry used to test this; at head_dim 64 the product was cast to unsigned
+    // unchecked.  A launch that large already fails in the runtime, so the rule refuses nothing that works.)
+    if (!plan.refused && d.dtype == UC_BF16 &&
+        ((int64_t)((Nq + 127) / 128) * H * B >= ((int64_t)1 << 31) || (int64_t)((Nk + 127) / 128) * H * B >= ((int64_t)1 << 31)))
+        plan.refused = UC_AR_BWD_GRID;
+    if (plan.refused) return plan;
     if (d.dtype == UC_F32) {   // one thread per query row (dQ) / per key row (dK, dV), 128 per workgroup, after the delta pass
-        const bool d32 = d.D <= 32;
-        plan.dq = d32 ? UC_AB_F32_DQ32 : UC_AB_F32_DQ64;
-        plan.dkv = d32 ? UC_AB_F32_DKV32 : UC_AB_F32_DKV64;
+        plan.dq = d.D <= 32 ? UC_AB_F32_DQ32 : d.D <= 64 ? UC_AB_F32_DQ64 : UC_AB_F32_DQ96;
+        plan.dkv = d.D <= 32 ? UC_AB_F32_DKV32 : d.D <= 64 ? UC_AB_F32_DKV64 : UC_AB_F32_DKV96;
         plan.dq_grid[0] = (unsigned)((Nq + 127) / 128); plan.dkv_grid[0] = (unsigned)((Nk + 127) / 128);
         plan.dq_grid[1] = plan.dkv_grid[1] = (unsigned)H; plan.dq_grid[2] = plan.dkv_grid[2] = (unsigned)B;
         plan.block = 128;
@@ -152,6 +222,11 @@ static inline AttnBwdPlan uc_attention_bwd_plan(const uc_attention_bwd_desc& d, 
     plan.dq_grid[1] = plan.dq_grid[2] = plan.dkv_grid[1] = plan.dkv_grid[2] = 1;
     plan.dq_grid[0] = (unsigned)(((Nq + 127) / 128) * H * B);
     plan.dkv_grid[0] = (unsigned)(((Nk + 127) / 128) * H * B);
+    if (d.D > 64) {   // the head_dim 80 / 96 kernels: these grids, no knob
+        plan.dq = d.D == 80 ? UC_AB_DQ80 : UC_AB_DQ96;
+        plan.dkv = d.D == 80 ? UC_AB_DKV80 : UC_AB_DKV96;
+        return plan;
+    }
     if (d.drop_p != 0.f) {   // attention dropout: the 32-row kernels with the forward's mask re-evaluated per element
         plan.dq = UC_AB_DQ32_DROP;
         plan.dkv = UC_AB_DKV32_DROP;

@@ -1,5 +1,6 @@
-// Attention forward and backward for head_dim 80 and 96 on gfx950 (bf16, v_mfma_f32_32x32x16_bf16), and the entry of every launch
-// with head_dim > 64 (the fp32 ones go on to the verification kernels of attention.hip / attention_bwd.hip at DMAX 96).
+// Attention forward and backward for head_dim 80 and 96 on gfx950 (bf16, v_mfma_f32_32x32x16_bf16): the kernels and their two
+// launchers.  uc_attention_fwd / uc_attention_bwd (attention.hip, attention_bwd.hip) validate, plan (attention_plan.h) and call a
+// launcher where the plan names one of these kernels; nothing here validates or decides.
 //
 // The layout is that of attention_tile.h / attention_bwd.hip with D / 16 k-steps and three 32-channel output blocks:
 //   forward   S^T = K . Q^T (KS = D / 16 k-steps), online softmax per lane pair, O^T += V^T . P^T into o[3];
@@ -477,28 +478,9 @@ __global__ __launch_bounds__(256) void attnw_bwd_dkv_kernel(AttnWideBwdParams p)
 }
 
 // =================================================================================================================
-// entry: every uc_attention_fwd / uc_attention_bwd with head_dim > 64 (null pointers, drop_p's range and the basic shape are checked)
+// launchers: uc_attention_fwd / uc_attention_bwd have validated the descriptor and planned the launch (attention_plan.h)
 // =================================================================================================================
-int uc_attention_fwd_wide(const uc_attention_desc& d, uc_stream_t stream) {
-    const char* fn = "uc_attention_fwd";
-    const int D = d.D;
-    UC_REQUIRE(d.dtype == UC_BF16 || d.dtype == UC_F32, "%s: unsupported dtype %d", fn, d.dtype);
-    if (d.dtype == UC_BF16)
-        UC_REQUIRE(uc_attention_wide_supported(UC_BF16, D), "%s(bf16): head_dim must be 64, 80 or 96 (got %d)", fn, D);
-    else
-        UC_REQUIRE(uc_attention_wide_supported(UC_F32, D), "%s(f32): head_dim must be <= %d (got %d)", fn, UC_ATTN_WIDE_MAX_D, D);
-    UC_REQUIRE(d.drop_p == 0.f, "%s: attention dropout is not available at head_dim %d (head_dim <= 64 only)", fn, D);
-    const AttnWideFwdPlan plan = uc_attention_wide_fwd_plan(d);
-    if (d.dtype == UC_F32) {
-        UC_REQUIRE(d.v_layout == UC_V_ROWMAJOR, "%s(f32): V must be row-major", fn);
-        return uc_attention_f32_96_launch(d, plan, stream);
-    }
-    UC_REQUIRE(d.v_layout == UC_V_PACKED_T, "%s(bf16): V must be in the packed VT layout (uc_vt_pack)", fn);
-    UC_REQUIRE(d.q_sb % 8 == 0 && d.q_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sb % 8 == 0 && d.k_sn % 8 == 0 && d.k_sh % 8 == 0,
-               "%s(bf16): Q/K strides must be multiples of 8 elements", fn);
-    UC_REQUIRE(d.o_sb % 4 == 0 && d.o_sn % 4 == 0 && d.o_sh % 4 == 0, "%s(bf16): O strides must be multiples of 4", fn);
-    UC_REQUIRE(((uintptr_t)d.Q % 16 == 0) && ((uintptr_t)d.K % 16 == 0) && ((uintptr_t)d.V % 16 == 0) && ((uintptr_t)d.O % 8 == 0),
-               "%s(bf16): pointer alignment", fn);
+int uc_attention_wide_fwd_launch(const uc_attention_desc& d, const AttnFwdPlan& plan, uc_stream_t stream) {
     AttnWideParams p;
     p.Q = (const bf16_t*)d.Q; p.K = (const bf16_t*)d.K; p.VT = (const bf16_t*)d.V; p.O = (bf16_t*)d.O; p.lse = d.lse;
     p.B = d.B; p.H = d.H; p.Nq = d.Nq; p.Nk = d.Nk; p.npad = (d.Nk + 63) / 64 * 64;
@@ -506,50 +488,27 @@ int uc_attention_fwd_wide(const uc_attention_desc& d, uc_stream_t stream) {
     p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh; p.scale = d.scale;
     const dim3 grid(plan.grid[0], plan.grid[1], plan.grid[2]), block(plan.block);
     hipStream_t st = (hipStream_t)stream;
-    if (plan.kernel == UC_AWF_BF16_80) hipLaunchKernelGGL(attnw_fwd_kernel<80>, grid, block, 0, st, p);
+    if (plan.kernel == UC_AF_BF16_80) hipLaunchKernelGGL(attnw_fwd_kernel<80>, grid, block, 0, st, p);
     else hipLaunchKernelGGL(attnw_fwd_kernel<96>, grid, block, 0, st, p);
-    UC_CHECK_LAUNCH(fn);
+    UC_CHECK_LAUNCH("uc_attention_fwd");
     return UC_OK;
 }
 
-int uc_attention_bwd_wide(const uc_attention_bwd_desc& d, uc_stream_t stream) {
-    const char* fn = "uc_attention_bwd";
-    const int D = d.D, B = d.B, H = d.H, Nq = d.Nq, Nk = d.Nk;
-    UC_REQUIRE(d.dtype == UC_BF16 || d.dtype == UC_F32, "%s: unsupported dtype %d", fn, d.dtype);
-    UC_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && B <= 65535 && H <= 65535, "%s: bad shape", fn);
-    if (d.dtype == UC_BF16)
-        UC_REQUIRE(uc_attention_wide_supported(UC_BF16, D), "%s(bf16): head_dim must be 64, 80 or 96 (got %d)", fn, D);
-    else
-        UC_REQUIRE(uc_attention_wide_supported(UC_F32, D), "%s(f32): head_dim must be <= %d (got %d)", fn, UC_ATTN_WIDE_MAX_D, D);
-    UC_REQUIRE(d.drop_p == 0.f, "%s: attention dropout is not available at head_dim %d (head_dim <= 64 only)", fn, D);
-    UC_REQUIRE(!d.rope_qpos && !d.rope_kpos, "%s: the inverse RoPE is not available at head_dim %d (head_dim 64 only)", fn, D);
-    const AttnWideBwdPlan plan = uc_attention_wide_bwd_plan(d);
-    if (d.dtype == UC_F32) return uc_attention_bwd_f32_96_launch(d, plan, stream);
-    UC_REQUIRE((int64_t)((Nq + 127) / 128) * H * B < ((int64_t)1 << 31) && (int64_t)((Nk + 127) / 128) * H * B < ((int64_t)1 << 31),
-               "%s: too many tiles for one grid", fn);
-    UC_REQUIRE(d.q_sn % 8 == 0 && d.k_sn % 8 == 0 && d.v_sn % 8 == 0 && d.o_sn % 8 == 0 && d.q_sh % 8 == 0 && d.k_sh % 8 == 0 &&
-                   d.v_sh % 8 == 0 && d.o_sh % 8 == 0 && d.q_sb % 8 == 0 && d.k_sb % 8 == 0 && d.v_sb % 8 == 0 && d.o_sb % 8 == 0,
-               "%s: input strides must be multiples of 8 elements", fn);
-    UC_REQUIRE(d.dq_sn % 4 == 0 && d.dk_sn % 4 == 0 && d.dv_sn % 4 == 0 && d.dq_sh % 4 == 0 && d.dk_sh % 4 == 0 && d.dv_sh % 4 == 0 &&
-                   d.dq_sb % 4 == 0 && d.dk_sb % 4 == 0 && d.dv_sb % 4 == 0,
-               "%s: output strides must be multiples of 4 elements", fn);
-    UC_REQUIRE(((uintptr_t)d.Q % 16 == 0) && ((uintptr_t)d.K % 16 == 0) && ((uintptr_t)d.V % 16 == 0) && ((uintptr_t)d.O % 16 == 0) &&
-                   ((uintptr_t)d.dO % 16 == 0) && ((uintptr_t)d.dQ % 8 == 0) && ((uintptr_t)d.dK % 8 == 0) && ((uintptr_t)d.dV % 8 == 0),
-               "%s(bf16): pointer alignment", fn);
+int uc_attention_wide_bwd_launch(const uc_attention_bwd_desc& d, const AttnBwdPlan& plan, uc_stream_t stream) {
     AttnWideBwdParams p;
     p.Q = (const bf16_t*)d.Q; p.K = (const bf16_t*)d.K; p.V = (const bf16_t*)d.V; p.O = (const bf16_t*)d.O; p.dO = (const bf16_t*)d.dO;
-    p.LSE = d.LSE; p.aux = d.delta; p.nq_pad = (Nq + 127) / 128 * 128;
+    p.LSE = d.LSE; p.aux = d.delta; p.nq_pad = (d.Nq + 127) / 128 * 128;
     p.dQ = (bf16_t*)d.dQ; p.dK = (bf16_t*)d.dK; p.dV = (bf16_t*)d.dV;
-    p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk;
+    p.B = d.B; p.H = d.H; p.Nq = d.Nq; p.Nk = d.Nk;
     p.q_sb = d.q_sb; p.q_sn = d.q_sn; p.q_sh = d.q_sh; p.k_sb = d.k_sb; p.k_sn = d.k_sn; p.k_sh = d.k_sh; p.v_sb = d.v_sb; p.v_sn = d.v_sn;
     p.v_sh = d.v_sh; p.o_sb = d.o_sb; p.o_sn = d.o_sn; p.o_sh = d.o_sh; p.dq_sb = d.dq_sb; p.dq_sn = d.dq_sn; p.dq_sh = d.dq_sh;
     p.dk_sb = d.dk_sb; p.dk_sn = d.dk_sn; p.dk_sh = d.dk_sh; p.dv_sb = d.dv_sb; p.dv_sn = d.dv_sn; p.dv_sh = d.dv_sh; p.scale = d.scale;
     hipStream_t st = (hipStream_t)stream;
     const dim3 gq(plan.dq_grid[0]), gkv(plan.dkv_grid[0]), block(plan.block);
-    if (plan.dq == UC_AWB_DQ_80) hipLaunchKernelGGL(attnw_bwd_dq_kernel<80>, gq, block, 0, st, p);
+    if (plan.dq == UC_AB_DQ80) hipLaunchKernelGGL(attnw_bwd_dq_kernel<80>, gq, block, 0, st, p);
     else hipLaunchKernelGGL(attnw_bwd_dq_kernel<96>, gq, block, 0, st, p);
-    if (plan.dkv == UC_AWB_DKV_80) hipLaunchKernelGGL(attnw_bwd_dkv_kernel<80>, gkv, block, 0, st, p);
+    if (plan.dkv == UC_AB_DKV80) hipLaunchKernelGGL(attnw_bwd_dkv_kernel<80>, gkv, block, 0, st, p);
     else hipLaunchKernelGGL(attnw_bwd_dkv_kernel<96>, gkv, block, 0, st, p);
-    UC_CHECK_LAUNCH(fn);
+    UC_CHECK_LAUNCH("uc_attention_bwd");
     return UC_OK;
 }

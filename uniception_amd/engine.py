@@ -655,19 +655,14 @@ def attention_route(dtype: torch.dtype, head_dim: int, native_rope: bool, qk_nor
       "wide"         bf16 at head_dim 80 / 96 (csrc/attention_wide.hip), with or without attention_precision("fp8") — fp8 has no wide
                      kernel: plain QKV GEMM(s) with bias, uc_vt_pack of V, uc_attention_fwd.  has_rope: the layer has a positional
                      encoding at all (native or not); the wide kernels have neither a RoPE nor a qk_norm form, and both raise.
-    The three fused routes need bf16 operands and head_dim 64; bf16 with a head_dim outside 64 / 80 / 96 has no kernel and raises."""
-    if dtype == torch.bfloat16 and head_dim in ops.WIDE_HEAD_DIMS:
-        if qk_norm:
-            raise UcHipError(f"qk_norm has no HIP path at head_dim {head_dim} in bf16 (head_dim 64 only); use fp32 precision for this model")
-        if has_rope or not native_rope:
-            raise UcHipError(f"RoPE has no HIP path at head_dim {head_dim} (the rotation kernels are head_dim 64); this model cannot run")
+    The three fused routes need bf16 operands and head_dim 64; what has no kernel raises (ops.attention_served states the served set)."""
+    ops.attention_served(dtype, head_dim, rope=has_rope or not native_rope, qk_norm=qk_norm)
+    if dtype == torch.bfloat16 and head_dim != 64:
         return "wide"
-    if dtype == torch.bfloat16 and head_dim == 64 and native_rope and not qk_norm and not separate_v:
+    if dtype == torch.bfloat16 and native_rope and not qk_norm and not separate_v:
         if _fp8_attention():
             return "fp8"
         return "vt_pack" if n_keys % 4 != 0 and VT_PACK_ODD else "vt_epilogue"
-    if dtype == torch.bfloat16 and head_dim != 64:
-        raise UcHipError(f"bf16 attention needs head_dim 64 (got {head_dim}); use fp32 precision for this model")
     return "unfused"
 
 

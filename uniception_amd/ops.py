@@ -593,6 +593,26 @@ def attention_fp8(q: torch.Tensor, k: torch.Tensor, vt8: torch.Tensor, scale: fl
 WIDE_HEAD_DIMS = (80, 96)
 
 
+def attention_served(dtype: torch.dtype, head_dim: int, dropout: bool = False, rope: bool = False, qk_norm: bool = False) -> None:
+    """The Python side's one statement of which attention the HIP kernels serve (the library's own is csrc/attention_plan.h): raises
+    UcHipError, naming the head_dim, for what has no kernel — so that a model is refused before any GEMM or pack is launched.
+    bf16 runs head_dim 64, and 80 / 96 on the wide-head kernels, which have no dropout, RoPE or qk_norm form; every other compute
+    dtype runs the fp32 kernels, head_dim <= 96.  Attention dropout exists at head_dim <= 64 only, in every dtype.
+    dropout: attention dropout is on.  rope: the layer has a positional encoding (a backward: inverse-RoPE positions).  qk_norm: the
+    layer normalises q / k."""
+    if dtype == torch.bfloat16 and head_dim != 64 and head_dim not in WIDE_HEAD_DIMS:
+        raise UcHipError(f"bf16 attention needs head_dim 64 (got {head_dim}), or 80 / 96 without dropout, RoPE and qk_norm; use fp32 precision for this model")
+    if dtype != torch.bfloat16 and head_dim > WIDE_HEAD_DIMS[-1]:
+        raise UcHipError(f"fp32 attention needs head_dim <= {WIDE_HEAD_DIMS[-1]} (got {head_dim})")
+    if dropout and head_dim > 64:
+        raise UcHipError(f"attn_drop > 0 has no HIP path at head_dim {head_dim} (attention dropout is head_dim <= 64 only)")
+    if dtype == torch.bfloat16 and head_dim > 64:
+        if qk_norm:
+            raise UcHipError(f"qk_norm has no HIP path at head_dim {head_dim} in bf16 (head_dim 64 only); use fp32 precision for this model")
+        if rope:
+            raise UcHipError(f"RoPE has no HIP path at head_dim {head_dim} (the rotation kernels are head_dim 64); this model cannot run in bf16")
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, v_packed: bool = False,
               out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None, dropout=None) -> torch.Tensor:
     """q [B,Nq,H,D], k [B,Nk,H,D] strided views (stride(3)==1); v same, or packed VT [B,H,D,Npad] when v_packed.
@@ -1082,10 +1102,9 @@ def attention_bwd(q, k, v, o, do, lse, scale: float, out=None, rope=None, dropou
     B, Nq, H, D = q.shape
     Nk = k.shape[1]
     dt = q.dtype
-    if not ((dt == torch.bfloat16 and D in (64,) + WIDE_HEAD_DIMS) or (dt == torch.float32 and D <= WIDE_HEAD_DIMS[-1])):
-        raise UcHipError(f"attention backward needs bf16 with head_dim 64, 80 or 96, or fp32 with head_dim <= 96 (got {D})")
-    if D > 64 and (rope is not None or (dropout is not None and float(dropout[0]) > 0.0)):
-        raise UcHipError(f"attention backward at head_dim {D}: the inverse RoPE and attention dropout exist at head_dim <= 64 only")
+    if dt not in (torch.bfloat16, torch.float32):
+        raise UcHipError(f"attention backward needs bf16 or fp32 operands (got {dt}, head_dim {D})")
+    attention_served(dt, D, dropout=dropout is not None and float(dropout[0]) > 0.0, rope=rope is not None)
     assert lse.dtype == torch.float32 and lse.is_contiguous()
     if do.stride() != o.stride() or o.stride(3) != 1:
         o, do = o.contiguous(), do.contiguous()
