@@ -103,6 +103,8 @@ int uc_rope_table(float* table, int npos, int Q, float base, float F0, uc_stream
  * LayerNorm over the last dim: y = (x-mean)/sqrt(var_biased+eps)*gamma+beta
  *   (nn.LayerNorm(eps=1e-6): encoders/croco.py:32, info_sharing/cross_attention_transformer.py:42).
  * x: [rows, C] (x_dtype f32|bf16), gamma/beta fp32 [C], y: [rows, C] (y_dtype f32|bf16).
+ * Any C, any element-aligned pointer; 16-byte alignment takes the vector kernels (C % 4 == 0, C <= 2048; widths 256*{1,2,3,4,6,8}
+ * the exact ones).  The routing is csrc/layernorm_plan.h.
  * ---------------------------------------------------------------------------------- */
 int uc_layernorm(const void* x, int x_dtype, const float* gamma, const float* beta, void* y,
                  int y_dtype, int64_t rows, int C, float eps, uc_stream_t stream);
@@ -440,7 +442,8 @@ int uc_assemble_prefix(const float* tok, const float* prefix, const float* pos, 
  *   dgamma[c] += sum_r dy*xhat, dbeta[c] += sum_r dy     (fp32 atomic accumulation: zero them first)
  *   dx_bf16 (optional, fp32 stream): a bf16 copy of dx written in the same pass — dx is the gradient of the residual stream, which
  *   the previous sub-layer's backward GEMMs consume in bf16.
- * Any C; widths 256*{1,2,3,4,6,8} take the register-resident kernel. */
+ * Any C, any element-aligned pointer; 16-byte alignment takes the vector kernels: widths 256*{1,2,3,4,6,8} the register-resident one,
+ * C = 64 without dres and dx_bf16 the four-rows-per-wave one.  The routing is csrc/layernorm_plan.h. */
 int uc_layernorm_bwd(const void* x, int x_dtype, const float* gamma, const void* dy, int dy_dtype, const void* dres, void* dx,
                      void* dx_bf16, float* dgamma, float* dbeta, int64_t rows, int C, float eps, uc_stream_t stream);
 

@@ -4,6 +4,7 @@
 // head either: kernels.cu:47-50 computes cos/sin once per (token, channel) and loops over heads).
 #include "vec_access.h"
 #include "knobs.h"
+#include "layernorm_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -125,7 +126,7 @@ extern "C" int uc_rope_table(float* table, int npos, int Q, float base, float F0
 // LayerNorm: one wavefront per row, row cached in registers (C <= 64*4*LN_MAXV), two-pass
 // mean/variance in fp32, 16-byte loads and stores.  4 rows per 256-thread workgroup.
 // ---------------------------------------------------------------------------------------
-#define LN_MAXV 8
+#define LN_MAXV UC_LN_MAXV   // layernorm_plan.h: the plan sends C <= 64 * 4 * LN_MAXV here
 
 // Exact-width variant: C == NV*256, no per-chunk predicates, so all NV 16-byte loads of a row are issued back to back
 // (the predicated generic kernel below serialises them behind exec-mask branches: 2.8 TB/s vs 7+ TB/s cache-hot).
@@ -259,28 +260,28 @@ static void launch_ln(const void* x, const float* g, const float* b, void* y, bf
                       float eps, hipStream_t st) {
     typedef typename TI::storage SI;
     typedef typename TO::storage SO;
-    const unsigned grid = (unsigned)ceil_div64(rows, 4);
-    const bool vec = (C % 4 == 0) && (C <= 64 * 4 * LN_MAXV) && ((uintptr_t)x % 16 == 0) &&
-                     ((uintptr_t)y % 16 == 0) && ((uintptr_t)twin % 8 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)b % 16 == 0) &&
-                     (((int64_t)C * sizeof(SI)) % (4 * sizeof(SI)) == 0);
-    const bool exact = vec && (C % 256 == 0);
-    const int nt_env = uc_knobs().ln_nt;
-    const bool nt = nt_env >= 0 ? nt_env != 0 : (rows * (int64_t)C * (int64_t)sizeof(SI) > ((int64_t)128 << 20));
+    const LnFwdPlan p = uc_ln_fwd_plan(rows, C, (int)sizeof(SI), (uintptr_t)x, (uintptr_t)y, (uintptr_t)twin, (uintptr_t)g, (uintptr_t)b,
+                                       uc_knobs().ln_nt);
+    const unsigned grid = p.grid;
 #define UC_LN_EXACT(NV_)                                                                                                          \
     do {                                                                                                                          \
-        if (nt) hipLaunchKernelGGL((layernorm_exact_kernel<TI, TO, NV_, true>), dim3(grid), dim3(256), 0, st, (const SI*)x, g, b,  \
-                                   (SO*)y, twin, rows, eps);                                                                      \
+        if (p.nt) hipLaunchKernelGGL((layernorm_exact_kernel<TI, TO, NV_, true>), dim3(grid), dim3(256), 0, st, (const SI*)x, g, b, \
+                                     (SO*)y, twin, rows, eps);                                                                    \
         else hipLaunchKernelGGL((layernorm_exact_kernel<TI, TO, NV_, false>), dim3(grid), dim3(256), 0, st, (const SI*)x, g, b,    \
                                 (SO*)y, twin, rows, eps);                                                                         \
     } while (0)
-    if (exact && C == 256) UC_LN_EXACT(1);
-    else if (exact && C == 512) UC_LN_EXACT(2);
-    else if (exact && C == 768) UC_LN_EXACT(3);
-    else if (exact && C == 1024) UC_LN_EXACT(4);
-    else if (exact && C == 1536) UC_LN_EXACT(6);
-    else if (exact && C == 2048) UC_LN_EXACT(8);
+    if (p.kernel == UC_LN_FWD_EXACT) {
+        switch (p.nv) {
+            case 1: UC_LN_EXACT(1); break;
+            case 2: UC_LN_EXACT(2); break;
+            case 3: UC_LN_EXACT(3); break;
+            case 4: UC_LN_EXACT(4); break;
+            case 6: UC_LN_EXACT(6); break;
+            default: UC_LN_EXACT(8); break;
+        }
+    }
 #undef UC_LN_EXACT
-    else if (vec)
+    else if (p.kernel == UC_LN_FWD_VEC)
         hipLaunchKernelGGL((layernorm_vec_kernel<TI, TO>), dim3(grid), dim3(256), 0, st, (const SI*)x, g, b,
                            (SO*)y, twin, rows, C, eps);
     else

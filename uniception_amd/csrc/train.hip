@@ -4,6 +4,7 @@
 // The reference has no hand-written backward (it is PyTorch autograd over the modules); each kernel cites the forward
 // expression it differentiates in include/uc_hip.h.
 #include "vec_access.h"
+#include "layernorm_plan.h"
 #include <algorithm>
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -236,10 +237,11 @@ extern "C" int uc_layernorm_bwd(const void* x, int x_dtype, const float* gamma, 
     UC_REQUIRE(x_dtype == UC_F32 || !dx_bf16, "uc_layernorm_bwd: a bf16 stream's dx is its own bf16 copy (dx_bf16 must be NULL)");
     if (rows == 0) return UC_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int nv = C / 256;
     const bool xb = x_dtype == UC_BF16;
-    if (C == 64 && !dres && !dx_bf16) {
-        const unsigned g64 = (unsigned)min((int64_t)1024, ceil_div64(rows, 16));
+    const LnBwdPlan p = uc_ln_bwd_plan(rows, C, dres != nullptr, dx_bf16 != nullptr, xb ? 2 : 4, dy_dtype == UC_BF16 ? 2 : 4, (uintptr_t)x,
+                                       (uintptr_t)dy, (uintptr_t)dres, (uintptr_t)dx, (uintptr_t)dx_bf16, (uintptr_t)gamma);
+    if (p.kernel == UC_LN_BWD_C64) {
+        const unsigned g64 = p.grid;
 #define UC_LN64(TD_, TX_)                                                                                                               \
         hipLaunchKernelGGL((layernorm64_bwd_kernel<TD_, TX_>), dim3(g64), dim3(256), 0, st, (const typename TX_::storage*)x, gamma,        \
                            (const typename TD_::storage*)dy, (typename TX_::storage*)dx, dgamma, dbeta, rows, eps)
@@ -249,8 +251,8 @@ extern "C" int uc_layernorm_bwd(const void* x, int x_dtype, const float* gamma, 
         UC_CHECK_LAUNCH("uc_layernorm_bwd");
         return UC_OK;
     }
-    if (C % 256 != 0 || !(nv == 1 || nv == 2 || nv == 3 || nv == 4 || nv == 6 || nv == 8)) {
-        const unsigned g = (unsigned)ceil_div64(rows, 4);
+    if (p.kernel == UC_LN_BWD_GENERIC) {
+        const unsigned g = p.grid;
 #define UC_LNG(TD_, TX_)                                                                                                                \
         hipLaunchKernelGGL((layernorm_bwd_generic_kernel<TD_, TX_>), dim3(g), dim3(256), 0, st, (const typename TX_::storage*)x, gamma,     \
                            (const typename TD_::storage*)dy, (const typename TX_::storage*)dres, (typename TX_::storage*)dx, dx_b, dgamma, dbeta, rows, C, eps)
@@ -260,12 +262,12 @@ extern "C" int uc_layernorm_bwd(const void* x, int x_dtype, const float* gamma, 
         UC_CHECK_LAUNCH("uc_layernorm_bwd");
         return UC_OK;
     }
-    const unsigned grid = (unsigned)min((int64_t)256, ceil_div64(rows, 8));
+    const unsigned grid = p.grid;
 #define UC_LNB(TD_, NV_, TX_)                                                                                                       \
     hipLaunchKernelGGL((layernorm_bwd_kernel<TD_, NV_, TX_>), dim3(grid), dim3(512), 0, st, (const typename TX_::storage*)x, gamma,      \
                        (const typename TD_::storage*)dy, (const typename TX_::storage*)dres, (typename TX_::storage*)dx, dx_b, dgamma, dbeta, rows, eps)
 #define UC_LNB_NV(TD_, TX_)                      \
-    switch (C / 256) {                           \
+    switch (p.nv) {                              \
         case 1: UC_LNB(TD_, 1, TX_); break;      \
         case 2: UC_LNB(TD_, 2, TX_); break;      \
         case 3: UC_LNB(TD_, 3, TX_); break;      \
