@@ -259,8 +259,7 @@ extern "C" int uc_conv1x1_to4_bwd(const void* feat, int dtype, const float* w, c
                                   int64_t npix, int Cin, int relu_mask, uc_stream_t stream) {
     UC_REQUIRE(feat && w && dout && dfeat && dw && db, "uc_conv1x1_to4_bwd: null pointer");
     UC_REQUIRE(npix > 0 && Cin > 0 && Cin <= 256 && Cin % 8 == 0, "uc_conv1x1_to4_bwd: Cin must be a multiple of 8 and <= 256");
-    const int lanes = 256 / (Cin / 8);
-    const unsigned grid = (unsigned)min((int64_t)2048, ceil_div64(npix, lanes));
+    const unsigned grid = uc_conv1x1_to4_bwd_grid(Cin, npix);      // stream_plan.h
     hipStream_t st = (hipStream_t)stream;
     UC_DISPATCH("uc_conv1x1_to4_bwd", dtype,
                 hipLaunchKernelGGL((conv1x1_to4_bwd_kernel<Tag>), dim3(grid), dim3(256), 0, st, (const Tag::storage*)feat, w, dout, (Tag::storage*)dfeat, dw, db, npix, Cin, relu_mask));

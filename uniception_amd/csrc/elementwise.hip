@@ -336,23 +336,23 @@ extern "C" int uc_bilinear_nhwc(const void* src, void* dst, int dtype, int B, in
     UC_REQUIRE(src && dst, "uc_bilinear_nhwc: null pointer");
     UC_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 8 == 0, "uc_bilinear_nhwc: bad shape (C must be a multiple of 8)");
     UC_REQUIRE(crop_h > 0 && crop_h <= Ho && crop_w > 0 && crop_w <= Wo, "uc_bilinear_nhwc: bad crop");
-    const float sy = Ho > 1 ? (float)(Hi - 1) / (float)(Ho - 1) : 0.f;
-    const float sx = Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f;
     UC_REQUIRE(crop_h <= 65535 && B <= 65535 && (int64_t)crop_w * (C / 8) < ((int64_t)1 << 31), "uc_bilinear_nhwc: shape exceeds the launch grid");
-    const dim3 grid((unsigned)(((int64_t)crop_w * (C / 8) + 255) / 256), (unsigned)crop_h, (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    const int rows2 = uc_knobs().bilinear_rows2;   // rows per work item of the upsampling form: 4 (default), 2, 0 = one-row kernel
-    // (bf16 only: the fp32 kernels are the verification path — its gradient fixtures sit on ReLU boundaries of the tiny test models,
+    // rows per work item of the upsampling form (UC_BILINEAR_ROWS2): 4 (default), 2, 0 = one-row kernel; the rule is stream_plan.h
+    // (16-bit only: the fp32 kernels are the verification path — its gradient fixtures sit on ReLU boundaries of the tiny test models,
     // where a 1e-7 change of the forward's rounding flips a mask and moves a small gradient tensor by 1e-3)
+    const BilinearPlan plan = uc_bilinear_plan(dtype, Hi, Ho, crop_h, crop_w, C, B, uc_knobs().bilinear_rows2);
+    const float sy = plan.sy, sx = uc_bilinear_scale(Wi, Wo);
+    const dim3 grid(plan.grid_x, plan.grid_y, plan.grid_z);
+    hipStream_t st = (hipStream_t)stream;
     // Instantiated for (bf16, 4 or 2 rows) and (fp16, 4 rows): these (dtype, rows) pairs are the specification, not a dtype dispatch.
-    if (rows2 && sy <= 0.5f && (dtype == UC_BF16 || dtype == UC_F16)) {
-#define UC_BL_ROWS(TAG, R)                                                                                                           \
-    hipLaunchKernelGGL((bilinear_rows_kernel<TAG, R>), dim3(grid.x, (unsigned)((crop_h + R - 1) / R), (unsigned)B), dim3(256), 0, st, \
-                       (const TAG::storage*)src, (TAG::storage*)dst, B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx)
-        if (dtype == UC_F16) UC_BL_ROWS(F16Tag, 4);
-        else if (rows2 == 4) UC_BL_ROWS(BF16Tag, 4);
-        else UC_BL_ROWS(BF16Tag, 2);
-#undef UC_BL_ROWS
+    if (plan.kernel == UC_BL_ROWS) {
+#define UC_BL_ROWS_LAUNCH(TAG, R)                                                                                 \
+    hipLaunchKernelGGL((bilinear_rows_kernel<TAG, R>), grid, dim3(256), 0, st, (const TAG::storage*)src, (TAG::storage*)dst, \
+                       B, Hi, Wi, C, Ho, Wo, crop_h, crop_w, sy, sx)
+        if (dtype == UC_F16) UC_BL_ROWS_LAUNCH(F16Tag, 4);
+        else if (plan.rows == 4) UC_BL_ROWS_LAUNCH(BF16Tag, 4);
+        else UC_BL_ROWS_LAUNCH(BF16Tag, 2);
+#undef UC_BL_ROWS_LAUNCH
         UC_CHECK_LAUNCH("uc_bilinear_nhwc");
         return UC_OK;
     }
@@ -519,18 +519,14 @@ __global__ __launch_bounds__(256) void conv1x1_to4_coop_kernel(const typename Ta
 }
 
 template <typename Tag>
-static bool launch_conv1x1_to4_coop(const void* feat, const float* w, const float* b, float* out, int64_t npix, int Cin, hipStream_t st) {
-    const int C8 = Cin / 8;
+static void launch_conv1x1_to4_coop(const Conv1x1Plan& plan, const void* feat, const float* w, const float* b, float* out, int64_t npix, hipStream_t st) {
 #define UC_C1X1(C8_)                                                                                                         \
-    case C8_: {                                                                                                              \
-        const unsigned grid = (unsigned)min((int64_t)65536, ceil_div64(npix, 256 / C8_));                                    \
-        hipLaunchKernelGGL((conv1x1_to4_coop_kernel<Tag, C8_>), dim3(grid), dim3(256), 0, st,                                \
+    case C8_:                                                                                                                \
+        hipLaunchKernelGGL((conv1x1_to4_coop_kernel<Tag, C8_>), dim3(plan.grid), dim3(256), 0, st,                           \
                            (const typename Tag::storage*)feat, w, b, out, npix);                                             \
-        return true;                                                                                                         \
-    }
-    switch (C8) {
+        break;
+    switch (plan.c8) {
         UC_C1X1(1) UC_C1X1(2) UC_C1X1(4) UC_C1X1(8) UC_C1X1(16) UC_C1X1(32)
-        default: return false;
     }
 #undef UC_C1X1
 }
@@ -540,11 +536,12 @@ extern "C" int uc_conv1x1_to4(const void* feat, int dtype, const float* w, const
     UC_REQUIRE(feat && w && b && out && npix > 0, "uc_conv1x1_to4: bad argument");
     UC_REQUIRE(Cin > 0 && Cin <= 256 && Cin % 8 == 0, "uc_conv1x1_to4: Cin must be a multiple of 8 and <= 256 (got %d)", Cin);
     hipStream_t st = (hipStream_t)stream;
-    bool coop = false;          // the coalesced form: a 16-byte aligned bias and Cin = 8 * 2^k
-    if ((uintptr_t)b % 16 == 0) UC_DISPATCH_F16("uc_conv1x1_to4", dtype, coop = launch_conv1x1_to4_coop<Tag>(feat, w, b, out, npix, Cin, st));
-    if (!coop)
+    const Conv1x1Plan plan = uc_conv1x1_to4_plan(Cin, (uintptr_t)b, npix);      // the coalesced form: a 16-byte aligned bias and Cin = 8 * 2^k
+    if (plan.kernel == UC_C1_COOP)
+        UC_DISPATCH_F16("uc_conv1x1_to4", dtype, launch_conv1x1_to4_coop<Tag>(plan, feat, w, b, out, npix, st));
+    else
         UC_DISPATCH_F16("uc_conv1x1_to4", dtype,
-                        hipLaunchKernelGGL((conv1x1_to4_kernel<Tag>), dim3(EW_GRID(npix)), dim3(256), 0, st, (const Tag::storage*)feat, w, b, out, npix, Cin));
+                        hipLaunchKernelGGL((conv1x1_to4_kernel<Tag>), dim3(plan.grid), dim3(256), 0, st, (const Tag::storage*)feat, w, b, out, npix, Cin));
     UC_CHECK_LAUNCH("uc_conv1x1_to4");
     return UC_OK;
 }

@@ -111,6 +111,7 @@ extern "C" int uc_tuning_get(const char* name, int* value) {
     else if (!strcmp(name, "conv_rows")) *value = g_uc_conv_rows.load();
     else if (!strcmp(name, "conv_rows_flat")) *value = g_uc_conv_rows_flat.load();
     else if (!strcmp(name, "small_m_split")) *value = g_uc_small_m_split.load();
+    else if (!strcmp(name, "bilinear_rows2")) *value = uc_knobs().bilinear_rows2;      // read-only: the environment's value, read once
     else { uc_set_error("uc_tuning_get: unknown knob '%s'", name); return UC_ERR_BAD_ARG; }
     return UC_OK;
 }

@@ -5,6 +5,7 @@
 //   float4_t / vec_load4 / vec_store4 : four consecutive elements, 16 bytes of fp32 or 8 of bf16 (F32Tag, BF16Tag)
 #pragma once
 #include "common.h"
+#include "stream_plan.h"
 
 struct Vec8 { float v[8]; };
 
@@ -74,8 +75,8 @@ template <> __device__ __forceinline__ void vec_store4<BF16Tag>(bf16_t* p, float
     *reinterpret_cast<uint2*>(p) = (uint2){pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)};
 }
 
-// grid of a grid-stride kernel with 256-thread workgroups
-#define EW_GRID(n_items) ((unsigned)min((int64_t)65536 * 4, ceil_div64((n_items), 256)))
+// grid of a grid-stride kernel with 256-thread workgroups (the cap: stream_plan.h)
+#define EW_GRID(n_items) uc_stream_grid((n_items), UC_STREAM_WG, UC_EW_GRID_CAP)
 
 // ---- one storage dtype chosen at run time ----------------------------------------------------------------------------------------
 // An entry point accepts {UC_F32, UC_BF16} (UC_DISPATCH) or {UC_F32, UC_BF16, UC_F16} (UC_DISPATCH_F16); which of the two is written
