@@ -68,8 +68,11 @@ const char* uc_last_error(void);
  *   21: the fused ViT stem of the Perception Encoder — uc_vit_stem, uc_vit_stem_bwd, uc_vit_stem_ws_bytes added (nothing existing
  *       changed).
  *   22: uc_attention_fwd / uc_attention_bwd take head_dim 80 and 96 in bf16 and head_dim <= 96 in fp32; uc_assemble_prefix
- *       added (nothing existing changed). */
-#define UC_ABI_VERSION 22
+ *       added (nothing existing changed).
+ *   23: the Cosmos image tokenizer's streaming passes — uc_haar_patch, uc_haar_unpatch, uc_group_norm_silu_nhwc (+ _bwd, two _ws_bytes queries),
+ *       uc_down2_gather (+ _bwd), uc_upsample2_nhwc (+ _bwd), uc_softmax_rows (+ _bwd) added; uc_transpose2d also takes f16 -> f16 (it
+ *       answered "unsupported dtypes" before); nothing else existing changed. */
+#define UC_ABI_VERSION 23
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -501,7 +504,8 @@ int uc_swiglu(const void* t, void* g, int dtype, int64_t M, int64_t H, uc_stream
  * s = sigmoid(x1); dg [M, H], t and dt [M, 2H]. */
 int uc_swiglu_bwd(const void* dg, const void* t, void* dt, int dtype, int64_t M, int64_t H, uc_stream_t stream);
 
-/* 2-D transpose src[R,S] -> dst[S, ld_dst] (row-major; f32->f32, bf16->bf16 or f32->bf16), used to put the reduction
+/* 2-D transpose src[R,S] -> dst[S, ld_dst] (row-major; f32->f32, bf16->bf16, f32->bf16 or, since ABI 23, f16->f16: v^T / k^T of the
+ * Cosmos head's wide attention under the fp16 head policy), used to put the reduction
  * dimension of the weight-gradient GEMMs (dW = dY^T X) on the contiguous axis.  ld_dst in [R, R+64): columns R..ld_dst-1
  * are written as zeros so the GEMM K dimension can be padded to a multiple of 64.  If rowmajor_copy != NULL the
  * converted (dst dtype) un-transposed [R,S] matrix is written there in the same pass. */
@@ -787,6 +791,58 @@ int64_t uc_vit_stem_ws_bytes(int64_t B, int64_t T, int64_t C);
 int uc_vit_stem_bwd(const void* dy, int dy_dtype, const void* tok, int tok_dtype, const float* cls, const float* pos, const float* gamma,
                     const float* stats, void* dtok, float* dcls, float* dpos, float* dgamma, float* dbeta, float* ws, int64_t B, int64_t hw, int C,
                     uc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Streaming passes of the Cosmos continuous image tokenizer (libs/cosmos_tokenizer/modules/patching.py, layers2d.py), csrc/cosmos.hip
+ * and csrc/groupnorm.hip.  They allocate nothing, use no atomics (every sum runs in one fixed order: the same bits on every run) and
+ * check every argument before anything is launched (UC_ERR_BAD_ARG, message prefixed with the function name).
+ *
+ *   uc_haar_patch:    the two-level Haar patcher in one pass.  img fp32 [B, C, H, W] (H % 4 == W % 4 == 0) -> rows [B, H/4, W/4, ld]
+ *                     in `dtype` (UC_F32 | UC_BF16 | UC_F16), ld >= 16 C, ld % 8 == 0.  Per level and channel, with x a 2x2 block
+ *                     (first index the row):  ll = (x00 + x01 + x10 + x11) / 4,  lh = (x00 + x01 - x10 - x11) / 4,
+ *                     hl = (x00 - x01 + x10 - x11) / 4,  hh = (x00 - x01 - x10 + x11) / 4, sub-band index s = 0..3 in that order;
+ *                     level 2 transforms every level-1 channel again:  rows[b, i, j, s2 4 C + s1 C + c], times `scale`.  Columns
+ *                     [16 C, ld) are written as zeros (the K padding of the GEMM that follows).  Each 4x4 block is read once, as
+ *                     four 16-byte loads; evaluated in fp32.
+ *   uc_haar_unpatch:  the exact inverse (x2 per level), times `scale`: rows [B, H/4, W/4, ld] in `dtype` -> img fp32 [B, C, H, W]; columns
+ *                     [16 C, ld) are not read.  The per-level matrix is symmetric and orthogonal up to a factor, so the adjoint of
+ *                     uc_haar_patch(scale = 1) is uc_haar_unpatch(scale = 1 / 16), and that of uc_haar_unpatch(scale = 1) is
+ *                     uc_haar_patch(scale = 16).
+ *   uc_group_norm_silu_nhwc:      uc_group_norm_nhwc with y = z sigmoid(z), z = (x - mean) rstd gamma + beta (the same statistics: chunk
+ *                     mean / M2, Chan merge, fp32).  Besides (C / G) % 8 == 0 it takes C / G == 4 (Normalize(128): 32 groups of 4).
+ *                     ws: uc_group_norm_silu_nhwc_ws_bytes.
+ *   uc_group_norm_silu_nhwc_bwd:  z is recomputed from x, mean, rstd, gamma, beta; g = dy s (1 + z (1 - s)), s = sigmoid(z), then the
+ *                     sums and dx of uc_group_norm_nhwc_bwd.  ws: uc_group_norm_silu_nhwc_bwd_ws_bytes.
+ *   uc_down2_gather:  operand rows of the tokenizer's Downsample (F.pad(0, 1, 0, 1) + 3x3 convolution, stride 2, no padding).
+ *                     x [B, H, W, C] (H, W even, C % 8 == 0) -> rows [B (H/2) (W/2), 9 C] with
+ *                     rows[(b, i, j)][(ky 3 + kx) C + c] = x[b, 2 i + ky, 2 j + kx, c], and 0 where 2 i + ky == H or 2 j + kx == W:
+ *                     the K order (ky, kx, c) of uc_gemm's convolution weights.
+ *   uc_down2_gather_bwd:  its adjoint, a gather: dx[b, y, x] = the sum of the at most four drows entries that read pixel (y, x), in the
+ *                     order (ky, kx) ascending.
+ *   uc_upsample2_nhwc:      y[b, 2 i + u, 2 j + v] = x[b, i, j], u, v in {0, 1} (nearest-neighbour x2); H, W: those of x.
+ *   uc_upsample2_nhwc_bwd:  dx[b, i, j] = ((dy[2i, 2j] + dy[2i, 2j+1]) + dy[2i+1, 2j]) + dy[2i+1, 2j+1], in fp32.
+ *   uc_softmax_rows:      P[r, :N] = softmax(scale S[r, :N]), S fp32 [rows, lds], P [rows, ldp] in `p_dtype`; columns [N, ldp) of P are
+ *                     written as zeros (the K padding of the product that follows).  One workgroup per row, one pass over S for rows
+ *                     of up to 4096 columns (held in registers), three for longer ones; row maximum and sum in fp32.  16-byte
+ *                     accesses when lds % 8 == 0, ldp % 8 == 0 and both bases are 16-byte aligned, scalar ones otherwise.  N >= 1.
+ *   uc_softmax_rows_bwd:  dS[r, :N] = scale P (dP - sum_n dP P), dS[r, N..ldp) = 0.  P, dS [rows, ldp] in `p_dtype`, dP fp32 [rows, lds].
+ * ---------------------------------------------------------------------------------- */
+int uc_haar_patch(const float* img, void* rows, int dtype, int B, int C, int H, int W, int ld, float scale, uc_stream_t stream);
+int uc_haar_unpatch(const void* rows, int dtype, float* img, int B, int C, int H, int W, int ld, float scale, uc_stream_t stream);
+int64_t uc_group_norm_silu_nhwc_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G);
+int64_t uc_group_norm_silu_nhwc_bwd_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G);
+int uc_group_norm_silu_nhwc(const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd, float* ws, int dtype,
+                            int B, int H, int W, int C, int G, float eps, uc_stream_t stream);
+int uc_group_norm_silu_nhwc_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                void* dx, float* dgamma, float* dbeta, float* ws, int dtype, int B, int H, int W, int C, int G,
+                                uc_stream_t stream);
+int uc_down2_gather(const void* x, void* rows, int dtype, int B, int H, int W, int C, uc_stream_t stream);
+int uc_down2_gather_bwd(const void* drows, void* dx, int dtype, int B, int H, int W, int C, uc_stream_t stream);
+int uc_upsample2_nhwc(const void* x, void* y, int dtype, int B, int H, int W, int C, uc_stream_t stream);
+int uc_upsample2_nhwc_bwd(const void* dy, void* dx, int dtype, int B, int H, int W, int C, uc_stream_t stream);
+int uc_softmax_rows(const float* S, int64_t lds, void* P, int p_dtype, int64_t ldp, int64_t rows, int64_t N, float scale, uc_stream_t stream);
+int uc_softmax_rows_bwd(const void* P, const float* dP, int64_t lds, void* dS, int p_dtype, int64_t ldp, int64_t rows, int64_t N, float scale,
+                        uc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -178,12 +178,24 @@ SIGNATURES = {
     "uc_vit_stem": [vp, i32, vp, vp, vp, vp, f32, vp, i32, vp, i64, i64, i32, vp],
     "uc_vit_stem_ws_bytes": [i64, i64, i64],
     "uc_vit_stem_bwd": [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, vp],
+    "uc_haar_patch": [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp],
+    "uc_haar_unpatch": [vp, i32, vp, i32, i32, i32, i32, i32, f32, vp],
+    "uc_group_norm_silu_nhwc_ws_bytes": [i64, i64, i64, i64, i64],
+    "uc_group_norm_silu_nhwc_bwd_ws_bytes": [i64, i64, i64, i64, i64],
+    "uc_group_norm_silu_nhwc": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp],
+    "uc_group_norm_silu_nhwc_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "uc_down2_gather": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "uc_down2_gather_bwd": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "uc_upsample2_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "uc_upsample2_nhwc_bwd": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "uc_softmax_rows": [vp, i64, vp, i32, i64, i64, i64, f32, vp],
+    "uc_softmax_rows_bwd": [vp, vp, i64, vp, i32, i64, i64, i64, f32, vp],
 }
 
 _lib = None
 
 
-ABI_VERSION = 22   # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 23  # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

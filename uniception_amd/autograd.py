@@ -2038,3 +2038,219 @@ def vit_stem(tok, cls, pos, ln, out_dtype=torch.float32):
         return VitStemFn.apply(tok, cls, pos, p[0], p[1], a[2] if a else 0.0, out_dtype)
     f = lambda t: None if t is None else (t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous())      # noqa: E731
     return ops.vit_stem(_c(tok), f(cls), f(pos), a, out_dtype)
+
+
+# =================================================================================================================
+# Cosmos continuous image tokenizer (libs/cosmos_tokenizer, encoders/cosmos.py, prediction_heads/cosmos.py): the Haar patcher and its
+# inverse, GroupNorm + SiLU, the stride-2 Downsample convolution as operand gather + dense GEMM, the nearest x2 upsample, and the
+# single-head attention over all pixels (head_dim 512) assembled from uc_gemm, the row softmax and uc_gemm_tn.
+# =================================================================================================================
+@_sink_aware
+class HaarPatchFn(Function):
+    "fp32 NCHW image -> NHWC two-level Haar coefficients (16 C channels, zero-padded to ld); the adjoint is the inverse / 16"
+
+    @staticmethod
+    def forward(ctx, img, dt, ld):
+        img = _c(img)
+        ctx.Cn = img.shape[1]
+        return ops.haar_patch(img if img.dtype == torch.float32 else img.float(), dt, ld)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.haar_unpatch(_c(dy), ctx.Cn, 1.0 / 16.0), None, None
+
+
+def haar_patch(img, dt, ld=None):
+    return HaarPatchFn.apply(img, dt, ld)
+
+
+@_sink_aware
+class HaarUnpatchFn(Function):
+    "NHWC coefficients [B, h, w, ld >= 16 Cn] -> fp32 NCHW image [B, Cn, 4h, 4w]; the adjoint is 16 x the patcher"
+
+    @staticmethod
+    def forward(ctx, rows, Cn):
+        rows = _c(rows)
+        ctx.meta = (rows.dtype, rows.shape[-1])
+        return ops.haar_unpatch(rows, Cn)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dt, ld = ctx.meta
+        return ops.haar_patch(_c(dy), dt, ld, 16.0), None
+
+
+def haar_unpatch(rows, Cn: int):
+    return HaarUnpatchFn.apply(rows, Cn)
+
+
+def check_group_size_silu(C: int, G: int, what: str = "group_norm_silu") -> None:
+    "what uc_group_norm_silu_nhwc would reject, said before any tensor is touched"
+    if G <= 0 or C % G != 0 or ((C // G) % 8 != 0 and C // G != 4):
+        raise UcHipError(f"{what}: {C} channels in {G} groups: channels per group ({C / max(G, 1):g}) must be a multiple of 8 or 4 "
+                         "(uc_group_norm_silu_nhwc)")
+
+
+@_sink_aware
+class GroupNormSiluFn(Function):
+    "y = silu(GroupNorm(x)) on an NHWC map; the backward recomputes the pre-activation from x"
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gn):
+        x = _c(x)
+        g, b = engine.ln_params(gn)
+        y, mean, rstd = ops.group_norm_silu_nhwc(x, g, b, gn.num_groups, gn.eps)
+        ctx.save_for_backward(x, g, b, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, g, b, mean, rstd = ctx.saved_tensors
+        dx, dg, db = ops.group_norm_silu_nhwc_bwd(_as_dt(_c(dy), x.dtype), x, mean, rstd, g, b)
+        return dx, dg, db, None
+
+
+def group_norm_silu(x, gn):
+    check_group_size_silu(x.shape[-1], gn.num_groups)
+    if gn.weight is None:
+        raise UcHipError("group_norm_silu: GroupNorm(affine=False) has no HIP path")
+    return GroupNormSiluFn.apply(x, gn.weight, gn.bias, gn)
+
+
+def _down2_weight(conv):
+    "fp32 [Cout, 9 Cin], K ordered (ky, kx, c)"
+    return conv.weight.detach().float().permute(0, 2, 3, 1).reshape(conv.out_channels, -1).contiguous()
+
+
+@_sink_aware
+class Down2ConvFn(Function):
+    """The tokenizer's Downsample: F.pad(x, (0, 1, 0, 1)) + Conv2d(k = 3, stride = 2, padding = 0) on an NHWC map, as operand rows
+    (uc_down2_gather) times the [Cout, 9 Cin] weight.  The backward regathers the rows for the weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, conv):
+        x = _c(x)
+        B, H, W, Cin = x.shape
+        w, b = engine.conv3x3_weights(conv, x.dtype)
+        ctx.save_for_backward(x)
+        ctx.meta = (conv, bias is not None)
+        return ops.gemm(ops.down2_gather(x), w, b).view(B, H // 2, W // 2, -1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        conv, has_b = ctx.meta
+        B, H, W, Cin = x.shape
+        dt = x.dtype
+        dy2 = _as_dt(_c(dy), dt).view(-1, conv.out_channels)
+        dWg, db = _wgrad(dy2, ops.down2_gather(x), dt, has_b)
+        dW = dWg.view(conv.out_channels, 3, 3, Cin).permute(0, 3, 1, 2)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            drows = ops.gemm(dy2, _w_t(conv, "down2", (conv.weight,), lambda: _down2_weight(conv), dt))
+            dx = ops.down2_gather_bwd(drows, B, H, W)
+        return dx, dW, db, None
+
+
+def down2_conv(x, conv):
+    if conv.kernel_size != (3, 3) or conv.stride != (2, 2) or conv.padding != (0, 0) or conv.dilation != (1, 1) or conv.groups != 1:
+        raise UcHipError("down2_conv: only the 3x3 / stride-2 / unpadded convolution of the tokenizer's Downsample has a HIP path")
+    if x.shape[1] % 2 or x.shape[2] % 2:
+        raise UcHipError(f"down2_conv: the Downsample of an odd map ({x.shape[1]} x {x.shape[2]}) has no HIP path")
+    return Down2ConvFn.apply(x, conv.weight, conv.bias, conv)
+
+
+@_sink_aware
+class Upsample2Fn(Function):
+    "nearest-neighbour x2 on an NHWC map; the adjoint sums every 2x2 block in a fixed order"
+
+    @staticmethod
+    def forward(ctx, x):
+        return ops.upsample2_nhwc(_c(x))
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.upsample2_nhwc_bwd(_c(dy))
+
+
+def upsample2(x):
+    return Upsample2Fn.apply(x)
+
+
+WIDE_ATTN_PANEL = 4096      # query rows per score panel: the fp32 score buffer holds at most PANEL x N_pad values
+
+
+def _wide_attn_operands(rows, N: int, C: int):
+    "(k, v zero-padded to a multiple of 64 rows, contiguous) of one sample's qkv rows [N, 3C]"
+    Np = head_pad(N)
+    kp = rows.new_zeros((Np, C))
+    vp = rows.new_zeros((Np, C))
+    kp[:N].copy_(rows[:, C:2 * C])
+    vp[:N].copy_(rows[:, 2 * C:])
+    return kp, vp, Np
+
+
+def _wide_attn_probs(q, kp, N: int, Np: int, scale: float):
+    "P [n, Np] (zeros beyond N) of one panel of query rows q [n, C]: S = q k^T (uc_gemm) -> row softmax"
+    s = ops.gemm(q, kp, out_dtype=torch.float32)
+    return ops.softmax_rows(s[:, :N], scale, q.dtype, out=torch.empty((q.shape[0], Np), dtype=q.dtype, device=q.device))
+
+
+@_sink_aware
+class WideAttentionFn(Function):
+    """softmax(q k^T scale) v with ONE head over all N pixels of a sample (head_dim = C = 512: beyond the fused kernels), assembled from
+    uc_gemm, uc_softmax_rows, uc_transpose2d and uc_gemm_tn per sample and per panel of at most `panel` query rows.  qkv: [B N, 3C]
+    rows (q | k | v).  P is NOT saved: the backward recomputes each panel's scores and probabilities (two launches) instead of keeping
+    B N^2 values alive."""
+
+    @staticmethod
+    def forward(ctx, qkv, B, N, scale, panel):
+        qkv = _c(qkv)
+        C = qkv.shape[1] // 3
+        o = torch.empty((B * N, C), dtype=qkv.dtype, device=qkv.device)
+        for b in range(B):
+            rows = qkv[b * N:(b + 1) * N]
+            kp, vp, Np = _wide_attn_operands(rows, N, C)
+            vt = ops.transpose2d(vp)                                   # [C, Np]
+            for r0 in range(0, N, panel):
+                r1 = min(N, r0 + panel)
+                p = _wide_attn_probs(rows[r0:r1, :C], kp, N, Np, scale)
+                ops.gemm(p, vt, out=o[b * N + r0:b * N + r1])
+        ctx.save_for_backward(qkv)
+        ctx.meta = (B, N, scale, panel)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        (qkv,) = ctx.saved_tensors
+        B, N, scale, panel = ctx.meta
+        C = qkv.shape[1] // 3
+        dt = qkv.dtype
+        do = _as_dt(_c(do), dt)
+        dqkv = torch.empty_like(qkv)
+        for b in range(B):
+            rows, drows = qkv[b * N:(b + 1) * N], dqkv[b * N:(b + 1) * N]
+            kp, vp, Np = _wide_attn_operands(rows, N, C)
+            kt = ops.transpose2d(kp)                                   # [C, Np]
+            dk = dv = None
+            for r0 in range(0, N, panel):
+                r1 = min(N, r0 + panel)
+                q, g = rows[r0:r1, :C], do[b * N + r0:b * N + r1]
+                p = _wide_attn_probs(q, kp, N, Np, scale)
+                dp = ops.gemm(g, vp, out_dtype=torch.float32)          # dP = dO v^T  [n, Np]
+                ds = ops.softmax_rows_bwd(p, dp[:, :N], N, scale)      # [n, Np], zeros beyond N
+                ops.gemm(ds, kt, out=drows[r0:r1, :C])                 # dQ = dS k
+                dvp, dkp = _wgrad(p, g, dt)[0], _wgrad(ds, q, dt)[0]   # dV = P^T dO, dK = dS^T q  [Np, C] fp32
+                dv, dk = (dvp, dkp) if dv is None else (dv + dvp, dk + dkp)      # (panels in ascending order)
+            drows[:, C:2 * C].copy_(dk[:N])
+            drows[:, 2 * C:].copy_(dv[:N])
+        return dqkv, None, None, None, None
+
+
+def wide_attention(qkv, B: int, N: int, scale: float, panel: int = WIDE_ATTN_PANEL):
+    "single-head attention over all pixels: qkv [B N, 3C] -> [B N, C] (WideAttentionFn); panel: query rows per score panel"
+    if qkv.dim() != 2 or qkv.shape[0] != B * N or qkv.shape[1] % 3 != 0 or (qkv.shape[1] // 3) % 64 != 0:
+        raise UcHipError(f"wide_attention: qkv {tuple(qkv.shape)} is not [B N, 3C] with C a multiple of 64 (B={B}, N={N})")
+    if panel < 1:
+        raise UcHipError(f"wide_attention: panel={panel}")
+    return WideAttentionFn.apply(qkv, B, N, float(scale), int(panel))

@@ -1,5 +1,6 @@
 // GroupNorm on channels-last maps (the ResidualConvBlocks of the MoGe head: nn.GroupNorm + ReLU in front of every 3x3 convolution)
-// and its backward.  x [B, H, W, C], G groups of C / G contiguous channels, (C / G) % 8 == 0.
+// and its backward.  x [B, H, W, C], G groups of C / G contiguous channels, (C / G) % 8 == 0.  The SiLU entry points (the Cosmos
+// tokenizer's Normalize(128): 32 groups of 4) also take C / G == 4: a work item then spans two groups, its low and its high half.
 //
 // Work item = 8 consecutive channels of one pixel (vec_access.h).  A workgroup of 256 threads is laid out as `rows` pixels x C / 8
 // channel vectors (rows = 256 / (C / 8)), so consecutive lanes read consecutive 16-byte pieces: a wave load covers whole pixel rows.
@@ -9,8 +10,9 @@
 //     chunk mean, then the squared deviations from THAT mean (a true two-pass over registers: nothing cancels) and stores
 //     (mean, M2) per (sample, chunk, group).  gn_stats_finalize merges the chunks with Chan's formula: one wave per (sample, group),
 //     a lane merges chunks lane, lane + 64, ... in ascending order, the lanes are merged in a fixed butterfly.  No atomics.
-//   apply: y = act((x - mean) rstd gamma + beta), a second kernel.
-//   backward: per (sample, chunk, channel) partials of sum g x^ and sum g (g = dy, gated by y > 0 under a fused ReLU); a per-sample
+//   apply: y = act((x - mean) rstd gamma + beta), a second kernel; act = none | ReLU | SiLU (the Cosmos tokenizer's Normalize + swish).
+//   backward: per (sample, chunk, channel) partials of sum g x^ and sum g (g = dy, gated by y > 0 under a fused ReLU, times silu'(z)
+//     with z recomputed from x under a fused SiLU); a per-sample
 //     kernel adds the chunks in a fixed order (four interleaved chains, combined in chain order) and forms the two group sums
 //     sum g gamma and sum g gamma x^ from the per-channel sums (they are gamma-weighted sums of those); a third adds the samples for
 //     dgamma / dbeta; the fourth writes dx.  Fixed order everywhere: two calls give the same bits.
@@ -22,7 +24,10 @@
 
 struct GnGeom {
     int HW, C, G, C8, cg8, rows, chunk_pix, nchunk;
+    int cg, half;      // channels per group; half: cg == 4, the two halves of an 8-channel vector belong to groups 2 c8 and 2 c8 + 1
 };
+// group of half `hi` (0: channels 0..3, 1: channels 4..7) of channel vector c8
+__host__ __device__ __forceinline__ int gn_group(const GnGeom& gm, int c8, int hi) { return gm.half ? 2 * c8 + hi : c8 / gm.cg8; }
 
 static inline GnGeom gn_geom(int64_t H, int64_t W, int64_t C, int64_t G) {
     GnGeom g;
@@ -31,6 +36,8 @@ static inline GnGeom gn_geom(int64_t H, int64_t W, int64_t C, int64_t G) {
     g.G = (int)G;
     g.C8 = (int)(C / 8);
     g.cg8 = (int)(C / G / 8);
+    g.cg = (int)(C / G);
+    g.half = g.cg == 4;
     g.rows = GN_THREADS / g.C8;
     g.chunk_pix = g.rows * GN_VECS;
     g.nchunk = (g.HW + g.chunk_pix - 1) / g.chunk_pix;
@@ -103,6 +110,57 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_partial_kernel(const type
     if (tid < gm.G) part[(b * gm.nchunk + chunk) * gm.G + tid] = make_float2(s_sum[tid] / cnt, s_m2[tid]);
 }
 
+// the same for groups of 4 channels (gm.half): the workgroup reduction runs once per half, over single channel vectors
+template <typename Tag>
+__global__ __launch_bounds__(GN_THREADS) void gn_stats_partial4_kernel(const typename Tag::storage* __restrict__ x, float2* __restrict__ part,
+                                                                       GnGeom gm) {
+    __shared__ float s_thr[GN_THREADS], s_col[GN_THREADS], s_sum[2][GN_THREADS], s_m2[2][GN_THREADS];
+    const int tid = threadIdx.x;
+    const int C8 = gm.C8, rows = gm.rows;
+    const bool active = tid < rows * C8;
+    const int r = tid / C8, c8 = tid - r * C8;
+    const int chunk = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    const int p0 = chunk * gm.chunk_pix;
+    const int npix = min(gm.chunk_pix, gm.HW - p0);
+    const typename Tag::storage* base = x + ((b * gm.HW + p0) * (int64_t)gm.C) + c8 * 8;
+    Vec8 v[GN_VECS];
+    float s[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < GN_VECS; ++j) {
+        const int p = j * rows + r;
+        if (active && p < npix) {
+            v[j] = vec_load8<Tag>(base + (int64_t)p * gm.C);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e >> 2] += v[j].v[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[j].v[e] = 0.f;
+        }
+    }
+    const float cnt = (float)npix * 4.f;
+    float mean[2], q[2] = {0.f, 0.f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        gn_group_reduce(active ? s[h] : 0.f, s_thr, s_col, s_sum[h], tid, C8, rows, 1, C8);
+        mean[h] = active ? s_sum[h][c8] / cnt : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < GN_VECS; ++j) {
+        const int p = j * rows + r;
+        if (active && p < npix) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d = v[j].v[e] - mean[e >> 2];
+                q[e >> 2] = fmaf(d, d, q[e >> 2]);
+            }
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) gn_group_reduce(active ? q[h] : 0.f, s_thr, s_col, s_m2[h], tid, C8, rows, 1, C8);
+    for (int g = tid; g < gm.G; g += GN_THREADS) part[(b * gm.nchunk + chunk) * gm.G + g] = make_float2(s_sum[g & 1][g >> 1] / cnt, s_m2[g & 1][g >> 1]);
+}
+
 // Chan et al.: (na, ma, Ma) + (nb, mb, Mb).  The element counts are carried in double: exact for any map the grid limits admit
 // (a float count is inexact above 2^24 elements per (sample, group), e.g. 518 x 518 x 64 with G = 1).
 __device__ __forceinline__ void gn_merge(double& na, float& ma, float& Ma, double nb, float mb, float Mb) {
@@ -120,7 +178,7 @@ __global__ __launch_bounds__(64) void gn_stats_finalize_kernel(const float2* __r
     const int lane = threadIdx.x;
     const int64_t b = blockIdx.x / gm.G;
     const int g = blockIdx.x - (int)b * gm.G;
-    const double cg = (double)(gm.cg8 * 8);
+    const double cg = (double)gm.cg;
     double n = 0.0;
     float mu = 0.f, m2 = 0.f;
     for (int k = lane; k < gm.nchunk; k += 64) {
@@ -145,8 +203,16 @@ __global__ __launch_bounds__(64) void gn_stats_finalize_kernel(const float2* __r
     }
 }
 
+enum { GN_ACT_NONE = 0, GN_ACT_RELU = 1, GN_ACT_SILU = 2 };
+
+// silu'(z) = s (1 + z (1 - s)), s = sigmoid(z)
+__device__ __forceinline__ float gn_silu_grad(float z) {
+    const float sg = 1.f / (1.f + expf(-z));
+    return sg * fmaf(z, 1.f - sg, 1.f);
+}
+
 // one thread per (pixel, 8 channels)
-template <typename Tag, bool RELU>
+template <typename Tag, int ACT>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const typename Tag::storage* __restrict__ x, typename Tag::storage* __restrict__ y,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        const float* __restrict__ mean, const float* __restrict__ rstd, int64_t items,
@@ -155,26 +221,28 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const typename Tag::stora
     if (it >= items) return;
     const int64_t b = it / per_sample;
     const int c8 = (int)((it - b * per_sample) % gm.C8);
-    const int sg = (int)b * gm.G + c8 / gm.cg8;
-    const float mu = mean[sg], rs = rstd[sg];
+    const int sg[2] = {(int)b * gm.G + gn_group(gm, c8, 0), (int)b * gm.G + gn_group(gm, c8, 1)};
+    const float mu[2] = {mean[sg[0]], mean[sg[1]]}, rs[2] = {rstd[sg[0]], rstd[sg[1]]};
     const Vec8 ga = vec_load8<F32Tag>(gamma + c8 * 8), be = vec_load8<F32Tag>(beta + c8 * 8);
     const Vec8 v = vec_load8<Tag>(x + it * 8);
     Vec8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float t = fmaf((v.v[e] - mu) * rs, ga.v[e], be.v[e]);
-        o.v[e] = RELU ? fmaxf(t, 0.f) : t;
+        const float t = fmaf((v.v[e] - mu[e >> 2]) * rs[e >> 2], ga.v[e], be.v[e]);
+        o.v[e] = ACT == GN_ACT_RELU ? fmaxf(t, 0.f) : ACT == GN_ACT_SILU ? t / (1.f + expf(-t)) : t;
     }
     vec_store8<Tag>(y + it * 8, o);
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------------
 // grid (chunk, sample); part [B][nchunk][2][C]: [0] = sum g x^, [1] = sum g over the chunk's pixels, per channel
-template <typename Tag, bool GATE>
+// ACT: GN_ACT_RELU gates dy by gate > 0 (gate = the forward's y); GN_ACT_SILU multiplies it by silu'(z), z from x, gamma, beta
+template <typename Tag, int ACT>
 __global__ __launch_bounds__(GN_THREADS) void gn_bwd_partial_kernel(const typename Tag::storage* __restrict__ dy,
                                                                     const typename Tag::storage* __restrict__ x,
                                                                     const typename Tag::storage* __restrict__ gate,
                                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                     float* __restrict__ part, GnGeom gm) {
     __shared__ float s[16][GN_THREADS];
     const int tid = threadIdx.x;
@@ -189,9 +257,11 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_partial_kernel(const typena
 #pragma unroll
     for (int e = 0; e < 8; ++e) a[e] = bs[e] = 0.f;
     if (active) {
-        const int sg = (int)b * gm.G + c8 / gm.cg8;
-        const float mu = mean[sg], rs = rstd[sg];
+        const int sg[2] = {(int)b * gm.G + gn_group(gm, c8, 0), (int)b * gm.G + gn_group(gm, c8, 1)};
+        const float mu[2] = {mean[sg[0]], mean[sg[1]]}, rs[2] = {rstd[sg[0]], rstd[sg[1]]};
         const int64_t off = ((b * gm.HW + p0) * (int64_t)gm.C) + c8 * 8;
+        Vec8 ga, be;
+        if (ACT == GN_ACT_SILU) { ga = vec_load8<F32Tag>(gamma + c8 * 8); be = vec_load8<F32Tag>(beta + c8 * 8); }
 #pragma unroll 4
         for (int j = 0; j < GN_VECS; ++j) {
             const int p = j * rows + r;
@@ -199,14 +269,18 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_partial_kernel(const typena
                 const int64_t o = off + (int64_t)p * gm.C;
                 Vec8 g = vec_load8<Tag>(dy + o);
                 const Vec8 xv = vec_load8<Tag>(x + o);
-                if (GATE) {
+                if (ACT == GN_ACT_RELU) {
                     const Vec8 yv = vec_load8<Tag>(gate + o);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) g.v[e] = yv.v[e] > 0.f ? g.v[e] : 0.f;
                 }
+                if (ACT == GN_ACT_SILU) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) g.v[e] *= gn_silu_grad(fmaf((xv.v[e] - mu[e >> 2]) * rs[e >> 2], ga.v[e], be.v[e]));
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    a[e] = fmaf(g.v[e], (xv.v[e] - mu) * rs, a[e]);
+                    a[e] = fmaf(g.v[e], (xv.v[e] - mu[e >> 2]) * rs[e >> 2], a[e]);
                     bs[e] += g.v[e];
                 }
             }
@@ -257,7 +331,7 @@ __global__ __launch_bounds__(256) void gn_bwd_finalize_kernel(const float* __res
         }
         __syncthreads();
     }
-    const int cg = gm.cg8 * 8;
+    const int cg = gm.cg;
     for (int g = tid; g < gm.G; g += 256) {
         float s1 = 0.f, s2 = 0.f;
         for (int k = 0; k < cg; ++k) { s1 += gs[0][g * cg + k]; s2 += gs[1][g * cg + k]; }
@@ -277,42 +351,48 @@ __global__ __launch_bounds__(256) void gn_bwd_params_kernel(const float* __restr
     (which ? dbeta : dgamma)[c] = t;
 }
 
-template <typename Tag, bool GATE>
+template <typename Tag, int ACT>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const typename Tag::storage* __restrict__ dy, const typename Tag::storage* __restrict__ x,
                                                            const typename Tag::storage* __restrict__ gate, const float* __restrict__ mean,
                                                            const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                           const float* __restrict__ S, typename Tag::storage* __restrict__ dx, int64_t items,
+                                                           const float* __restrict__ beta, const float* __restrict__ S, typename Tag::storage* __restrict__ dx, int64_t items,
                                                            int64_t per_sample, float inv_m, GnGeom gm) {
     const int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (it >= items) return;
     const int64_t b = it / per_sample;
     const int c8 = (int)((it - b * per_sample) % gm.C8);
-    const int sg = (int)b * gm.G + c8 / gm.cg8;
-    const float mu = mean[sg], rs = rstd[sg];
-    const float s1 = S[sg * 2] * inv_m, s2 = S[sg * 2 + 1] * inv_m;
+    const int sg[2] = {(int)b * gm.G + gn_group(gm, c8, 0), (int)b * gm.G + gn_group(gm, c8, 1)};
+    const float mu[2] = {mean[sg[0]], mean[sg[1]]}, rs[2] = {rstd[sg[0]], rstd[sg[1]]};
+    const float s1[2] = {S[sg[0] * 2] * inv_m, S[sg[1] * 2] * inv_m}, s2[2] = {S[sg[0] * 2 + 1] * inv_m, S[sg[1] * 2 + 1] * inv_m};
     const Vec8 ga = vec_load8<F32Tag>(gamma + c8 * 8);
     Vec8 g = vec_load8<Tag>(dy + it * 8);
     const Vec8 xv = vec_load8<Tag>(x + it * 8);
-    if (GATE) {
+    if (ACT == GN_ACT_RELU) {
         const Vec8 yv = vec_load8<Tag>(gate + it * 8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) g.v[e] = yv.v[e] > 0.f ? g.v[e] : 0.f;
     }
+    if (ACT == GN_ACT_SILU) {
+        const Vec8 be = vec_load8<F32Tag>(beta + c8 * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g.v[e] *= gn_silu_grad(fmaf((xv.v[e] - mu[e >> 2]) * rs[e >> 2], ga.v[e], be.v[e]));
+    }
     Vec8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float xh = (xv.v[e] - mu) * rs;
-        o.v[e] = rs * ((g.v[e] * ga.v[e] - s1) - xh * s2);
+        const float xh = (xv.v[e] - mu[e >> 2]) * rs[e >> 2];
+        o.v[e] = rs[e >> 2] * ((g.v[e] * ga.v[e] - s1[e >> 2]) - xh * s2[e >> 2]);
     }
     vec_store8<Tag>(dx + it * 8, o);
 }
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------------
-static int gn_check_shape(const char* fn, int dtype, int B, int H, int W, int C, int G) {
+// group4: groups of 4 channels are accepted too (the SiLU entry points)
+static int gn_check_shape(const char* fn, int dtype, int B, int H, int W, int C, int G, bool group4 = false) {
     UC_REQUIRE_DTYPE(fn, dtype, true);
     UC_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && G > 0, "%s: bad shape B=%d H=%d W=%d C=%d G=%d", fn, B, H, W, C, G);
     UC_REQUIRE(C % G == 0, "%s: C (%d) is not a multiple of G (%d)", fn, C, G);
-    UC_REQUIRE((C / G) % 8 == 0, "%s: channels per group (%d) must be a multiple of 8", fn, C / G);
+    UC_REQUIRE((C / G) % 8 == 0 || (group4 && C / G == 4), "%s: channels per group (%d) must be a multiple of 8%s", fn, C / G, group4 ? " (or 4)" : "");
     UC_REQUIRE(C <= GN_MAX_C, "%s: C (%d) exceeds %d", fn, C, GN_MAX_C);
     UC_REQUIRE(B <= 65535 && (int64_t)H * W <= 0x7fffffff && (int64_t)B * G <= 0x7fffffff &&
                    ((int64_t)B * H * W * (C / 8) + 255) / 256 <= 0x7fffffff,
@@ -320,17 +400,27 @@ static int gn_check_shape(const char* fn, int dtype, int B, int H, int W, int C,
     return UC_OK;
 }
 
-extern "C" int64_t uc_group_norm_nhwc_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || G <= 0 || C % G || (C / G) % 8 || C > GN_MAX_C) return 0;
-    const GnGeom gm = gn_geom(H, W, C, G);
-    return B * (int64_t)gm.nchunk * G * (int64_t)sizeof(float2);
+static bool gn_shape_ok(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G, bool group4) {
+    return B > 0 && H > 0 && W > 0 && C > 0 && G > 0 && C % G == 0 && ((C / G) % 8 == 0 || (group4 && C / G == 4)) && C <= GN_MAX_C;
+}
+static int64_t gn_fwd_ws(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
+    return B * (int64_t)gn_geom(H, W, C, G).nchunk * G * (int64_t)sizeof(float2);
+}
+static int64_t gn_bwd_ws(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
+    return (B * (int64_t)gn_geom(H, W, C, G).nchunk * 2 * C + B * 2 * C + B * G * 2) * (int64_t)sizeof(float);
 }
 
-extern "C" int uc_group_norm_nhwc(const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd, float* ws,
-                                  int dtype, int B, int H, int W, int C, int G, float eps, int relu, uc_stream_t stream) {
-    const char* fn = "uc_group_norm_nhwc";
+extern "C" int64_t uc_group_norm_nhwc_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
+    return gn_shape_ok(B, H, W, C, G, false) ? gn_fwd_ws(B, H, W, C, G) : 0;
+}
+extern "C" int64_t uc_group_norm_silu_nhwc_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
+    return gn_shape_ok(B, H, W, C, G, true) ? gn_fwd_ws(B, H, W, C, G) : 0;
+}
+
+static int gn_forward(const char* fn, const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd, float* ws,
+                      int dtype, int B, int H, int W, int C, int G, float eps, int act, uc_stream_t stream) {
     UC_REQUIRE(x && y && gamma && beta && mean && rstd && ws, "%s: null pointer", fn);
-    if (int e = gn_check_shape(fn, dtype, B, H, W, C, G)) return e;
+    if (int e = gn_check_shape(fn, dtype, B, H, W, C, G, act == GN_ACT_SILU)) return e;
     UC_REQUIRE(eps > 0.f, "%s: eps must be positive", fn);
     UC_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)gamma % 16 == 0 && (uintptr_t)beta % 16 == 0 &&
                    (uintptr_t)ws % 8 == 0 && (uintptr_t)mean % 4 == 0 && (uintptr_t)rstd % 4 == 0,
@@ -338,34 +428,52 @@ extern "C" int uc_group_norm_nhwc(const void* x, void* y, const float* gamma, co
     const GnGeom gm = gn_geom(H, W, C, G);
     hipStream_t st = (hipStream_t)stream;
     const dim3 pgrid((unsigned)gm.nchunk, (unsigned)B);
-    UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL(gn_stats_partial_kernel<Tag>, pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)x, (float2*)ws, gm));
+    if (gm.half)
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL(gn_stats_partial4_kernel<Tag>, pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)x, (float2*)ws, gm));
+    else
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL(gn_stats_partial_kernel<Tag>, pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)x, (float2*)ws, gm));
     UC_CHECK_LAUNCH(fn);
     hipLaunchKernelGGL(gn_stats_finalize_kernel, dim3((unsigned)(B * G)), dim3(64), 0, st, (const float2*)ws, mean, rstd, gm, eps);
     UC_CHECK_LAUNCH(fn);
     const int64_t per_sample = (int64_t)gm.HW * gm.C8, items = per_sample * B;
     const dim3 agrid((unsigned)((items + 255) / 256));
-    if (relu)
-        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_apply_kernel<Tag, true>), agrid, dim3(256), 0, st, (const Tag::storage*)x, (Tag::storage*)y, gamma, beta,
+    if (act == GN_ACT_SILU)
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_apply_kernel<Tag, GN_ACT_SILU>), agrid, dim3(256), 0, st, (const Tag::storage*)x, (Tag::storage*)y, gamma, beta,
+                                              (const float*)mean, (const float*)rstd, items, per_sample, gm));
+    else if (act == GN_ACT_RELU)
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_apply_kernel<Tag, GN_ACT_RELU>), agrid, dim3(256), 0, st, (const Tag::storage*)x, (Tag::storage*)y, gamma, beta,
                                               (const float*)mean, (const float*)rstd, items, per_sample, gm));
     else
-        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_apply_kernel<Tag, false>), agrid, dim3(256), 0, st, (const Tag::storage*)x, (Tag::storage*)y, gamma, beta,
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_apply_kernel<Tag, GN_ACT_NONE>), agrid, dim3(256), 0, st, (const Tag::storage*)x, (Tag::storage*)y, gamma, beta,
                                               (const float*)mean, (const float*)rstd, items, per_sample, gm));
     UC_CHECK_LAUNCH(fn);
     return UC_OK;
 }
 
-extern "C" int64_t uc_group_norm_nhwc_bwd_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
-    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || G <= 0 || C % G || (C / G) % 8 || C > GN_MAX_C) return 0;
-    const GnGeom gm = gn_geom(H, W, C, G);
-    return (B * (int64_t)gm.nchunk * 2 * C + B * 2 * C + B * G * 2) * (int64_t)sizeof(float);
+extern "C" int uc_group_norm_nhwc(const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd, float* ws,
+                                  int dtype, int B, int H, int W, int C, int G, float eps, int relu, uc_stream_t stream) {
+    return gn_forward("uc_group_norm_nhwc", x, y, gamma, beta, mean, rstd, ws, dtype, B, H, W, C, G, eps, relu ? GN_ACT_RELU : GN_ACT_NONE, stream);
 }
 
-extern "C" int uc_group_norm_nhwc_bwd(const void* dy, const void* x, const void* gate, const float* mean, const float* rstd,
-                                      const float* gamma, void* dx, float* dgamma, float* dbeta, float* ws, int dtype, int B, int H, int W,
-                                      int C, int G, uc_stream_t stream) {
-    const char* fn = "uc_group_norm_nhwc_bwd";
+extern "C" int uc_group_norm_silu_nhwc(const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd, float* ws,
+                                       int dtype, int B, int H, int W, int C, int G, float eps, uc_stream_t stream) {
+    return gn_forward("uc_group_norm_silu_nhwc", x, y, gamma, beta, mean, rstd, ws, dtype, B, H, W, C, G, eps, GN_ACT_SILU, stream);
+}
+
+extern "C" int64_t uc_group_norm_nhwc_bwd_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
+    return gn_shape_ok(B, H, W, C, G, false) ? gn_bwd_ws(B, H, W, C, G) : 0;
+}
+extern "C" int64_t uc_group_norm_silu_nhwc_bwd_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
+    return gn_shape_ok(B, H, W, C, G, true) ? gn_bwd_ws(B, H, W, C, G) : 0;
+}
+
+// beta != NULL: the fused SiLU's backward (gate unused); gate != NULL: the fused ReLU's
+static int gn_backward(const char* fn, const void* dy, const void* x, const void* gate, const float* mean, const float* rstd,
+                       const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta, float* ws, int dtype, int B, int H, int W,
+                       int C, int G, uc_stream_t stream) {
     UC_REQUIRE(dy && x && mean && rstd && gamma && dx && dgamma && dbeta && ws, "%s: null pointer", fn);
-    if (int e = gn_check_shape(fn, dtype, B, H, W, C, G)) return e;
+    UC_REQUIRE(!beta || (uintptr_t)beta % 16 == 0, "%s: beta must be 16-byte aligned", fn);
+    if (int e = gn_check_shape(fn, dtype, B, H, W, C, G, beta != nullptr)) return e;
     UC_REQUIRE((uintptr_t)dy % 16 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)dx % 16 == 0 && (uintptr_t)gamma % 16 == 0 &&
                    (!gate || (uintptr_t)gate % 16 == 0) && (uintptr_t)ws % 4 == 0 && (uintptr_t)dgamma % 4 == 0 && (uintptr_t)dbeta % 4 == 0 &&
                    (uintptr_t)mean % 4 == 0 && (uintptr_t)rstd % 4 == 0,
@@ -376,12 +484,15 @@ extern "C" int uc_group_norm_nhwc_bwd(const void* dy, const void* x, const void*
     float* pc = part + (int64_t)B * gm.nchunk * 2 * C;
     float* S = pc + (int64_t)B * 2 * C;
     const dim3 pgrid((unsigned)gm.nchunk, (unsigned)B);
-    if (gate)
-        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_partial_kernel<Tag, true>), pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
-                                              (const Tag::storage*)gate, mean, rstd, part, gm));
+    if (beta)
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_partial_kernel<Tag, GN_ACT_SILU>), pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
+                                              (const Tag::storage*)nullptr, mean, rstd, gamma, beta, part, gm));
+    else if (gate)
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_partial_kernel<Tag, GN_ACT_RELU>), pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
+                                              (const Tag::storage*)gate, mean, rstd, gamma, beta, part, gm));
     else
-        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_partial_kernel<Tag, false>), pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
-                                              (const Tag::storage*)nullptr, mean, rstd, part, gm));
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_partial_kernel<Tag, GN_ACT_NONE>), pgrid, dim3(GN_THREADS), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
+                                              (const Tag::storage*)nullptr, mean, rstd, gamma, beta, part, gm));
     UC_CHECK_LAUNCH(fn);
     hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3((unsigned)B), dim3(256), 0, st, (const float*)part, gamma, pc, S, gm);
     UC_CHECK_LAUNCH(fn);
@@ -389,13 +500,30 @@ extern "C" int uc_group_norm_nhwc_bwd(const void* dy, const void* x, const void*
     UC_CHECK_LAUNCH(fn);
     const int64_t per_sample = (int64_t)gm.HW * gm.C8, items = per_sample * B;
     const dim3 agrid((unsigned)((items + 255) / 256));
-    const float inv_m = (float)(1.0 / ((double)gm.HW * (double)(gm.cg8 * 8)));
-    if (gate)
-        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<Tag, true>), agrid, dim3(256), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x, (const Tag::storage*)gate,
-                                              mean, rstd, gamma, (const float*)S, (Tag::storage*)dx, items, per_sample, inv_m, gm));
+    const float inv_m = (float)(1.0 / ((double)gm.HW * (double)gm.cg));
+    if (beta)
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<Tag, GN_ACT_SILU>), agrid, dim3(256), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
+                                              (const Tag::storage*)nullptr, mean, rstd, gamma, beta, (const float*)S, (Tag::storage*)dx, items, per_sample, inv_m, gm));
+    else if (gate)
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<Tag, GN_ACT_RELU>), agrid, dim3(256), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x, (const Tag::storage*)gate,
+                                              mean, rstd, gamma, beta, (const float*)S, (Tag::storage*)dx, items, per_sample, inv_m, gm));
     else
-        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<Tag, false>), agrid, dim3(256), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
-                                              (const Tag::storage*)nullptr, mean, rstd, gamma, (const float*)S, (Tag::storage*)dx, items, per_sample, inv_m, gm));
+        UC_DISPATCH_F16(fn, dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<Tag, GN_ACT_NONE>), agrid, dim3(256), 0, st, (const Tag::storage*)dy, (const Tag::storage*)x,
+                                              (const Tag::storage*)nullptr, mean, rstd, gamma, beta, (const float*)S, (Tag::storage*)dx, items, per_sample, inv_m, gm));
     UC_CHECK_LAUNCH(fn);
     return UC_OK;
+}
+
+extern "C" int uc_group_norm_nhwc_bwd(const void* dy, const void* x, const void* gate, const float* mean, const float* rstd,
+                                      const float* gamma, void* dx, float* dgamma, float* dbeta, float* ws, int dtype, int B, int H, int W,
+                                      int C, int G, uc_stream_t stream) {
+    return gn_backward("uc_group_norm_nhwc_bwd", dy, x, gate, mean, rstd, gamma, nullptr, dx, dgamma, dbeta, ws, dtype, B, H, W, C, G, stream);
+}
+
+extern "C" int uc_group_norm_silu_nhwc_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                                           const float* beta, void* dx, float* dgamma, float* dbeta, float* ws, int dtype, int B, int H, int W,
+                                           int C, int G, uc_stream_t stream) {
+    const char* fn = "uc_group_norm_silu_nhwc_bwd";
+    UC_REQUIRE(beta, "%s: null pointer", fn);
+    return gn_backward(fn, dy, x, nullptr, mean, rstd, gamma, beta, dx, dgamma, dbeta, ws, dtype, B, H, W, C, G, stream);
 }

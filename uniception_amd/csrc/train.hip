@@ -560,6 +560,7 @@ extern "C" int uc_transpose2d(const void* src, int sd, void* dst, int dd, void* 
     if (sd == UC_BF16 && dd == UC_BF16) hipLaunchKernelGGL((transpose64_kernel<BF16Tag, BF16Tag>), grid, dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, (bf16_t*)rowmajor_copy, R, S, ld_dst, rows_on_x);
     else if (sd == UC_F32 && dd == UC_F32) hipLaunchKernelGGL((transpose64_kernel<F32Tag, F32Tag>), grid, dim3(256), 0, st, (const float*)src, (float*)dst, (float*)rowmajor_copy, R, S, ld_dst, rows_on_x);
     else if (sd == UC_F32 && dd == UC_BF16) hipLaunchKernelGGL((transpose64_kernel<F32Tag, BF16Tag>), grid, dim3(256), 0, st, (const float*)src, (bf16_t*)dst, (bf16_t*)rowmajor_copy, R, S, ld_dst, rows_on_x);
+    else if (sd == UC_F16 && dd == UC_F16) hipLaunchKernelGGL((transpose64_kernel<F16Tag, F16Tag>), grid, dim3(256), 0, st, (const unsigned short*)src, (unsigned short*)dst, (unsigned short*)rowmajor_copy, R, S, ld_dst, rows_on_x);
     else { uc_set_error("uc_transpose2d: unsupported dtypes %d -> %d", sd, dd); return UC_ERR_BAD_ARG; }
     UC_CHECK_LAUNCH("uc_transpose2d");
     return UC_OK;

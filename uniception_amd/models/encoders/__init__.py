@@ -1,6 +1,7 @@
 """Encoder factory, restricted to the encoders with a HIP path (reference: encoders/__init__.py:32-140)."""
 from .base import (EncoderGlobalRepInput, EncoderGlobalRepOutput, EncoderInput, EncoderOutput, UniCeptionEncoderBase,  # noqa: F401
                    UniCeptionViTEncoderBase, ViTEncoderInput, ViTEncoderNonImageInput, ViTEncoderOutput)
+from .cosmos import CosmosEncoder
 from .croco import CroCoEncoder, CroCoIntermediateFeatureReturner
 from .dense_rep_encoder import DenseRepresentationEncoder, ResidualBlock  # noqa: F401
 from .dinov2 import DINOv2Encoder, DINOv2IntermediateFeatureReturner
@@ -11,6 +12,7 @@ from .perception_encoder import PerceptionEncoder, PerceptionEncoderIntermediate
 from .pixio import PixioEncoder
 
 ENCODER_CONFIGS = {
+    "cosmos": {"class": CosmosEncoder, "supported_models": ["Cosmos-Tokenizer CI8x8", "Cosmos-Tokenizer CI16x16"]},
     "croco": {"class": CroCoEncoder, "intermediate_feature_returner_class": CroCoIntermediateFeatureReturner,
               "supported_models": ["CroCov2", "DUSt3R", "MASt3R"]},
     "dense_rep_encoder": {"class": DenseRepresentationEncoder, "supported_models": ["Dense-Representation-Encoder"]},

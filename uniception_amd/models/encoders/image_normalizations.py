@@ -20,5 +20,6 @@ _TABLE = {
     "patch_embedder": _IMAGENET,
     "perception_encoder": ([0.5] * 3, [0.5] * 3),
     "pixio": _IMAGENET,
+    "cosmos": ([0.0, 0.0, 0.0], [0.5, 0.5, 0.5]),
 }
 IMAGE_NORMALIZATION_DICT = {k: ImageNormalization(mean=torch.tensor(m), std=torch.tensor(s)) for k, (m, s) in _TABLE.items()}

@@ -8,3 +8,4 @@ from .mlp_head import MLPHead  # noqa: F401,E402
 from .pose_head import PoseHead, ResConvBlock  # noqa: F401,E402
 from .mlp_feature import MLPFeature  # noqa: F401,E402
 from .moge_conv import MoGeConvFeature, ResidualConvBlock, normalized_view_plane_uv  # noqa: F401,E402
+from .cosmos import COSMOS_LATENT_CHANNELS, CosmosFeature, CosmosSingleChannel  # noqa: F401,E402

@@ -1521,3 +1521,127 @@ def vit_stem_bwd(dy: torch.Tensor, tok: torch.Tensor, cls: Optional[torch.Tensor
     _lib.check(lib.uc_vit_stem_bwd(dy.data_ptr(), _dt(dy.dtype), tok.data_ptr(), _dt(tok.dtype), _p(cls), _p(pos), _p(gamma), _p(stats), _p(dtok),
                                    _p(dcls), _p(dpos), _p(dg), _p(db), ws.data_ptr(), B, hw, Cn, _stream()), "uc_vit_stem_bwd")
     return dtok, dcls, dpos, dg, db
+
+
+# =================================================================================================================
+# Cosmos image tokenizer: Haar patcher, GroupNorm + SiLU, Downsample operand rows, nearest x2 upsample, row softmax
+# =================================================================================================================
+def haar_patch(img: torch.Tensor, out_dtype: torch.dtype, ld: Optional[int] = None, scale: float = 1.0) -> torch.Tensor:
+    """fp32 NCHW image [B,C,H,W] (H, W multiples of 4) -> NHWC [B,H/4,W/4,ld] in out_dtype: the two-level Haar transform in the first
+    16 C channels (index s2 * 4C + s1 * C + c), zeros in the others (uc_haar_patch)."""
+    _need_gpu(img)
+    assert img.dim() == 4 and img.is_contiguous() and img.dtype == torch.float32
+    B, Cn, H, W = img.shape
+    ld = 16 * Cn if ld is None else ld
+    y = torch.empty((B, H // 4, W // 4, ld), dtype=out_dtype, device=img.device)
+    _lib.check(_lib.load().uc_haar_patch(img.data_ptr(), y.data_ptr(), _dt(out_dtype), B, Cn, H, W, ld, float(scale), _stream()), "uc_haar_patch")
+    return y
+
+
+def haar_unpatch(rows: torch.Tensor, Cn: int, scale: float = 1.0) -> torch.Tensor:
+    "NHWC [B,h,w,ld] (ld >= 16 Cn) -> fp32 NCHW [B,Cn,4h,4w]: the inverse of haar_patch, times scale (uc_haar_unpatch)."
+    B, h, w, ld = _nhwc4(rows)
+    img = torch.empty((B, Cn, 4 * h, 4 * w), dtype=torch.float32, device=rows.device)
+    _lib.check(_lib.load().uc_haar_unpatch(rows.data_ptr(), _dt(rows.dtype), img.data_ptr(), B, Cn, 4 * h, 4 * w, ld, float(scale), _stream()),
+               "uc_haar_unpatch")
+    return img
+
+
+def group_norm_silu_nhwc(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, G: int, eps: float):
+    "(y, mean [B,G], rstd [B,G]) of y = silu(GroupNorm(x)) on NHWC x: group_norm_nhwc's statistics, SiLU in the apply pass."
+    B, H, W, Cn = _nhwc4(x)
+    _need_gpu(gamma, beta)
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.is_contiguous() and beta.is_contiguous()
+    assert gamma.numel() == Cn and beta.numel() == Cn
+    lib = _lib.load()
+    y = torch.empty_like(x)
+    mean = torch.empty((B, G), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((B, G), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(1, lib.uc_group_norm_silu_nhwc_ws_bytes(B, H, W, Cn, G) // 4), dtype=torch.float32, device=x.device)
+    _lib.check(lib.uc_group_norm_silu_nhwc(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                           ws.data_ptr(), _dt(x.dtype), B, H, W, Cn, G, float(eps), _stream()), "uc_group_norm_silu_nhwc")
+    return y, mean, rstd
+
+
+def group_norm_silu_nhwc_bwd(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
+    "(dx, dgamma, dbeta) of group_norm_silu_nhwc; the pre-activation is recomputed from x."
+    B, H, W, Cn = _nhwc4(x)
+    _need_gpu(dy, gamma, beta)
+    assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous()
+    assert mean.dtype == torch.float32 and rstd.dtype == torch.float32 and mean.is_contiguous() and rstd.is_contiguous() and mean.shape == rstd.shape
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == Cn for t in (gamma, beta))
+    G = mean.shape[1]
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    dg = torch.empty(Cn, dtype=torch.float32, device=x.device)
+    db = torch.empty(Cn, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(1, lib.uc_group_norm_silu_nhwc_bwd_ws_bytes(B, H, W, Cn, G) // 4), dtype=torch.float32, device=x.device)
+    _lib.check(lib.uc_group_norm_silu_nhwc_bwd(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                               dx.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), _dt(x.dtype), B, H, W, Cn, G, _stream()),
+               "uc_group_norm_silu_nhwc_bwd")
+    return dx, dg, db
+
+
+def down2_gather(x: torch.Tensor) -> torch.Tensor:
+    """NHWC x [B,H,W,C] (H, W even) -> operand rows [B*(H/2)*(W/2), 9C], K ordered (ky,kx,c), of the 3x3 / stride-2 convolution padded on
+    the right and bottom only (uc_down2_gather)."""
+    B, H, W, Cn = _nhwc4(x)
+    if H % 2 or W % 2:
+        raise UcHipError(f"down2_gather: the Downsample of an odd map ({H} x {W}) has no HIP path")
+    rows = torch.empty((B * (H // 2) * (W // 2), 9 * Cn), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.load().uc_down2_gather(x.data_ptr(), rows.data_ptr(), _dt(x.dtype), B, H, W, Cn, _stream()), "uc_down2_gather")
+    return rows
+
+
+def down2_gather_bwd(drows: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+    "adjoint of down2_gather: drows [B*(H/2)*(W/2), 9C] -> dx [B,H,W,C]"
+    _need_gpu(drows)
+    assert drows.dim() == 2 and drows.is_contiguous() and drows.shape[0] == B * (H // 2) * (W // 2) and drows.shape[1] % 9 == 0
+    Cn = drows.shape[1] // 9
+    dx = torch.empty((B, H, W, Cn), dtype=drows.dtype, device=drows.device)
+    _lib.check(_lib.load().uc_down2_gather_bwd(drows.data_ptr(), dx.data_ptr(), _dt(drows.dtype), B, H, W, Cn, _stream()), "uc_down2_gather_bwd")
+    return dx
+
+
+def upsample2_nhwc(x: torch.Tensor) -> torch.Tensor:
+    "[B,H,W,C] -> [B,2H,2W,C], every pixel repeated 2x2 (nearest neighbour)"
+    B, H, W, Cn = _nhwc4(x)
+    y = torch.empty((B, 2 * H, 2 * W, Cn), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.load().uc_upsample2_nhwc(x.data_ptr(), y.data_ptr(), _dt(x.dtype), B, H, W, Cn, _stream()), "uc_upsample2_nhwc")
+    return y
+
+
+def upsample2_nhwc_bwd(dy: torch.Tensor) -> torch.Tensor:
+    "adjoint of upsample2_nhwc: dy [B,2H,2W,C] -> the sum of every 2x2 block [B,H,W,C]"
+    B, H2, W2, Cn = _nhwc4(dy)
+    assert H2 % 2 == 0 and W2 % 2 == 0
+    dx = torch.empty((B, H2 // 2, W2 // 2, Cn), dtype=dy.dtype, device=dy.device)
+    _lib.check(_lib.load().uc_upsample2_nhwc_bwd(dy.data_ptr(), dx.data_ptr(), _dt(dy.dtype), B, H2 // 2, W2 // 2, Cn, _stream()),
+               "uc_upsample2_nhwc_bwd")
+    return dx
+
+
+def softmax_rows(s: torch.Tensor, scale: float, out_dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """P = softmax(scale * s) per row.  s: fp32 [rows, N] (unit column stride, any row stride).  Returns P [rows, N] in out_dtype; with
+    `out` [rows, ldp >= N] given, P is its first N columns and the others are written as zeros (the K padding of the next product)."""
+    _need_gpu(s, out)
+    assert s.dim() == 2 and s.stride(1) == 1 and s.dtype == torch.float32
+    rows, N = s.shape
+    if out is None:
+        out = torch.empty((rows, N), dtype=out_dtype, device=s.device)
+    assert out.dim() == 2 and out.is_contiguous() and out.shape[0] == rows and out.shape[1] >= N and out.dtype == out_dtype
+    _lib.check(_lib.load().uc_softmax_rows(s.data_ptr(), s.stride(0), out.data_ptr(), _dt(out_dtype), out.shape[1], rows, N, float(scale), _stream()),
+               "uc_softmax_rows")
+    return out
+
+
+def softmax_rows_bwd(p: torch.Tensor, dp: torch.Tensor, N: int, scale: float) -> torch.Tensor:
+    """dS = scale * P * (dP - sum(dP * P)) per row.  p: [rows, ldp] contiguous (P in its first N columns), dp: fp32 [rows, N] (any row
+    stride).  Returns dS shaped like p, zeros in the columns beyond N."""
+    _need_gpu(p, dp)
+    assert p.dim() == 2 and p.is_contiguous() and dp.dim() == 2 and dp.stride(1) == 1 and dp.dtype == torch.float32
+    assert dp.shape == (p.shape[0], N) and p.shape[1] >= N
+    ds = torch.empty_like(p)
+    _lib.check(_lib.load().uc_softmax_rows_bwd(p.data_ptr(), dp.data_ptr(), dp.stride(0), ds.data_ptr(), _dt(p.dtype), p.shape[1], p.shape[0], N,
+                                               float(scale), _stream()), "uc_softmax_rows_bwd")
+    return ds
