@@ -71,8 +71,9 @@ const char* uc_last_error(void);
  *       added (nothing existing changed).
  *   23: the Cosmos image tokenizer's streaming passes — uc_haar_patch, uc_haar_unpatch, uc_group_norm_silu_nhwc (+ _bwd, two _ws_bytes queries),
  *       uc_down2_gather (+ _bwd), uc_upsample2_nhwc (+ _bwd), uc_softmax_rows (+ _bwd) added; uc_transpose2d also takes f16 -> f16 (it
- *       answered "unsupported dtypes" before); nothing else existing changed. */
-#define UC_ABI_VERSION 23
+ *       answered "unsupported dtypes" before); nothing else existing changed.
+ *   24: the axial RoPE of the DINOv3 ViT — uc_rope_axial added (nothing existing changed). */
+#define UC_ABI_VERSION 24
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -101,6 +102,20 @@ int uc_rope2d(void* tokens, const int64_t* positions, int B, int N, int H, int D
 /* cos/sin table used by the fused GEMM epilogue: table[p][i] = (cos, sin)(p * F0 * base^(-i/Q)),
  * p in [0,npos), i in [0,Q), fp32 pairs.  Same angle formula as uc_rope2d. */
 int uc_rope_table(float* table, int npos, int Q, float base, float F0, uc_stream_t stream);
+
+/* Axial RoPE of the DINOv3 ViT, in place, on one or two operands (q, or q and k of a packed projection) in one launch.
+ * tokens is addressed as tokens[part*sp + b*sb + n*sn + h*sh + d] (element strides, d contiguous), part in [0, parts), parts 1 or 2.
+ * N = prefix + grid_h*grid_w: the first `prefix` tokens (class + register tokens) are left untouched; token n >= prefix lies at
+ * (y, x) = ((n-prefix) / grid_w, (n-prefix) % grid_w).  A head's D channels are laid out [y | x | y | x], each D/4 wide, and channel
+ * j is paired with j + D/2 (rotate_half): for j in [0, D/4) the pair (j, j + D/2) is rotated by table_y[y][j] and the pair
+ * (D/4 + j, D/4 + j + D/2) by table_x[x][j]:  u' = u c - v s,  v' = v c + u s,  (c, s) the table entry; inverse != 0 negates s (the
+ * gradient path).  table_y [grid_h][D/4][2], table_x [grid_w][D/4][2]: fp32 (cos, sin) pairs built by the caller — the kernel
+ * computes no trigonometry, so the coordinates behind the angles are the caller's (per axis, non-integer, augmented per call).
+ * D % 8 == 0, D <= 1024; dtype UC_F32 | UC_BF16 | UC_F16.  16-byte accesses when D % 32 == 0 and tokens / every stride are 16-byte
+ * aligned, element accesses otherwise.  An empty problem (B, N, H or the grid zero) launches nothing.  Allocates nothing. */
+int uc_rope_axial(void* tokens, int B, int N, int H, int D, int64_t sb, int64_t sn, int64_t sh, int parts, int64_t sp,
+                  int prefix, int grid_h, int grid_w, const float* table_y, const float* table_x, int inverse, int dtype,
+                  uc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * LayerNorm over the last dim: y = (x-mean)/sqrt(var_biased+eps)*gamma+beta

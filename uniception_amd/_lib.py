@@ -102,6 +102,7 @@ SIGNATURES = {
     "uc_tuning_get": [C.c_char_p, C.POINTER(i32)],
     "uc_rope2d": [vp, vp, i32, i32, i32, i32, i64, i64, i64, f32, f32, i32, vp],
     "uc_rope_table": [vp, i32, i32, f32, f32, vp],
+    "uc_rope_axial": [vp, i32, i32, i32, i32, i64, i64, i64, i32, i64, i32, i32, i32, vp, vp, i32, i32, vp],
     "uc_layernorm": [vp, i32, vp, vp, vp, i32, i64, i32, f32, vp],
     "uc_layernorm_twin": [vp, i32, vp, vp, vp, i32, vp, i64, i32, f32, vp],
     "uc_gemm": [C.POINTER(GemmDesc), vp],
@@ -195,7 +196,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 23  # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 24  # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

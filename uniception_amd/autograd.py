@@ -236,7 +236,7 @@ def kv_weight_t(projk, projv, dt):
 
 
 def _check_rope(rope):
-    if rope is not None and not engine.is_native_rope(rope):
+    if rope is not None and not engine.is_native_rope(rope) and not engine.is_axial_rope(rope):
         raise UcHipError("training through a foreign positional-encoding callable is not supported; use RoPE2D / cuRoPE2D")
 
 
@@ -245,9 +245,18 @@ def _rope_inverse_(t4, pos, rope):
         ops.rope_2d_(t4, pos.contiguous(), rope.base, -rope.F0)
 
 
+def _rope_forward_(q4, k4, qpos, kpos, rope):
+    "the positional encoding of q / k as a pass of its own, in place: the axial RoPE's one launch over q | k, or two uc_rope2d passes"
+    if engine.is_axial_rope(rope):
+        rope.rotate_(q4, k4)
+    else:
+        ops.rope_2d_(q4, qpos.contiguous(), rope.base, rope.F0)
+        ops.rope_2d_(k4, kpos.contiguous(), rope.base, rope.F0)
+
+
 def _bwd_rope(rope, qpos, kpos, dt):
     "rope argument of ops.attention_bwd when the inverse rotation can ride in the bf16 backward kernels, else None."
-    if rope is None or dt != torch.bfloat16 or qpos is None or kpos is None or qpos.numel() == 0:
+    if rope is None or engine.is_axial_rope(rope) or dt != torch.bfloat16 or qpos is None or kpos is None or qpos.numel() == 0:
         return None
     return (engine._pos2d(qpos), engine._pos2d(kpos), rope.base, rope.F0)
 
@@ -550,7 +559,7 @@ def _unfold_layerscale(lin, gamma, dWf, dbf):
 # =================================================================================================================
 def _rope_in_gemm(rope, qn, kn, dt, Dh) -> bool:
     "Does the q / k GEMM's epilogue rotate its output (bf16 with a rope and no qk_norm)?  Else _prep_qk rotates behind the GEMM."
-    if qn is not None or kn is not None or dt != torch.bfloat16 or rope is None:
+    if qn is not None or kn is not None or dt != torch.bfloat16 or rope is None or engine.is_axial_rope(rope):
         return False
     ops.attention_served(dt, Dh, rope=True)
     return True
@@ -563,14 +572,12 @@ def _prep_qk(q4, k4, qn, kn, rope, qpos, kpos, in_gemm: bool):
     unless the GEMM's epilogue did (`in_gemm`, see _rope_in_gemm), and None is returned."""
     if qn is None and kn is None:
         if rope is not None and not in_gemm:
-            ops.rope_2d_(q4, qpos.contiguous(), rope.base, rope.F0)
-            ops.rope_2d_(k4, kpos.contiguous(), rope.base, rope.F0)
+            _rope_forward_(q4, k4, qpos, kpos, rope)
         return None
     qx = engine.qk_layernorm(q4, qn) if qn is not None else q4.contiguous()
     kx = engine.qk_layernorm(k4, kn) if kn is not None else k4.contiguous()
     if rope is not None:
-        ops.rope_2d_(qx, qpos.contiguous(), rope.base, rope.F0)
-        ops.rope_2d_(kx, kpos.contiguous(), rope.base, rope.F0)
+        _rope_forward_(qx, kx, qpos, kpos, rope)
     return qx, kx
 
 
@@ -581,7 +588,9 @@ def _attention_bwd_block(q4, k4, v4, qkn, o, do4, lse, scale, dq4, dk4, dv4, rop
     qa, ka = qkn if qkn else (q4, k4)
     dqa, dka = (torch.empty_like(qa), torch.empty_like(ka)) if qkn else (dq4, dk4)
     ops.attention_bwd(qa, ka, v4, o, do4, lse, scale, out=(dqa, dka, dv4), rope=fused_rope, dropout=adrop)
-    if fused_rope is None:
+    if engine.is_axial_rope(rope):        # (gradients of the rotated q | k -> one inverse pass over dq | dk)
+        rope.rotate_(dqa, dka, inverse=True)
+    elif fused_rope is None:
         _rope_inverse_(dqa, qpos, rope)
         _rope_inverse_(dka, kpos, rope)
     dqn_w = dqn_b = dkn_w = dkn_b = None
@@ -684,7 +693,7 @@ def self_attn_sublayer(x2d, ln, qkv, proj, B, N, H, rope, pos, scale, dt, gamma=
     """gamma: LayerScale on the sub-layer's output (x + gamma * proj(...)), or None.  q_norm / k_norm: the layer's qk_norm modules
     (LayerNorm over head_dim before the positional encoding; nn.Identity / None: off).  attn_drop: (p, seed) from attn_dropout, or None."""
     qn, kn = _norm_or_none(q_norm), _norm_or_none(k_norm)
-    if rope is not None and not engine.is_native_rope(rope):      # a foreign positional-encoding callable: the unfused route
+    if rope is not None and not engine.is_native_rope(rope) and not engine.is_axial_rope(rope):      # a foreign positional-encoding callable: the unfused route
         if gamma is not None or qn is not None or kn is not None:
             raise UcHipError("LayerScale / qk_norm next to a foreign positional-encoding callable have no HIP training path")
         return self_attn_sublayer_unfused(x2d, ln, qkv, proj, B, N, H, rope, pos, scale, dt, drops, attn_drop)

@@ -621,9 +621,16 @@ def is_native_rope(rope) -> bool:
     return rope is not None and getattr(rope, "_uc_native_rope", False)
 
 
+def is_axial_rope(rope) -> bool:
+    """A bound axial RoPE (models/libs/dinov3/rope.py: RoPEAxial.bind): the second native kind.  It carries its own (cos, sin) tables
+    and grid, takes no position tensor, leaves the prefix tokens alone and rotates q | k in one uc_rope_axial pass behind the QKV GEMM
+    (`rope.rotate_(q, k, inverse=False)`) — no GEMM epilogue and no attention-backward epilogue has its arithmetic."""
+    return rope is not None and getattr(rope, "_uc_axial_rope", False)
+
+
 def _rope_epilogue(rope, pos: torch.Tensor, cols: int):
-    "rope argument of ops.gemm: the native RoPE-2D on the first `cols` output columns, or None without a rope."
-    if rope is None:
+    "rope argument of ops.gemm: the native RoPE-2D on the first `cols` output columns, or None without a rope (or with the axial one)."
+    if rope is None or is_axial_rope(rope):
         return None
     pos2d = _pos2d(pos)
     table = ops.rope_table(pos2d.device, ROPE_TABLE_NPOS, rope.base, rope.F0)
@@ -742,16 +749,21 @@ def self_attention(h2d: torch.Tensor, B: int, N: int, qkv: nn.Linear, proj: nn.L
     Cd = qkv.out_features // 3          # width of q / k / v: the model width, or `latent_attn_dim` (utils/transformer_blocks.py:178-199)
     Dh = Cd // num_heads
     wq, bq, lnq = _folded(qkv, fold, dtype)
-    route = attention_route(dtype, Dh, rope is None or is_native_rope(rope), _has_norm(q_norm, k_norm), False, N, has_rope=rope is not None)
+    axial = is_axial_rope(rope)       # (rotated in place behind the GEMM on every route: the GEMM then runs with bias / VT epilogue only)
+    route = attention_route(dtype, Dh, rope is None or axial or is_native_rope(rope), _has_norm(q_norm, k_norm), False, N, has_rope=rope is not None)
     if route in ("unfused", "wide"):      # ("wide": bf16 q, k, v of the plain GEMM -> uc_vt_pack -> the wide-head kernel, in _attention_generic)
         t = ops.gemm(h2d, wq, bq, ln=lnq).view(B, N, 3, num_heads, Dh)
         o = _unfused_attention(t[:, :, 0], t[:, :, 1], t[:, :, 2], q_norm, k_norm, rope, pos, pos, scale)
     elif route == "vt_epilogue":
         vt = ops.vt_buffer(B, num_heads, N, h2d.device)
         qk = ops.gemm(h2d, wq, bq, rope=_rope_epilogue(rope, pos, 2 * Cd), vt=(2 * Cd, vt, N), ln=lnq).view(B, N, 2, num_heads, Dh)
+        if axial:
+            rope.rotate_(qk[:, :, 0], qk[:, :, 1])
         o = _fused_attention(route, qk[:, :, 0], qk[:, :, 1], vt, scale)
     else:
         t = ops.gemm(h2d, wq, bq, rope=_rope_epilogue(rope, pos, 2 * Cd), ln=lnq).view(B, N, 3, num_heads, Dh)
+        if axial:
+            rope.rotate_(t[:, :, 0], t[:, :, 1])
         o = _fused_attention(route, t[:, :, 0], t[:, :, 1], t[:, :, 2], scale)
     return _out_proj(o.view(M, Cd), proj, proj_wb, dtype, residual, out_dtype, emit_ln)
 
@@ -759,6 +771,9 @@ def self_attention(h2d: torch.Tensor, B: int, N: int, qkv: nn.Linear, proj: nn.L
 def _apply_rope(rope, q, k, qpos, kpos):
     """q,k: [B,N,H,D] views.  Native rope rotates in place; a foreign callable gets the reference's [B,H,N,D] view."""
     if rope is None:
+        return q, k
+    if is_axial_rope(rope):
+        rope.rotate_(q, k)
         return q, k
     if is_native_rope(rope):
         ops.rope_2d_(q, qpos.contiguous(), rope.base, rope.F0)
@@ -816,6 +831,8 @@ def cross_attention(hq2d: torch.Tensor, hkv2d: torch.Tensor, B: int, Nq: int, Nk
     dtype = hq2d.dtype
     Cd = hq2d.shape[1]
     Dh = Cd // num_heads
+    if is_axial_rope(rope):
+        raise UcHipError("the axial RoPE is bound to one token grid: it serves self-attention only")
     route = attention_route(dtype, Dh, rope is None or is_native_rope(rope), _has_norm(q_norm, k_norm), hv2d is not None, Nk,
                             has_rope=rope is not None)
     wq, bq, lnq = _folded(projq, fold_q, dtype)

@@ -17,6 +17,7 @@ _TABLE = {
     "croco": _IMAGENET,
     "dust3r": ([0.5, 0.5, 0.5], [0.5, 0.5, 0.5]),
     "dinov2": _IMAGENET,
+    "dinov3": _IMAGENET,
     "patch_embedder": _IMAGENET,
     "perception_encoder": ([0.5] * 3, [0.5] * 3),
     "pixio": _IMAGENET,

@@ -100,6 +100,35 @@ def rope_2d_(tokens: torch.Tensor, positions: torch.Tensor, base: float, fwd: fl
                              tokens.stride(2), float(base), float(fwd), _dt(tokens.dtype), _stream()), "uc_rope2d")
 
 
+def rope_axial_(q: torch.Tensor, k: Optional[torch.Tensor], table_y: torch.Tensor, table_x: torch.Tensor, prefix: int, grid_h: int,
+                grid_w: int, inverse: bool = False) -> None:
+    """In-place axial RoPE (DINOv3: uc_rope_axial) of q [B,N,H,D] and, when given, k of the same shape — views with stride(3) == 1, e.g.
+    the q | k slices of a packed [B,N,3,H,D] projection, which are rotated in ONE launch (k lies a constant offset behind q with the same
+    strides; anything else takes one launch per operand).  N == prefix + grid_h * grid_w; the first `prefix` tokens stay as they are.
+    table_y [grid_h, D/4, 2], table_x [grid_w, D/4, 2]: fp32 (cos, sin).  inverse: the rotation by the negated angle (gradients)."""
+    _need_gpu(q, k, table_y, table_x)
+    if q.dim() != 4 or q.stride(3) != 1:
+        raise UcHipError("rope_axial_: tokens must be a [B, N, H, D] view with a contiguous last dimension")
+    B, N, H, D = q.shape
+    for t, n in ((table_y, grid_h), (table_x, grid_w)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n, D // 4, 2):
+            raise UcHipError(f"rope_axial_: a table must be a contiguous fp32 [{n}, {D // 4}, 2] tensor, got {t.dtype} {tuple(t.shape)}")
+    lib = _lib.load()
+
+    def run(t, parts, sp):
+        _lib.check(lib.uc_rope_axial(t.data_ptr(), B, N, H, D, t.stride(0), t.stride(1), t.stride(2), parts, sp, prefix, grid_h, grid_w,
+                                     table_y.data_ptr(), table_x.data_ptr(), int(bool(inverse)), _dt(t.dtype), _stream()), "uc_rope_axial")
+    if k is None:
+        return run(q, 1, 0)
+    if k.shape != q.shape or k.dtype != q.dtype or k.stride(3) != 1:
+        raise UcHipError("rope_axial_: q and k must have the same shape and dtype")
+    off = k.data_ptr() - q.data_ptr()
+    if k.stride() == q.stride() and off > 0 and off % q.element_size() == 0:
+        return run(q, 2, off // q.element_size())
+    run(q, 1, 0)
+    run(k, 1, 0)
+
+
 _rope_tables = {}
 
 

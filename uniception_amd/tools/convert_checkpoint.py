@@ -28,6 +28,12 @@ checkpoints (tests/test_convert_checkpoint.py: round trip through `uniception_to
 "state_dict" / "weights", with optional "module." and "visual." prefixes; of a CLIP checkpoint only the "visual." entries are kept —
 the prefix handling of the reference's VisionTransformer.load_ckpt) -> the {"model": {"model." + key: tensor}} file that
 PerceptionEncoder(pretrained_checkpoint_path=...) loads.  A missing or unexpected key is an error that names it.
+
+--mode dinov3: the state_dict of a transformers DINOv3ViTModel (the bare dict, or under "state_dict" / "model") -> the
+{"model": {"model." + key: tensor}} file that DINOv3Encoder(pretrained_checkpoint_path=...) loads: q / k / v packed into attn.qkv
+(a missing key bias becomes zeros), attn.qkv.bias_mask (1 | 0 | 1) and rope_embed.periods synthesised, layer_scale*.lambda1 ->
+ls*.gamma, register_tokens -> storage_tokens, gate_proj / up_proj / down_proj -> w1 / w2 / w3 (up_proj / down_proj -> fc1 / fc2
+without a gate).  An unexpected key is an error that names it.
 """
 import argparse
 import os
@@ -203,11 +209,71 @@ def perception_encoder_to_uniception(ckpt: Dict, config_name: str) -> Dict[str, 
     return {"model." + k: sd[k] for k in want}
 
 
+_DINOV3_BLOCK = {"norm1.weight": "norm1.weight", "norm1.bias": "norm1.bias", "norm2.weight": "norm2.weight", "norm2.bias": "norm2.bias",
+                 "attention.o_proj.weight": "attn.proj.weight", "attention.o_proj.bias": "attn.proj.bias",
+                 "layer_scale1.lambda1": "ls1.gamma", "layer_scale2.lambda1": "ls2.gamma"}
+_DINOV3_FFN = {True: {"gate_proj": "w1", "up_proj": "w2", "down_proj": "w3"}, False: {"up_proj": "fc1", "down_proj": "fc2"}}
+_DINOV3_TOP = {"embeddings.cls_token": "cls_token", "embeddings.register_tokens": "storage_tokens",
+               "embeddings.patch_embeddings.weight": "patch_embed.proj.weight", "embeddings.patch_embeddings.bias": "patch_embed.proj.bias",
+               "norm.weight": "norm.weight", "norm.bias": "norm.bias"}
+
+
+def dinov3_hf_to_uniception(ckpt: Dict, num_heads: Optional[int] = None, rope_base: float = 100.0, prefix: str = "model.") -> Dict[str, torch.Tensor]:
+    """The state_dict of DINOv3Encoder (keys under `prefix`) from a transformers DINOv3ViTModel state_dict.  num_heads: the model's
+    head count (rope_embed.periods has head_dim / 4 entries); None: head_dim 64, which every served size has.  KeyError naming the first key without a counterpart."""
+    sd = ckpt
+    for wrap in ("state_dict", "model"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+    out, qkv = {}, {}
+    for k, v in sd.items():
+        m = re.match(r"(?:model\.)?layer\.(\d+)\.(.+)$", k)
+        if k in _DINOV3_TOP:
+            out[_DINOV3_TOP[k]] = v
+        elif k == "embeddings.mask_token":
+            out["mask_token"] = v.reshape(1, -1)
+        elif k == "rope_embeddings.inv_freq":
+            continue          # (a derived buffer: rope_embed.periods is synthesised below)
+        elif m:
+            i, rest = m.group(1), m.group(2)
+            b = f"blocks.{i}."
+            ma = re.match(r"attention\.([qkv])_proj\.(weight|bias)$", rest)
+            mf = re.match(r"mlp\.(gate_proj|up_proj|down_proj)\.(weight|bias)$", rest)
+            if ma:
+                qkv.setdefault(i, {})[ma.group(1) + ma.group(2)] = v
+            elif mf:
+                gated = any(x.endswith(f"layer.{i}.mlp.gate_proj.weight") for x in sd)
+                out[b + f"mlp.{_DINOV3_FFN[gated][mf.group(1)]}.{mf.group(2)}"] = v
+            elif rest in _DINOV3_BLOCK:
+                out[b + _DINOV3_BLOCK[rest]] = v
+            else:
+                raise KeyError(f"unexpected key {k} in a transformers DINOv3ViTModel state_dict")
+        else:
+            raise KeyError(f"unexpected key {k} in a transformers DINOv3ViTModel state_dict")
+    for i, p in qkv.items():
+        for need in ("qweight", "kweight", "vweight"):
+            if need not in p:
+                raise KeyError(f"missing key layer.{i}.attention.{need[0]}_proj.weight")
+        D = p["qweight"].shape[0]
+        zeros = torch.zeros(D, dtype=p["qweight"].dtype)
+        out[f"blocks.{i}.attn.qkv.weight"] = torch.cat([p["qweight"], p["kweight"], p["vweight"]], 0)
+        out[f"blocks.{i}.attn.qkv.bias"] = torch.cat([p.get("qbias", zeros), p.get("kbias", zeros), p.get("vbias", zeros)], 0)
+        mask = torch.ones(3 * D, dtype=p["qweight"].dtype)
+        mask[D:2 * D] = 0.0 if "kbias" not in p else 1.0
+        out[f"blocks.{i}.attn.qkv.bias_mask"] = mask
+    if "cls_token" not in out:
+        raise KeyError("missing key embeddings.cls_token: not a transformers DINOv3ViTModel state_dict")
+    hd = out["cls_token"].shape[-1] // num_heads if num_heads else 64
+    out["rope_embed.periods"] = rope_base ** (4 * torch.arange(hd // 4, dtype=torch.float32) / hd)
+    return {prefix + k: v for k, v in out.items()}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("original")
     ap.add_argument("out")
-    ap.add_argument("--mode", default="dust3r", choices=("dust3r", "perception_encoder"))
+    ap.add_argument("--mode", default="dust3r", choices=("dust3r", "perception_encoder", "dinov3"))
+    ap.add_argument("--num-heads", type=int, default=None, help="dinov3 mode: the model's attention head count (default: embed dim / 64)")
     ap.add_argument("--pe-config", default=None, help="perception_encoder mode: the vision tower's config name, e.g. PE-Core-L14-336")
     ap.add_argument("--per-module-dir", default=None, help="also write encoder / info_sharing / head checkpoints there")
     a = ap.parse_args(argv)
@@ -218,6 +284,11 @@ def main(argv=None):
         converted = perception_encoder_to_uniception(ckpt, a.pe_config)
         torch.save({"model": converted}, a.out)
         print(f"wrote {a.out}: {len(converted)} entries of {a.pe_config}")
+        return
+    if a.mode == "dinov3":
+        converted = dinov3_hf_to_uniception(ckpt, a.num_heads)
+        torch.save({"model": converted}, a.out)
+        print(f"wrote {a.out}: {len(converted)} entries of a DINOv3 ViT")
         return
     sd = ckpt["model"] if "model" in ckpt else ckpt
     converted, dropped = original_to_uniception(sd)
