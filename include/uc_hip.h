@@ -72,8 +72,10 @@ const char* uc_last_error(void);
  *   23: the Cosmos image tokenizer's streaming passes — uc_haar_patch, uc_haar_unpatch, uc_group_norm_silu_nhwc (+ _bwd, two _ws_bytes queries),
  *       uc_down2_gather (+ _bwd), uc_upsample2_nhwc (+ _bwd), uc_softmax_rows (+ _bwd) added; uc_transpose2d also takes f16 -> f16 (it
  *       answered "unsupported dtypes" before); nothing else existing changed.
- *   24: the axial RoPE of the DINOv3 ViT — uc_rope_axial added (nothing existing changed). */
-#define UC_ABI_VERSION 24
+ *   24: the axial RoPE of the DINOv3 ViT — uc_rope_axial added (nothing existing changed).
+ *   25: the DINOv3 ConvNeXt's depthwise 7x7 convolution and stage downsample — uc_dwconv7x7_nhwc, uc_dwconv7x7_nhwc_wgrad (+ _ws_bytes),
+ *       uc_patch2_gather_nhwc (+ _bwd) added (nothing existing changed). */
+#define UC_ABI_VERSION 25
 int uc_abi_version(void);
 /* "release" (the shipped library: no diagnostics compiled in) or "diag" (-DUC_DIAG: UC_GEMM_DBG / UC_ATTN_DBG / UC_GEMM_TRACE honoured). */
 const char* uc_build_flavor(void);
@@ -858,6 +860,37 @@ int uc_upsample2_nhwc_bwd(const void* dy, void* dx, int dtype, int B, int H, int
 int uc_softmax_rows(const float* S, int64_t lds, void* P, int p_dtype, int64_t ldp, int64_t rows, int64_t N, float scale, uc_stream_t stream);
 int uc_softmax_rows_bwd(const void* P, const float* dP, int64_t lds, void* dS, int p_dtype, int64_t ldp, int64_t rows, int64_t N, float scale,
                         uc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * The ConvNeXt layer's depthwise convolution nn.Conv2d(C, C, 7, padding=3, groups=C) and the operand rows of the stage downsample
+ * nn.Conv2d(Cin, Cout, 2, stride=2), on channels-last maps [B, H, W, C] (csrc/dwconv.hip; launch geometry: csrc/dwconv_plan.h).
+ * They allocate nothing, use no atomics (every sum runs in one fixed order: the same bits on every run) and check every argument
+ * before anything is launched (UC_ERR_BAD_ARG, message prefixed with the function name); B == 0 is UC_OK with no launch.
+ * dtype: UC_F32 | UC_BF16 | UC_F16, the storage type of every map; C % 8 == 0 and 16-byte aligned bases (anything else is refused:
+ * there is no scalar path).
+ *
+ *   uc_dwconv7x7_nhwc:  y[b, i, j, c] = bias[c] + sum over (ky, kx), ascending row-major, of w[ky 7 + kx][c] x[b, i + ky - 3, j + kx - 3, c];
+ *                     taps outside the map contribute nothing (zero padding 3).  x, y in `dtype`; w fp32 [49][C], tap-major (the
+ *                     [C, 1, 7, 7] parameter transposed once); bias fp32 [C] or NULL.  fp32 accumulation (one fused multiply-add
+ *                     per tap), starting from the bias.  flip != 0 reads tap 48 - t in place of t: the data gradient is
+ *                     dx = uc_dwconv7x7_nhwc(dy, w, NULL, flip = 1).  y == x is refused.
+ *   uc_dwconv7x7_nhwc_wgrad:  dw[ky 7 + kx][c] = sum over b, i, j of dy[b, i, j, c] x[b, i + ky - 3, j + kx - 3, c] (x zero outside the map),
+ *                     db[c] = sum dy[b, i, j, c]; dw fp32 [49][C], db fp32 [C] or NULL.  Two fixed-order stages: per-workgroup
+ *                     partials into ws, then a merge in ascending partial order.  ws: caller-provided, at least
+ *                     uc_dwconv7x7_nhwc_wgrad_ws_bytes(B, H, W, C) bytes (the same for every dtype), 16-byte aligned.
+ *   uc_patch2_gather_nhwc:  rows[(b, i, j)][(ky 2 + kx) C + c] = x[b, 2 i + ky, 2 j + kx, c]: rows [B (H/2) (W/2), 4 C] (integer division);
+ *                     an odd last row or column of x is not read, as Conv2d drops it.  The GEMM weight is the [Cout, Cin, 2, 2]
+ *                     parameter permuted once to (ky, kx, c) order.
+ *   uc_patch2_gather_nhwc_bwd:  its adjoint, a permutation: dx[b, y, x, c] = drows[(b, y/2, x/2)][((y & 1) 2 + (x & 1)) C + c], and zero in
+ *                     an odd last row or column.  H, W: those of x.
+ * ---------------------------------------------------------------------------------- */
+int uc_dwconv7x7_nhwc(const void* x, const float* w, const float* bias, void* y, int dtype, int B, int H, int W, int C, int flip,
+                      uc_stream_t stream);
+int64_t uc_dwconv7x7_nhwc_wgrad_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C);
+int uc_dwconv7x7_nhwc_wgrad(const void* x, const void* dy, float* dw, float* db, float* ws, int dtype, int B, int H, int W, int C,
+                            uc_stream_t stream);
+int uc_patch2_gather_nhwc(const void* x, void* rows, int dtype, int B, int H, int W, int C, uc_stream_t stream);
+int uc_patch2_gather_nhwc_bwd(const void* drows, void* dx, int dtype, int B, int H, int W, int C, uc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -191,12 +191,17 @@ SIGNATURES = {
     "uc_upsample2_nhwc_bwd": [vp, vp, i32, i32, i32, i32, i32, vp],
     "uc_softmax_rows": [vp, i64, vp, i32, i64, i64, i64, f32, vp],
     "uc_softmax_rows_bwd": [vp, vp, i64, vp, i32, i64, i64, i64, f32, vp],
+    "uc_dwconv7x7_nhwc": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "uc_dwconv7x7_nhwc_wgrad_ws_bytes": [i64, i64, i64, i64],
+    "uc_dwconv7x7_nhwc_wgrad": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "uc_patch2_gather_nhwc": [vp, vp, i32, i32, i32, i32, i32, vp],
+    "uc_patch2_gather_nhwc_bwd": [vp, vp, i32, i32, i32, i32, i32, vp],
 }
 
 _lib = None
 
 
-ABI_VERSION = 24  # UC_ABI_VERSION of include/uc_hip.h this binding was written against
+ABI_VERSION = 25  # UC_ABI_VERSION of include/uc_hip.h this binding was written against
 
 
 def load():

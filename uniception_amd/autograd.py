@@ -2263,3 +2263,69 @@ def wide_attention(qkv, B: int, N: int, scale: float, panel: int = WIDE_ATTN_PAN
     if panel < 1:
         raise UcHipError(f"wide_attention: panel={panel}")
     return WideAttentionFn.apply(qkv, B, N, float(scale), int(panel))
+
+
+# =================================================================================================================
+# DINOv3 ConvNeXt (encoders/dinov3.py): the depthwise 7x7 convolution and the operand rows of the stage downsample
+# =================================================================================================================
+def dwconv7x7_weights(conv):
+    "(fp32 [49, C] tap-major, fp32 bias [C] | None) of nn.Conv2d(C, C, 7, padding=3, groups=C), prepared once per weight version"
+    return engine.prepared(conv, "dw49", (conv.weight, conv.bias),
+                           lambda: (conv.weight.detach().float().reshape(conv.out_channels, 49).t().contiguous(),
+                                    None if conv.bias is None else conv.bias.detach().float().contiguous()))
+
+
+def check_dwconv7x7(conv) -> None:
+    if (conv.kernel_size != (7, 7) or conv.stride != (1, 1) or conv.padding != (3, 3) or conv.dilation != (1, 1)
+            or conv.groups != conv.in_channels or conv.out_channels != conv.in_channels or conv.padding_mode != "zeros"):
+        raise UcHipError("dwconv7x7: only the zero-padded depthwise 7x7 convolution of stride 1 has a HIP path (uc_dwconv7x7_nhwc)")
+    if conv.in_channels % 8:
+        raise UcHipError(f"dwconv7x7: {conv.in_channels} channels: uc_dwconv7x7_nhwc takes multiples of 8")
+
+
+@_sink_aware
+class DwConv7x7(Function):
+    """Depthwise 7x7 / padding 3 convolution on an NHWC map (uc_dwconv7x7_nhwc).  Backward: the data gradient is the same kernel on dy
+    with the taps read in reverse (flip: no flipped copy of weights that change every step), the weight and bias gradients are
+    uc_dwconv7x7_nhwc_wgrad (two fixed-order stages)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, conv):
+        x = _c(x)
+        w, b = dwconv7x7_weights(conv)
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return ops.dwconv7x7_nhwc(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = _as_dt(_c(dy), x.dtype)
+        dx = ops.dwconv7x7_nhwc(dy, w, None, flip=True) if ctx.needs_input_grad[0] else None
+        dw, db = ops.dwconv7x7_nhwc_wgrad(x, dy, bias=ctx.has_bias)
+        return dx, dw.t().reshape(-1, 1, 7, 7), db, None
+
+
+def dwconv7x7(x, conv):
+    "x NHWC [B, H, W, C] -> conv(x), same shape and dtype"
+    check_dwconv7x7(conv)
+    return DwConv7x7.apply(x, conv.weight, conv.bias, conv)
+
+
+@_sink_aware
+class Patch2Gather(Function):
+    "operand rows [B (H//2) (W//2), 4 C] of Conv2d(k = 2, stride = 2) on an NHWC map, K ordered (ky, kx, c); the adjoint is a permutation"
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _c(x)
+        ctx.geom = tuple(x.shape[:3])
+        return ops.patch2_gather_nhwc(x)
+
+    @staticmethod
+    def backward(ctx, drows):
+        return ops.patch2_gather_nhwc_bwd(_c(drows), *ctx.geom)
+
+
+def patch2_gather(x):
+    return Patch2Gather.apply(x)

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libuc_hip.so")
 SOURCES = ["error.hip", "rope_norm.hip", "rope_axial.hip", "gemm.hip", "gemm_glds_dense_bf16.hip", "gemm_glds_dense_f32.hip", "gemm_glds_dense_bs.hip", "gemm_glds_dense_all.hip", "gemm_glds_conv.hip", "gemm_glds_conv_f16.hip", "gemm_glds_dense_all_f16.hip", "gemm_tn.hip", "attention.hip", "attention_x3.hip", "attention_fp8.hip",
-           "attention_bwd.hip", "attention_wide.hip", "attention_diff.hip", "elementwise.hip", "train.hip", "dpt_bwd.hip", "pool.hip", "groupnorm.hip", "pad_resize.hip", "input_encoders.hip", "vit_stem.hip", "cosmos.hip"]
+           "attention_bwd.hip", "attention_wide.hip", "attention_diff.hip", "elementwise.hip", "train.hip", "dpt_bwd.hip", "pool.hip", "groupnorm.hip", "pad_resize.hip", "input_encoders.hip", "vit_stem.hip", "cosmos.hip", "dwconv.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-inline-asm"]
 
 

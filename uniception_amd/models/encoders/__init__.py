@@ -5,7 +5,8 @@ from .cosmos import CosmosEncoder
 from .croco import CroCoEncoder, CroCoIntermediateFeatureReturner
 from .dense_rep_encoder import DenseRepresentationEncoder, ResidualBlock  # noqa: F401
 from .dinov2 import DINOv2Encoder, DINOv2IntermediateFeatureReturner
-from .dinov3 import DINOv3Encoder, DINOv3IntermediateFeatureReturner
+from .dinov3 import (DINOv3ConvNextEncoder, DINOv3ConvNextIntermediateFeatureReturner, DINOv3Encoder,  # noqa: F401
+                     DINOv3IntermediateFeatureReturner)
 from .global_rep_encoder import GlobalRepresentationEncoder
 from .image_normalizations import IMAGE_NORMALIZATION_DICT  # noqa: F401
 from .patch_embedder import PatchEmbedder
@@ -21,6 +22,8 @@ ENCODER_CONFIGS = {
                "supported_models": ["DINOv2", "DINOv2-Registers", "DINOv2-Depth-Anythingv2"]},
     "dinov3": {"class": DINOv3Encoder, "intermediate_feature_returner_class": DINOv3IntermediateFeatureReturner,
                "supported_models": ["DINOv3-ViT"]},
+    "dinov3_convnext": {"class": DINOv3ConvNextEncoder, "intermediate_feature_returner_class": DINOv3ConvNextIntermediateFeatureReturner,
+                        "supported_models": ["DINOv3-ConvNext"]},
     "global_rep_encoder": {"class": GlobalRepresentationEncoder, "supported_models": ["Global-Representation-Encoder"]},
     "patch_embedder": {"class": PatchEmbedder, "supported_models": ["Patch-Embedder"]},
     "perception_encoder": {"class": PerceptionEncoder, "intermediate_feature_returner_class": PerceptionEncoderIntermediateFeatureReturner,

@@ -22,7 +22,26 @@ gradients of the ROTATED q | k and one uc_rope_axial(inverse) pass over dq | dk 
 split are a handful of torch ops on small tensors (cls_token / storage_tokens receive their gradients from autograd).  In train mode
 the RoPE coordinates are augmented per forward (libs/dinov3/rope.py) — two tiny tables rebuilt, no kernel work.
 
-The DINOv3 ConvNeXt variants of the reference are out of scope here.
+DINOv3 ConvNeXt (reference wrapper: `DINOv3ConvNextEncoder` / `DINOv3ConvNextIntermediateFeatureReturner`, hub entries
+`dinov3_convnext_{tiny,small,base,large}`).  `DINOv3ConvNextParams` restates the PUBLISHED ConvNeXt: a 4x4 / stride-4 stem convolution
++ LayerNorm, four stages of layers  x + gamma * pwconv2(GELU(pwconv1(LN(dwconv7x7(x)))))  (LayerNorm eps 1e-6, erf-GELU, a LayerScale
+`gamma` per layer), LayerNorm + 2x2 / stride-2 convolution between the stages, and a final LayerNorm, under the original ConvNeXt
+parameter names AS FAR AS THEY ARE REMEMBERED — the hub code was not available, so these names are UNVERIFIED:
+    downsample_layers.0.{0 (conv 4x4 s4), 1 (LayerNorm)}, downsample_layers.{1,2,3}.{0 (LayerNorm), 1 (conv 2x2 s2)},
+    stages.i.j.{dwconv, norm, pwconv1, pwconv2}.{weight,bias}, stages.i.j.gamma, norm.
+Equally UNVERIFIED is what the hub model does with `model.patch_size` (the wrapper sets it) on intermediate maps: the stage outputs
+are handed out at their native strides 4, 8, 16, 32 here; resampling them to the `patch_size` grid is NOT built.
+PARITY: pinned to transformers' DINOv3ConvNextModel (tests/golden/dinov3_convnext_hf.npz: final features, the four stage outputs,
+parameter gradients); UNPINNED against the hub code and checkpoints.  `convert_checkpoint --mode dinov3_convnext` maps a transformers
+state_dict onto these names.
+
+Kernel mapping (every activation stays NHWC, rows [B H W, C], between layers; NCHW only at the public boundary): uc_unshuffle_rows
+(the 4x4 patch rows, K = 48 zero-padded to 64) -> stem GEMM -> uc_layernorm -> per layer: uc_dwconv7x7_nhwc (csrc/dwconv.hip) ->
+uc_layernorm -> pwconv1 GEMM + GELU -> pwconv2 GEMM with gamma folded into weight and bias and the LAYER INPUT as the epilogue residual
+-> between stages: uc_layernorm -> uc_patch2_gather_nhwc -> GEMM with the weight permuted once to (ky, kx, c) -> final norm per pixel
+-> uc_nhwc_to_nchw.  The pooled "class" row the hub model prepends is normalised independently of the patch rows and never returned
+by the wrapper: it is not computed.  Training: DwConv7x7 (backward = the same kernel with flipped taps + uc_dwconv7x7_nhwc_wgrad),
+Patch2Gather, and the existing LayerNorm / linear / MLP Functions; LayerScale and the residual sum are differentiable products there.
 """
 from typing import List, Optional, Union
 
@@ -33,7 +52,7 @@ from ... import autograd, engine, ops
 from ..libs.dinov3.rope import RoPEAxial
 from ..utils import sublayers
 from ..utils.intermediate_feature_return import IntermediateFeatureReturner, feature_take_indices
-from .base import UniCeptionViTEncoderBase, ViTEncoderInput, ViTEncoderOutput
+from .base import UniCeptionEncoderBase, UniCeptionViTEncoderBase, ViTEncoderInput, ViTEncoderOutput
 
 # embed dim, depth, heads, FFN kind, FFN hidden width (head_dim 64 throughout)
 _SIZES = {"small": (384, 12, 6, "mlp", 1536), "small+": (384, 12, 6, "swiglu", 1536), "base": (768, 12, 12, "mlp", 3072),
@@ -327,4 +346,199 @@ class DINOv3IntermediateFeatureReturner(DINOv3Encoder, IntermediateFeatureReturn
             x2d = blk.forward_tokens(x2d, B, Nt, dt, rope)
             if i in take:
                 outs.append(ViTEncoderOutput(features=self._patch_map(self._normed_f32(x2d, self.norm_intermediate).view(B, Nt, D), B, h0, w0)))
+        return outs
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# DINOv3 ConvNeXt
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stage widths, stage depths (published)
+_CONVNEXT_SIZES = {"tiny": ((96, 192, 384, 768), (3, 3, 9, 3)), "small": ((96, 192, 384, 768), (3, 3, 27, 3)),
+                   "base": ((128, 256, 512, 1024), (3, 3, 27, 3)), "large": ((192, 384, 768, 1536), (3, 3, 27, 3))}
+# the reference wrapper's table (its tiny / small entry is the width of the last stage, 768)
+_CONVNEXT_EMBED_DIM = {"tiny": 768, "small": 768, "base": 1024, "large": 1536}
+STEM_PATCH, STEM_KPAD = 4, 64
+
+
+def resolve_convnext_size(size):
+    "(widths, depths) of a named size, or of a dict(hidden_sizes=, depths=) — custom variants and the tiny configurations of the tests"
+    if isinstance(size, dict):
+        widths, depths = tuple(size["hidden_sizes"]), tuple(size["depths"])
+    elif size in _CONVNEXT_SIZES:
+        widths, depths = _CONVNEXT_SIZES[size]
+    else:
+        raise engine.UcHipError(f"unknown DINOv3 ConvNeXt size '{size}'; supported: {sorted(_CONVNEXT_SIZES)}")
+    if len(widths) != 4 or len(depths) != 4 or any(w <= 0 or w % 8 for w in widths) or any(d < 1 for d in depths):
+        raise engine.UcHipError(f"DINOv3 ConvNeXt: four stage widths (multiples of 8: uc_dwconv7x7_nhwc) and four depths >= 1, got {widths} / {depths}")
+    return widths, depths
+
+
+class _ConvNextLayer(nn.Module):
+    "x + gamma * pwconv2(act(pwconv1(norm(dwconv(x)))))  — parameter container; the pipeline on NHWC rows is forward_rows."
+
+    def __init__(self, dim, layer_scale_init_value=1e-6):
+        super().__init__()
+        self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim)
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.pwconv1 = nn.Linear(dim, 4 * dim)
+        self.act = nn.GELU()
+        self.pwconv2 = nn.Linear(4 * dim, dim)
+        self.gamma = nn.Parameter(layer_scale_init_value * torch.ones(dim))
+
+    def forward_rows(self, x, dt):
+        "x: NHWC [B, H, W, C] in the stage's stream dtype -> the same"
+        C = x.shape[-1]
+        if autograd.grad_needed(x, *self.parameters()):
+            h = autograd.layer_norm(autograd.dwconv7x7(x, self.dwconv).view(-1, C), self.norm, dt)
+            g = self.gamma.float()
+            f = autograd.mlp(h, self.pwconv1, _Lin(self.pwconv2.weight * g[:, None], self.pwconv2.bias * g), "gelu", dt)
+            return x + f.view(x.shape).to(x.dtype)
+        autograd.check_dwconv7x7(self.dwconv)
+        w49, b = autograd.dwconv7x7_weights(self.dwconv)
+        h = engine.layernorm(ops.dwconv7x7_nhwc(x, w49, b).view(-1, C), self.norm, dt)
+        x2d = x.view(-1, C)
+        out = engine.mlp(h, self.pwconv1, self.pwconv2, "gelu", x2d, x2d.dtype, fc2_wb=engine.layerscale_lin_weights(self.pwconv2, self.gamma, dt))
+        return out.view(x.shape)
+
+
+def _down2_lin(conv, train: bool, dt) -> _Lin:
+    "the [Cout, 4 Cin] linear of Conv2d(k = 2, stride = 2) on uc_patch2_gather_nhwc's rows: K permuted to (ky, kx, c)"
+    if train:
+        return _Lin(conv.weight.permute(0, 2, 3, 1).reshape(conv.out_channels, -1), conv.bias)
+    w, b = engine.prepared(conv, ("p2", dt), (conv.weight, conv.bias),
+                           lambda: (conv.weight.detach().permute(0, 2, 3, 1).reshape(conv.out_channels, -1).to(dt).contiguous(),
+                                    conv.bias.detach().float().contiguous()))
+    return _Lin(w, b)
+
+
+class DINOv3ConvNextParams(nn.Module):
+    "Parameters of a DINOv3 ConvNeXt under the original ConvNeXt names (`model.*` inside DINOv3ConvNextEncoder)."
+
+    def __init__(self, size):
+        super().__init__()
+        widths, depths = resolve_convnext_size(size)
+        self.widths, self.depths = widths, depths
+        self.downsample_layers = nn.ModuleList(
+            [nn.Sequential(nn.Conv2d(3, widths[0], kernel_size=STEM_PATCH, stride=STEM_PATCH), nn.LayerNorm(widths[0], eps=1e-6))] +
+            [nn.Sequential(nn.LayerNorm(widths[i - 1], eps=1e-6), nn.Conv2d(widths[i - 1], widths[i], kernel_size=2, stride=2)) for i in range(1, 4)])
+        self.stages = nn.ModuleList([nn.Sequential(*[_ConvNextLayer(widths[i]) for _ in range(depths[i])]) for i in range(4)])
+        self.norm = nn.LayerNorm(widths[-1], eps=1e-6)
+
+
+class DINOv3ConvNextEncoder(UniCeptionEncoderBase):
+    """UniCeption DINOv3 ConvNext Encoder.  dinov3_repo_dir and weights are accepted and unused (there is no torch.hub here: the
+    architecture is built directly); `pretrained_checkpoint_path` is a {"model": state_dict of this wrapper} file.  size: a name
+    (tiny | small | base | large), or a dict(hidden_sizes=, depths=).  The features are the final-normed last stage, [B, C, H/32, W/32]."""
+
+    def __init__(self, name: str, dinov3_repo_dir: Optional[str] = None, data_norm_type: str = "dinov3", patch_size: int = 16,
+                 size="large", weights: Optional[str] = None, pretrained_checkpoint_path: Optional[str] = None, *args, **kwargs):
+        super().__init__(name=name, data_norm_type=data_norm_type, *args, **kwargs)
+        self.patch_size = patch_size
+        self.final_layer_patch_size = 32          # DINOv3 ConvNext uses a final patch size of 32
+        self.version = size
+        widths, _ = resolve_convnext_size(size)
+        self.enc_embed_dim = widths[-1] if isinstance(size, dict) else _CONVNEXT_EMBED_DIM[size]
+        self.model = DINOv3ConvNextParams(size)
+        self.model.patch_size = self.patch_size
+        if pretrained_checkpoint_path:
+            print(f"Loading custom pretrained DINOv3 checkpoint from {pretrained_checkpoint_path}")
+            ckpt = torch.load(pretrained_checkpoint_path, map_location="cpu", weights_only=False)
+            print(self.load_state_dict(ckpt["model"]))
+
+    def _check(self, encoder_input):
+        self._check_data_normalization_type(encoder_input.data_norm_type)
+        assert isinstance(encoder_input.image, torch.Tensor), "Input must be a torch.Tensor"
+        assert encoder_input.image.ndim == 4, "Input must be of shape (B, C, H, W)"
+        B, C, H, W = encoder_input.image.shape
+        assert C == 3, "Input must have 3 channels"
+        assert H % self.patch_size == 0 and W % self.patch_size == 0, \
+            f"Input shape must be divisible by patch size: {self.patch_size}"
+        if H % STEM_PATCH or W % STEM_PATCH:
+            raise engine.UcHipError(f"DINOv3 ConvNeXt: the {STEM_PATCH}x{STEM_PATCH} stem needs H ({H}) and W ({W}) divisible by {STEM_PATCH}")
+        return B, H, W
+
+    def _stem(self, image, B, H, W, dt, train):
+        "NHWC [B, H/4, W/4, C0] in stage 0's stream dtype: 4x4 patch rows (K = 48 zero-padded to 64) -> GEMM -> LayerNorm"
+        conv, ln = self.model.downsample_layers[0]
+        C0 = conv.out_channels
+        sdt = engine.stream_dtype(dt, C0)
+        img = image.float().contiguous() if (image.dtype != torch.float32 or not image.is_contiguous()) else image
+        if train:
+            rows = autograd.unshuffle_rows(img, STEM_PATCH, STEM_KPAD, dt)
+            w = torch.nn.functional.pad(conv.weight.reshape(C0, -1), (0, STEM_KPAD - 3 * STEM_PATCH * STEM_PATCH))
+            tok = autograd.linear(rows, w, conv.bias, conv, dt, torch.float32)
+            x = autograd.layer_norm(tok, ln, sdt)
+        else:
+            w, b = engine.patch_weights_padded(conv, dt, STEM_KPAD)
+            tok = ops.gemm(ops.unshuffle_rows(img, STEM_PATCH, STEM_KPAD, dt), w, b, out_dtype=torch.float32)
+            x = engine.layernorm(tok, ln, sdt)
+        return x.view(B, H // STEM_PATCH, W // STEM_PATCH, C0)
+
+    def _downsample(self, x, i, dt, train):
+        "stage i - 1's output NHWC -> stage i's input: LayerNorm -> 2x2 / stride-2 patch rows -> GEMM (an odd last row / column is dropped)"
+        ln, conv = self.model.downsample_layers[i]
+        B, H, W, C = x.shape
+        sdt = engine.stream_dtype(dt, conv.out_channels)
+        lin = _down2_lin(conv, train, dt)
+        if train:
+            h = autograd.layer_norm(x.reshape(-1, C), ln, dt).view(B, H, W, C)
+            y = autograd.linear(autograd.patch2_gather(h), lin.weight, lin.bias, conv, dt, sdt)
+        else:
+            h = engine.layernorm(x.view(-1, C), ln, dt).view(B, H, W, C)
+            y = ops.gemm(ops.patch2_gather_nhwc(h), lin.weight, lin.bias, out_dtype=sdt)
+        return y.view(B, H // 2, W // 2, conv.out_channels)
+
+    def _stage_outputs(self, encoder_input, upto: int = 3):
+        "generator of (stage index, NHWC output of that stage) for stages 0..upto"
+        B, H, W = self._check(encoder_input)
+        image = encoder_input.image
+        dt = engine.compute_dtype()
+        train = autograd.grad_needed(image, *self.model.parameters())
+        x = self._stem(image, B, H, W, dt, train)
+        for i in range(upto + 1):
+            if i > 0:
+                x = self._downsample(x, i, dt, train)
+            for layer in self.model.stages[i]:
+                x = layer.forward_rows(x, dt)
+            yield i, x
+
+    def _to_nchw(self, x, norm: bool):
+        "NHWC stage output -> fp32 NCHW, through the final norm (per pixel) when asked"
+        B, H, W, C = x.shape
+        if norm:
+            x = engine.layernorm(x.reshape(-1, C), self.model.norm, torch.float32).view(B, H, W, C)
+        if x.requires_grad:           # training: a plain (differentiable) permute
+            return x.float().permute(0, 3, 1, 2)
+        return ops.nhwc_to_nchw(x.contiguous(), torch.float32)
+
+    def forward(self, encoder_input: ViTEncoderInput) -> ViTEncoderOutput:
+        "the final-normed last-stage map (the published `forward_features(...)[\"x_norm_patchtokens\"]` reshaped) as [B, C, H/32, W/32]"
+        for i, x in self._stage_outputs(encoder_input):
+            pass
+        return ViTEncoderOutput(features=self._to_nchw(x, True))
+
+
+class DINOv3ConvNextIntermediateFeatureReturner(DINOv3ConvNextEncoder, IntermediateFeatureReturner):
+    """Intermediate Feature Returner for UniCeption DINOv3 ConvNext Encoder.  `indices` selects among the FOUR stage outputs (None: all,
+    an int n: the last n, a list: those); each is handed out as fp32 NCHW at its native stride (4, 8, 16, 32).  norm_intermediate=True
+    applies the final `norm` to stage 3 only — the one stage whose width it has; stages 0-2 are handed out as they are.  Resampling the
+    stage maps to the `patch_size` grid (what the hub model may do with `model.patch_size`: UNVERIFIED) is not built."""
+
+    def __init__(self, name: str, dinov3_repo_dir: Optional[str] = None, data_norm_type: str = "dinov3", patch_size: int = 16,
+                 size="large", weights: Optional[str] = None, pretrained_checkpoint_path: Optional[str] = None,
+                 indices: Optional[Union[int, List[int]]] = 1, norm_intermediate: bool = True, *args, **kwargs):
+        DINOv3ConvNextEncoder.__init__(self, name=name, data_norm_type=data_norm_type, patch_size=patch_size, size=size,
+                                       dinov3_repo_dir=dinov3_repo_dir, weights=weights,
+                                       pretrained_checkpoint_path=pretrained_checkpoint_path, *args, **kwargs)
+        IntermediateFeatureReturner.__init__(self, indices=indices, norm_intermediate=norm_intermediate)
+
+    def forward(self, encoder_input: ViTEncoderInput) -> List[ViTEncoderOutput]:
+        n = len(self.model.downsample_layers)
+        if self.indices is None:
+            self.indices = range(n)
+        take, last = feature_take_indices(n, self.indices)
+        outs = []
+        for i, x in self._stage_outputs(encoder_input, upto=last):
+            if i in take:
+                outs.append(ViTEncoderOutput(features=self._to_nchw(x, self.norm_intermediate and i == n - 1)))
         return outs

@@ -1674,3 +1674,57 @@ def softmax_rows_bwd(p: torch.Tensor, dp: torch.Tensor, N: int, scale: float) ->
     _lib.check(_lib.load().uc_softmax_rows_bwd(p.data_ptr(), dp.data_ptr(), dp.stride(0), ds.data_ptr(), _dt(p.dtype), p.shape[1], p.shape[0], N,
                                                float(scale), _stream()), "uc_softmax_rows_bwd")
     return ds
+
+
+# ---- DINOv3 ConvNeXt: depthwise 7x7 convolution and the stage downsample's operand rows (csrc/dwconv.hip) --------------------------
+def dwconv7x7_nhwc(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, flip: bool = False) -> torch.Tensor:
+    """Depthwise 7x7 / padding 3 convolution of NHWC x [B,H,W,C] (f32 | bf16 | f16): w fp32 [49, C] tap-major, bias fp32 [C] or None.
+    flip: tap 48 - t in place of t — the data gradient of the same convolution (uc_dwconv7x7_nhwc)."""
+    B, H, W, Cn = _nhwc4(x)
+    _need_gpu(w, bias)
+    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (49, Cn)
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == Cn)
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().uc_dwconv7x7_nhwc(x.data_ptr(), w.data_ptr(), _p(bias), y.data_ptr(), _dt(x.dtype), B, H, W, Cn, int(bool(flip)), _stream()),
+               "uc_dwconv7x7_nhwc")
+    return y
+
+
+def dwconv7x7_nhwc_wgrad(x: torch.Tensor, dy: torch.Tensor, bias: bool = True, ws: Optional[torch.Tensor] = None):
+    """(dw fp32 [49, C], db fp32 [C] | None) of dwconv7x7_nhwc for NHWC x and dy of one dtype (uc_dwconv7x7_nhwc_wgrad).  ws: an fp32
+    workspace of at least uc_dwconv7x7_nhwc_wgrad_ws_bytes(B, H, W, C) bytes; allocated here when None."""
+    B, H, W, Cn = _nhwc4(x)
+    _need_gpu(dy, ws)
+    assert dy.shape == x.shape and dy.dtype == x.dtype and dy.is_contiguous()
+    lib = _lib.load()
+    need = lib.uc_dwconv7x7_nhwc_wgrad_ws_bytes(B, H, W, Cn)
+    if ws is None:
+        ws = torch.empty(max(1, need // 4), dtype=torch.float32, device=x.device)
+    elif ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() * 4 < need:
+        raise UcHipError(f"uc_dwconv7x7_nhwc_wgrad: the workspace holds {ws.numel() * ws.element_size()} bytes of {ws.dtype}, "
+                         f"B={B} H={H} W={W} C={Cn} needs {need} bytes of contiguous fp32")
+    dw = torch.empty((49, Cn), dtype=torch.float32, device=x.device)
+    db = torch.empty(Cn, dtype=torch.float32, device=x.device) if bias else None
+    _lib.check(lib.uc_dwconv7x7_nhwc_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _p(db), ws.data_ptr(), _dt(x.dtype), B, H, W, Cn, _stream()),
+               "uc_dwconv7x7_nhwc_wgrad")
+    return dw, db
+
+
+def patch2_gather_nhwc(x: torch.Tensor) -> torch.Tensor:
+    """NHWC x [B,H,W,C] -> operand rows [B*(H//2)*(W//2), 4C], K ordered (ky,kx,c), of Conv2d(k = 2, stride = 2); an odd last row or
+    column is dropped (uc_patch2_gather_nhwc)."""
+    B, H, W, Cn = _nhwc4(x)
+    rows = torch.empty((B * (H // 2) * (W // 2), 4 * Cn), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.load().uc_patch2_gather_nhwc(x.data_ptr(), rows.data_ptr(), _dt(x.dtype), B, H, W, Cn, _stream()), "uc_patch2_gather_nhwc")
+    return rows
+
+
+def patch2_gather_nhwc_bwd(drows: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+    "adjoint of patch2_gather_nhwc: drows [B*(H//2)*(W//2), 4C] -> dx [B,H,W,C], zero in an odd last row or column"
+    _need_gpu(drows)
+    assert drows.dim() == 2 and drows.is_contiguous() and drows.shape[0] == B * (H // 2) * (W // 2) and drows.shape[1] % 4 == 0
+    Cn = drows.shape[1] // 4
+    dx = torch.empty((B, H, W, Cn), dtype=drows.dtype, device=drows.device)
+    _lib.check(_lib.load().uc_patch2_gather_nhwc_bwd(drows.data_ptr(), dx.data_ptr(), _dt(drows.dtype), B, H, W, Cn, _stream()),
+               "uc_patch2_gather_nhwc_bwd")
+    return dx

@@ -34,6 +34,11 @@ PerceptionEncoder(pretrained_checkpoint_path=...) loads.  A missing or unexpecte
 (a missing key bias becomes zeros), attn.qkv.bias_mask (1 | 0 | 1) and rope_embed.periods synthesised, layer_scale*.lambda1 ->
 ls*.gamma, register_tokens -> storage_tokens, gate_proj / up_proj / down_proj -> w1 / w2 / w3 (up_proj / down_proj -> fc1 / fc2
 without a gate).  An unexpected key is an error that names it.
+
+--mode dinov3_convnext: the state_dict of a transformers DINOv3ConvNextModel -> the {"model": {"model." + key: tensor}} file that
+DINOv3ConvNextEncoder(pretrained_checkpoint_path=...) loads: model.stages.i.downsample_layers.k -> downsample_layers.i.k,
+model.stages.i.layers.j.{depthwise_conv, layer_norm, pointwise_conv1, pointwise_conv2, gamma} -> stages.i.j.{dwconv, norm, pwconv1,
+pwconv2, gamma}, layer_norm -> norm.  An unexpected key is an error that names it.
 """
 import argparse
 import os
@@ -268,11 +273,42 @@ def dinov3_hf_to_uniception(ckpt: Dict, num_heads: Optional[int] = None, rope_ba
     return {prefix + k: v for k, v in out.items()}
 
 
+_CONVNEXT_LAYER = {"depthwise_conv": "dwconv", "layer_norm": "norm", "pointwise_conv1": "pwconv1", "pointwise_conv2": "pwconv2"}
+
+
+def dinov3_convnext_hf_to_uniception(ckpt: Dict, prefix: str = "model.") -> Dict[str, torch.Tensor]:
+    """The state_dict of DINOv3ConvNextEncoder (keys under `prefix`) from a transformers DINOv3ConvNextModel state_dict (the bare
+    dict, or under "state_dict" / "model").  KeyError naming the first key without a counterpart."""
+    sd = ckpt
+    for wrap in ("state_dict", "model"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+    out = {}
+    for k, v in sd.items():
+        md = re.match(r"(?:model\.)?stages\.(\d+)\.downsample_layers\.(\d+)\.(weight|bias)$", k)
+        ml = re.match(r"(?:model\.)?stages\.(\d+)\.layers\.(\d+)\.(depthwise_conv|layer_norm|pointwise_conv1|pointwise_conv2)\.(weight|bias)$", k)
+        mg = re.match(r"(?:model\.)?stages\.(\d+)\.layers\.(\d+)\.gamma$", k)
+        mn = re.match(r"layer_norm\.(weight|bias)$", k)
+        if md:
+            out[f"downsample_layers.{md.group(1)}.{md.group(2)}.{md.group(3)}"] = v
+        elif ml:
+            out[f"stages.{ml.group(1)}.{ml.group(2)}.{_CONVNEXT_LAYER[ml.group(3)]}.{ml.group(4)}"] = v
+        elif mg:
+            out[f"stages.{mg.group(1)}.{mg.group(2)}.gamma"] = v
+        elif mn:
+            out[f"norm.{mn.group(1)}"] = v
+        else:
+            raise KeyError(f"unexpected key {k} in a transformers DINOv3ConvNextModel state_dict")
+    if "norm.weight" not in out:
+        raise KeyError("missing key layer_norm.weight: not a transformers DINOv3ConvNextModel state_dict")
+    return {prefix + k: v for k, v in out.items()}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("original")
     ap.add_argument("out")
-    ap.add_argument("--mode", default="dust3r", choices=("dust3r", "perception_encoder", "dinov3"))
+    ap.add_argument("--mode", default="dust3r", choices=("dust3r", "perception_encoder", "dinov3", "dinov3_convnext"))
     ap.add_argument("--num-heads", type=int, default=None, help="dinov3 mode: the model's attention head count (default: embed dim / 64)")
     ap.add_argument("--pe-config", default=None, help="perception_encoder mode: the vision tower's config name, e.g. PE-Core-L14-336")
     ap.add_argument("--per-module-dir", default=None, help="also write encoder / info_sharing / head checkpoints there")
@@ -289,6 +325,11 @@ def main(argv=None):
         converted = dinov3_hf_to_uniception(ckpt, a.num_heads)
         torch.save({"model": converted}, a.out)
         print(f"wrote {a.out}: {len(converted)} entries of a DINOv3 ViT")
+        return
+    if a.mode == "dinov3_convnext":
+        converted = dinov3_convnext_hf_to_uniception(ckpt)
+        torch.save({"model": converted}, a.out)
+        print(f"wrote {a.out}: {len(converted)} entries of a DINOv3 ConvNeXt")
         return
     sd = ckpt["model"] if "model" in ckpt else ckpt
     converted, dropped = original_to_uniception(sd)
