@@ -212,12 +212,13 @@ def test_group_norm_silu_arguments_are_checked_before_any_launch():
     base = dict(x=P, y=P, gamma=P, beta=P, mean=P, rstd=P, ws=P, dtype=1, B=2, H=5, W=7, C=64, G=2, eps=1e-6)
     for kw, needle in ((dict(C=64, G=3), "C (64) is not a multiple of G (3)"), (dict(C=48, G=4), "channels per group (12) must be a multiple of 8 (or 4)"),
                        (dict(dtype=3), "unsupported dtype 3"), (dict(beta=None), "null pointer"), (dict(eps=0.0), "eps must be positive"),
-                       (dict(x=P + 8), "16-byte aligned")):
+                       (dict(x=P + 8), "16-byte aligned"), (dict(C=12, G=3), "C=12 G=3 (C must be a multiple of 8)")):
         a = dict(base, **kw)
         _rejects(lib, "uc_group_norm_silu_nhwc", (a["x"], a["y"], a["gamma"], a["beta"], a["mean"], a["rstd"], a["ws"], a["dtype"], a["B"],
                                                   a["H"], a["W"], a["C"], a["G"], a["eps"], None), needle)
     for kw, needle in ((dict(beta=None), "null pointer"), (dict(dx=None), "null pointer"), (dict(C=48, G=4), "(or 4)"),
-                       (dict(dtype=-1), "unsupported dtype -1"), (dict(beta=P + 4), "beta must be 16-byte aligned")):
+                       (dict(dtype=-1), "unsupported dtype -1"), (dict(beta=P + 4), "beta must be 16-byte aligned"),
+                       (dict(C=12, G=3), "C=12 G=3 (C must be a multiple of 8)")):
         a = dict(dict(dy=P, x=P, mean=P, rstd=P, gamma=P, beta=P, dx=P, dgamma=P, dbeta=P, ws=P, dtype=1, B=2, H=5, W=7, C=64, G=2), **kw)
         _rejects(lib, "uc_group_norm_silu_nhwc_bwd", (a["dy"], a["x"], a["mean"], a["rstd"], a["gamma"], a["beta"], a["dx"], a["dgamma"],
                                                       a["dbeta"], a["ws"], a["dtype"], a["B"], a["H"], a["W"], a["C"], a["G"], None), needle)
@@ -226,6 +227,10 @@ def test_group_norm_silu_arguments_are_checked_before_any_launch():
     assert lib.uc_group_norm_nhwc_ws_bytes(2, 8, 8, 128, 32) == 0 and lib.uc_group_norm_nhwc_bwd_ws_bytes(2, 8, 8, 128, 32) == 0
     assert lib.uc_group_norm_silu_nhwc_ws_bytes(2, 8, 8, 256, 32) == lib.uc_group_norm_nhwc_ws_bytes(2, 8, 8, 256, 32) > 0
     assert lib.uc_group_norm_silu_nhwc_ws_bytes(2, 8, 8, 48, 4) == 0
+    # groups of four with an odd G: C % 8 == 4, no work item of 8 channels fits; none of the four sizes a workspace for it
+    for fn in ("uc_group_norm_nhwc_ws_bytes", "uc_group_norm_silu_nhwc_ws_bytes", "uc_group_norm_nhwc_bwd_ws_bytes", "uc_group_norm_silu_nhwc_bwd_ws_bytes"):
+        assert getattr(lib, fn)(2, 5, 7, 12, 3) == 0, fn
+    assert lib.uc_group_norm_silu_nhwc_ws_bytes(2, 5, 7, 8, 2) > 0 and lib.uc_group_norm_silu_nhwc_bwd_ws_bytes(2, 5, 7, 8, 2) > 0
 
 
 @pytest.mark.parametrize("fn", ["uc_down2_gather", "uc_down2_gather_bwd", "uc_upsample2_nhwc", "uc_upsample2_nhwc_bwd"])

@@ -16,33 +16,9 @@
 //     kernel adds the chunks in a fixed order (four interleaved chains, combined in chain order) and forms the two group sums
 //     sum g gamma and sum g gamma x^ from the per-channel sums (they are gamma-weighted sums of those); a third adds the samples for
 //     dgamma / dbeta; the fourth writes dx.  Fixed order everywhere: two calls give the same bits.
+// The geometry (GnGeom, gn_geom, gn_group), the constants and the one shape rule live in groupnorm_plan.h, which the host compiler builds too.
 #include "vec_access.h"
-
-#define GN_THREADS 256
-#define GN_VECS 8            // 8-channel vectors per thread and chunk (64 values in registers)
-#define GN_MAX_C 2048        // C / 8 <= 256: one pixel never spans more than one workgroup row
-
-struct GnGeom {
-    int HW, C, G, C8, cg8, rows, chunk_pix, nchunk;
-    int cg, half;      // channels per group; half: cg == 4, the two halves of an 8-channel vector belong to groups 2 c8 and 2 c8 + 1
-};
-// group of half `hi` (0: channels 0..3, 1: channels 4..7) of channel vector c8
-__host__ __device__ __forceinline__ int gn_group(const GnGeom& gm, int c8, int hi) { return gm.half ? 2 * c8 + hi : c8 / gm.cg8; }
-
-static inline GnGeom gn_geom(int64_t H, int64_t W, int64_t C, int64_t G) {
-    GnGeom g;
-    g.HW = (int)(H * W);
-    g.C = (int)C;
-    g.G = (int)G;
-    g.C8 = (int)(C / 8);
-    g.cg8 = (int)(C / G / 8);
-    g.cg = (int)(C / G);
-    g.half = g.cg == 4;
-    g.rows = GN_THREADS / g.C8;
-    g.chunk_pix = g.rows * GN_VECS;
-    g.nchunk = (g.HW + g.chunk_pix - 1) / g.chunk_pix;
-    return g;
-}
+#include "groupnorm_plan.h"
 
 // ---- workgroup reduction: per-thread value -> per-group value (threads are (row, channel vector); a group is cg8 adjacent vectors).
 // Fixed order: rows ascending, then vectors ascending.  Result in s_grp[0..G); the caller synchronises before reading it.
@@ -390,31 +366,23 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const typename Tag::s
 // group4: groups of 4 channels are accepted too (the SiLU entry points)
 static int gn_check_shape(const char* fn, int dtype, int B, int H, int W, int C, int G, bool group4 = false) {
     UC_REQUIRE_DTYPE(fn, dtype, true);
-    UC_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && G > 0, "%s: bad shape B=%d H=%d W=%d C=%d G=%d", fn, B, H, W, C, G);
-    UC_REQUIRE(C % G == 0, "%s: C (%d) is not a multiple of G (%d)", fn, C, G);
-    UC_REQUIRE((C / G) % 8 == 0 || (group4 && C / G == 4), "%s: channels per group (%d) must be a multiple of 8%s", fn, C / G, group4 ? " (or 4)" : "");
-    UC_REQUIRE(C <= GN_MAX_C, "%s: C (%d) exceeds %d", fn, C, GN_MAX_C);
-    UC_REQUIRE(B <= 65535 && (int64_t)H * W <= 0x7fffffff && (int64_t)B * G <= 0x7fffffff &&
-                   ((int64_t)B * H * W * (C / 8) + 255) / 256 <= 0x7fffffff,
-               "%s: grid limit exceeded (B <= 65535, H * W < 2^31, B * H * W * C < 2^42)", fn);
+    const GnShape rule = gn_shape_rule(B, H, W, C, G, group4);      // the one rule of groupnorm_plan.h; here only its messages
+    UC_REQUIRE(rule != GN_SHAPE_DIMS, "%s: bad shape B=%d H=%d W=%d C=%d G=%d", fn, B, H, W, C, G);
+    UC_REQUIRE(rule != GN_SHAPE_C_MOD_G, "%s: C (%d) is not a multiple of G (%d)", fn, C, G);
+    UC_REQUIRE(rule != GN_SHAPE_GROUP, "%s: channels per group (%d) must be a multiple of 8%s", fn, C / G, group4 ? " (or 4)" : "");
+    UC_REQUIRE(rule != GN_SHAPE_C_MOD_8, "%s: bad shape B=%d H=%d W=%d C=%d G=%d (C must be a multiple of 8)", fn, B, H, W, C, G);
+    UC_REQUIRE(rule != GN_SHAPE_MAX_C, "%s: C (%d) exceeds %d", fn, C, GN_MAX_C);
+    UC_REQUIRE(rule != GN_SHAPE_GRID, "%s: grid limit exceeded (B <= 65535, H * W < 2^31, B * H * W * C < 2^42)", fn);
     return UC_OK;
 }
 
-static bool gn_shape_ok(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G, bool group4) {
-    return B > 0 && H > 0 && W > 0 && C > 0 && G > 0 && C % G == 0 && ((C / G) % 8 == 0 || (group4 && C / G == 4)) && C <= GN_MAX_C;
-}
-static int64_t gn_fwd_ws(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
-    return B * (int64_t)gn_geom(H, W, C, G).nchunk * G * (int64_t)sizeof(float2);
-}
-static int64_t gn_bwd_ws(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
-    return (B * (int64_t)gn_geom(H, W, C, G).nchunk * 2 * C + B * 2 * C + B * G * 2) * (int64_t)sizeof(float);
-}
+static_assert(sizeof(float2) == 8, "gn_fwd_ws_bytes counts (mean, M2) as 8 bytes");
 
 extern "C" int64_t uc_group_norm_nhwc_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
-    return gn_shape_ok(B, H, W, C, G, false) ? gn_fwd_ws(B, H, W, C, G) : 0;
+    return gn_shape_ok(B, H, W, C, G, false) ? gn_fwd_ws_bytes(B, H, W, C, G) : 0;
 }
 extern "C" int64_t uc_group_norm_silu_nhwc_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
-    return gn_shape_ok(B, H, W, C, G, true) ? gn_fwd_ws(B, H, W, C, G) : 0;
+    return gn_shape_ok(B, H, W, C, G, true) ? gn_fwd_ws_bytes(B, H, W, C, G) : 0;
 }
 
 static int gn_forward(const char* fn, const void* x, void* y, const float* gamma, const float* beta, float* mean, float* rstd, float* ws,
@@ -461,10 +429,10 @@ extern "C" int uc_group_norm_silu_nhwc(const void* x, void* y, const float* gamm
 }
 
 extern "C" int64_t uc_group_norm_nhwc_bwd_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
-    return gn_shape_ok(B, H, W, C, G, false) ? gn_bwd_ws(B, H, W, C, G) : 0;
+    return gn_shape_ok(B, H, W, C, G, false) ? gn_bwd_ws_bytes(B, H, W, C, G) : 0;
 }
 extern "C" int64_t uc_group_norm_silu_nhwc_bwd_ws_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int64_t G) {
-    return gn_shape_ok(B, H, W, C, G, true) ? gn_bwd_ws(B, H, W, C, G) : 0;
+    return gn_shape_ok(B, H, W, C, G, true) ? gn_bwd_ws_bytes(B, H, W, C, G) : 0;
 }
 
 // beta != NULL: the fused SiLU's backward (gate unused); gate != NULL: the fused ReLU's
