@@ -799,6 +799,21 @@ def cross_attn_sublayer(x2d, y2d, ln, lny, ca, B, Nq, Nk, H, rope, qpos, kpos, s
                                      getattr(kn, "bias", None), qn, kn, drops, gamma, attn_drop)
 
 
+def _mlp_bwd(dyb, h, u, a, fc1, fc2, gamma, act, dt, has_b1, has_b2, drops):
+    """(dW2, db2, dgamma, du, dW1, db1) of fc2(act(fc1(h))) for the already-dropped cotangent dyb (u: the pre-activation, a: fc2's
+    operand): what the backwards of MlpSubLayerFn and MlpFn share."""
+    dW2, db2, dgamma, w2t = _out_linear_bwd(dyb, a, fc2, gamma, has_b2, dt)
+    if act != "none" and dt == torch.bfloat16 and w2t.shape[1] % 64 == 0:
+        du = ops.gemm(dyb, w2t, dact=(u, act))          # act'(u) applied in the data-gradient GEMM's epilogue
+    else:
+        da = ops.gemm(dyb, w2t)
+        du = ops.act_bwd(da, u, act) if act != "none" else da
+    if drops is not None and drops.mid is not None:      # (elementwise factors commute: mask * act'(u) * da)
+        du = ops.mask_scale(du, drops.mid, 0, drops.mid_scale)
+    dW1, db1 = _wgrad(du, h, dt, has_b1, sink=[(fc1.weight, 0, fc1.weight.shape[0])], bias_sink=[fc1.bias])
+    return dW2, db2, dgamma, du, dW1, db1
+
+
 @_sink_aware
 class MlpSubLayerFn(Function):
     """x + fc2(act(fc1(LN(x))))   (blocks.py:64-86,159; transformer_blocks.py:517-560)."""
@@ -839,15 +854,7 @@ class MlpSubLayerFn(Function):
         dyb = _as_dt(dxo, dt)
         if drops is not None and drops.has_out:
             dyb = _drop_out(dyb, drops)
-        dW2, db2, dgamma, w2t = _out_linear_bwd(dyb, a, fc2, gamma, has_b2, dt)
-        if act != "none" and dt == torch.bfloat16 and w2t.shape[1] % 64 == 0:
-            du = ops.gemm(dyb, w2t, dact=(u, act))          # act'(u) applied in the data-gradient GEMM's epilogue
-        else:
-            da = ops.gemm(dyb, w2t)
-            du = ops.act_bwd(da, u, act) if act != "none" else da
-        if drops is not None and drops.mid is not None:      # (elementwise factors commute: mask * act'(u) * da)
-            du = ops.mask_scale(du, drops.mid, 0, drops.mid_scale)
-        dW1, db1 = _wgrad(du, h, dt, has_b1, sink=[(fc1.weight, 0, fc1.weight.shape[0])], bias_sink=[fc1.bias])
+        dW2, db2, dgamma, du, dW1, db1 = _mlp_bwd(dyb, h, u, a, fc1, fc2, gamma, act, dt, has_b1, has_b2, drops)
         dh = ops.gemm(du, lin_weight_t(fc1, dt))
         dx, dg, db = _ln_bwd_tail(x2d, ln, g, dh, dxo, dt)
         return (dx, dg, db, dW1, db1, dW2, db2) + (None,) * 5 + (dgamma, None)
@@ -1001,61 +1008,73 @@ def convert(x, dt):
     return ConvertFn.apply(x, dt)
 
 
-def _conv3x3_rot_weight(conv, dt):
-    """GEMM weight of the data gradient: [Cin, 9*Cout] with K ordered (ky', kx', o) = W[o, c, 2-ky', 2-kx']."""
-    return engine.prepared(conv, ("c3rot", dt), (conv.weight,),
-                           lambda: conv.weight.detach().flip(2, 3).permute(1, 2, 3, 0).reshape(conv.in_channels, -1).to(dt).contiguous())
+def _conv3x3_rot_weight(conv, dt, cin_pad: int, cout_pad: int):
+    """GEMM weight of the data gradient: [cin_pad, 9*cout_pad] with K ordered (ky', kx', o) = W[o, c, 2-ky', 2-kx']: the forward layout of
+    the flipped, transposed weight."""
+    return engine.prepared(conv, ("c3rot", dt, cin_pad, cout_pad), (conv.weight,),
+                           lambda: engine.conv3x3_weight2d(conv.weight.flip(2, 3).transpose(0, 1), cout_pad, cin_pad).to(dt).contiguous())
 
 
 @_sink_aware
 class Conv3x3Fn(Function):
-    """y = [residual +] act(conv3x3(relu?(x)) + b) on NHWC maps (dpt_block.py:17-289, dpt.py:116-178,271-277)."""
+    """y = [residual +] act(conv3x3(relu?(x)) + b) on NHWC maps (dpt_block.py:17-289, dpt.py:116-178,271-277).  x may carry zero
+    channels beyond conv.in_channels and y zero channels up to `cout_pad` (zero weight columns / rows: the MoGe output block's
+    Conv2d(64 + 2 -> 32), the dense encoder's ResidualBlock); stride 1 without `relu_in` only.  out_dtype: of y, default x's."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, residual2, conv, relu_in, act, grad_mask_cell=None):
+    def forward(ctx, x, weight, bias, residual, residual2, conv, relu_in, act, grad_mask_cell=None, cout_pad=None, out_dtype=None):
         ctx.grad_mask_cell = grad_mask_cell
         x = _c(x)
-        B, H, W, Cin = x.shape
+        B, H, W, cin_pad = x.shape
         s = conv.stride[0]
-        w, b = engine.conv3x3_weights(conv, x.dtype)
+        if (cin_pad != conv.in_channels or (cout_pad or conv.out_channels) != conv.out_channels) and (s != 1 or relu_in):
+            raise UcHipError("conv3x3: zero-padded channel counts are for stride 1 without a fused input ReLU")
+        w, b = engine.conv3x3_weights(conv, x.dtype, cin_pad, cout_pad)
         Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
         r1 = None if residual is None else _c(residual).reshape(-1, residual.shape[-1])
         r2 = None if residual2 is None else _c(residual2).reshape(-1, residual2.shape[-1])
-        y = ops.gemm(x, w, b, act=act, residual=r1, residual2=r2, relu_a=relu_in, conv=(B, H, W, Cin, s)).view(B, Ho, Wo, -1)
+        y = ops.gemm(x, w, b, act=act, residual=r1, residual2=r2, relu_a=relu_in, conv=(B, H, W, cin_pad, s), out_dtype=out_dtype)
+        y = y.view(B, Ho, Wo, -1)
         if act not in (None, "none", "relu"):
             raise UcHipError(f"conv3x3 backward: unsupported fused activation {act}")
         if act == "relu" and residual is not None:
             raise UcHipError("conv3x3 backward: fused ReLU together with a residual is not used by the DPT head")
         ctx.save_for_backward(x, y if act == "relu" else torch.empty(0))
-        ctx.meta = (conv, relu_in, act, bias is not None, residual is not None, residual2 is not None, s)
+        ctx.meta = (conv, relu_in, act, bias is not None, s, [None if r is None else r.dtype for r in (residual, residual2)])
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, y = ctx.saved_tensors
-        conv, relu_in, act, has_b, has_r1, has_r2, s = ctx.meta
-        B, H, W, Cin = x.shape
+        conv, relu_in, act, has_b, s, res_dtypes = ctx.meta
+        B, H, W, cin_pad = x.shape
         dt = x.dtype
         dy = _c(dy)
-        Cout = dy.shape[-1]
+        cout_pad = dy.shape[-1]
         cell = ctx.grad_mask_cell
         already_masked = cell is not None and cell[0]          # the only consumer's backward applied this ReLU's mask (Conv1x1To4Fn)
         if cell is not None:
             cell[0] = False
-        dz = ops.act_bwd(dy, y, "relu") if (act == "relu" and not already_masked) else dy
-        dz2 = dz.view(-1, Cout)
-        dWg, db = _wgrad_conv(dz, x, s, relu_in, has_b)                          # [Cout, 9*Cin], K ordered (ky,kx,c)
-        dW = dWg.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2)
+        dz = _as_dt(dy, dt)
+        if act == "relu" and not already_masked:
+            dz = ops.act_bwd(dz, y, "relu")
+        if has_b and dy.dtype != dt:       # an fp32 cotangent (the head's last layer): the bias gradient sums it unrounded
+            dWg, db = _wgrad_conv(dz, x, s, relu_in)[0], _colsum(dy.view(-1, cout_pad))
+        else:
+            dWg, db = _wgrad_conv(dz, x, s, relu_in, has_b)                      # [cout_pad, 9*cin_pad], K ordered (ky,kx,c)
+        dW = dWg.view(cout_pad, 3, 3, cin_pad)[:conv.out_channels, :, :, :conv.in_channels].permute(0, 3, 1, 2)
         dx = None
         if ctx.needs_input_grad[0]:
             g = dz if s == 1 else ops.dilate_nhwc(dz, H, W, s)
-            if relu_in and dt == torch.bfloat16 and Cout % 64 == 0:
-                dx = ops.gemm(g, _conv3x3_rot_weight(conv, dt), conv=(B, H, W, Cout, 1), dact=(x.view(-1, Cin), "relu")).view(B, H, W, Cin)
+            wr = _conv3x3_rot_weight(conv, dt, cin_pad, cout_pad)
+            if relu_in and dt == torch.bfloat16 and cout_pad % 64 == 0:
+                dx = ops.gemm(g, wr, conv=(B, H, W, cout_pad, 1), dact=(x.view(-1, cin_pad), "relu")).view(B, H, W, cin_pad)
             else:
-                dx = ops.gemm(g, _conv3x3_rot_weight(conv, dt), conv=(B, H, W, Cout, 1)).view(B, H, W, Cin)
+                dx = ops.gemm(g, wr, conv=(B, H, W, cout_pad, 1)).view(B, H, W, cin_pad)
                 if relu_in:
                     dx = ops.act_bwd(dx, x, "relu")
-        return dx, dW, db, (dy if has_r1 else None), (dy if has_r2 else None), None, None, None, None
+        dr1, dr2 = (None if rdt is None or not ctx.needs_input_grad[i] else _as_dt(dy, rdt) for i, rdt in zip((3, 4), res_dtypes))
+        return dx, dW, (db[:conv.out_channels] if has_b else None), dr1, dr2, None, None, None, None, None, None
 
 
 def conv3x3(x, conv, relu_in=False, act=None, residual=None, residual2=None, grad_mask_cell=None):
@@ -1070,91 +1089,105 @@ def conv1x1(x, conv):
     return y.view(B, H, W, -1)
 
 
+def _padded_conv1x1_weight2d(conv, cpad):
+    "fp32 [cpad, Cin] of a Conv2d(k=1) weight: zero rows beyond conv.out_channels"
+    w = torch.zeros(cpad, conv.in_channels, device=conv.weight.device)
+    w[:conv.out_channels] = conv.weight.detach().reshape(conv.out_channels, -1).float()
+    return w
+
+
 def padded_conv1x1_weights(conv, dt, cpad):
     "Conv2d(k=1) weights with the output channels padded by zero rows to `cpad` (the 8-channel granule of the NHWC kernels)."
-    n = conv.out_channels
-
     def build():
-        w = torch.zeros(cpad, conv.in_channels, device=conv.weight.device)
-        w[:n] = conv.weight.detach().reshape(n, -1).float()
         b = torch.zeros(cpad, device=conv.weight.device)
         if conv.bias is not None:
-            b[:n] = conv.bias.detach().float()
-        return w.to(dt).contiguous(), b
+            b[:conv.out_channels] = conv.bias.detach().float()
+        return _padded_conv1x1_weight2d(conv, cpad).to(dt).contiguous(), b
     return engine.prepared(conv, ("c1pad", dt), (conv.weight, conv.bias), build)
 
 
 @_sink_aware
 class PaddedConv1x1Fn(Function):
-    """A 1x1 convolution to a channel count that is not a multiple of 8 (DPTSegmentationProcessor's class logits, dpt.py:314-381):
-    computed on `cpad` output columns (zero weight rows), fp32 output [M, cpad]; gradients of the real rows only."""
+    """A 1x1 convolution to a channel count that is not a multiple of 8 (DPTSegmentationProcessor's class logits, dpt.py:314-381; the
+    MoGe head's last conv): computed on `cpad` output columns (zero weight rows), fp32 output [M, cpad]; gradients of the real rows only.
+    fp32_bias: the bias gradient is the column sum of the fp32 cotangent itself, not of its copy rounded to the operand dtype (a sum
+    over every pixel of the image in which the rounding errors of the summands do not average out against a cancelling total)."""
 
     @staticmethod
-    def forward(ctx, x2d, weight, bias, conv, dt, cpad):
+    def forward(ctx, x2d, weight, bias, conv, dt, cpad, fp32_bias):
         x2d = _c(x2d)
         xb = x2d if x2d.dtype == dt else ops.convert(x2d, dt)
         w, b = padded_conv1x1_weights(conv, dt, cpad)
         ctx.save_for_backward(xb)
-        ctx.meta = (conv, dt, x2d.dtype, weight.shape, bias is not None, cpad)
+        ctx.meta = (conv, dt, x2d.dtype, weight.shape, bias is not None, cpad, fp32_bias)
         return ops.gemm(xb, w, b, out_dtype=torch.float32)
 
     @staticmethod
     def backward(ctx, dy):
         (xb,) = ctx.saved_tensors
-        conv, dt, x_dtype, wshape, has_b, cpad = ctx.meta
+        conv, dt, x_dtype, wshape, has_b, cpad, fp32_bias = ctx.meta
         n = wshape[0]
-        dyb = _as_dt(_c(dy), dt)
-        dW, db = _wgrad(dyb, xb, dt, has_b)
+        dy = _c(dy)
+        dyb = _as_dt(dy, dt)
+        dW, db = _wgrad(dyb, xb, dt, has_b and not fp32_bias)
+        if has_b and fp32_bias:
+            db = _colsum(dy)
         dx = None
         if ctx.needs_input_grad[0]:
-            def padded32():
-                w = torch.zeros(cpad, conv.in_channels, device=conv.weight.device)
-                w[:n] = conv.weight.detach().reshape(n, -1).float()
-                return w
-            dx = ops.gemm(dyb, _w_t(conv, "c1pad", (conv.weight,), padded32, dt), out_dtype=x_dtype)
-        return dx, dW[:n].reshape(wshape), (db[:n] if has_b else None), None, None, None
+            dx = ops.gemm(dyb, _w_t(conv, "c1pad", (conv.weight,), lambda: _padded_conv1x1_weight2d(conv, cpad), dt), out_dtype=x_dtype)
+        return dx, dW[:n].reshape(wshape), (db[:n] if has_b else None), None, None, None, None
 
 
-def padded_conv1x1(x, conv, dt, cpad):
+def padded_conv1x1(x, conv, dt, cpad, fp32_bias: bool = False):
     B, H, W, Cin = x.shape
-    return PaddedConv1x1Fn.apply(x.reshape(-1, Cin), conv.weight, conv.bias, conv, dt, cpad).view(B, H, W, cpad)
+    return PaddedConv1x1Fn.apply(x.reshape(-1, Cin), conv.weight, conv.bias, conv, dt, cpad, fp32_bias).view(B, H, W, cpad)
+
+
+def out_conv1x1(x, conv, dt, cpad):
+    "the head's last 1x1 convolution: padded_conv1x1 with the bias gradient summed from the fp32 cotangent"
+    return padded_conv1x1(x, conv, dt, cpad, fp32_bias=True)
 
 
 @_sink_aware
 class ConvTransposeFn(Function):
-    """ConvTranspose2d(kernel = stride, no padding) = GEMM to (u,v,o) columns + pixel scatter (dpt.py:116-140)."""
+    """ConvTranspose2d(kernel = stride, no padding) = GEMM to (u,v,o) columns + pixel scatter (dpt.py:116-140).  x may carry zero
+    channels beyond ct.in_channels (the K granule of the dense GEMM: 514 -> 576, ...), matched by zero weight columns."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, ct):
         x = _c(x)
-        B, H, W, Cin = x.shape
+        B, H, W, kpad = x.shape
         k = ct.kernel_size[0]
-        w, b = engine.convt_weights(ct, x.dtype)
-        x2 = x.view(-1, Cin)
+        w, b = engine.convt_weights(ct, x.dtype, kpad)
+        x2 = x.view(-1, kpad)
         y = ops.gemm(x2, w, b)
         ctx.save_for_backward(x2)
-        ctx.meta = (ct, k, (B, H, W, Cin), bias is not None)
+        ctx.meta = (ct, k, (B, H, W, kpad), bias is not None)
         return ops.convt_scatter(y, B, H, W, k, ct.out_channels)
 
     @staticmethod
     def backward(ctx, dy):
         (x2,) = ctx.saved_tensors
-        ct, k, (B, H, W, Cin), has_b = ctx.meta
+        ct, k, (B, H, W, kpad), has_b = ctx.meta
         dt = x2.dtype
         Cout = ct.out_channels
-        dyg = ops.convt_gather(_c(dy), k)                                        # [B*H*W, k*k*Cout]
-        dWg, dbg = _wgrad(dyg, x2, dt, has_b)                                    # [k*k*Cout, Cin], [k*k*Cout]
-        dW = dWg.view(k, k, Cout, Cin).permute(3, 2, 0, 1)
+        dyg = ops.convt_gather(_as_dt(_c(dy), dt), k)                            # [B*H*W, k*k*Cout]
+        dWg, dbg = _wgrad(dyg, x2, dt, has_b)                                    # [k*k*Cout, kpad], [k*k*Cout]
+        dW = dWg.view(k, k, Cout, kpad)[..., :ct.in_channels].permute(3, 2, 0, 1)
         db = dbg.view(k * k, Cout).sum(0) if has_b else None
         dx = None
         if ctx.needs_input_grad[0]:
-            wT = _w_t(ct, "ct", (ct.weight,),
-                      lambda: ct.weight.detach().permute(2, 3, 1, 0).reshape(k * k * Cout, Cin).float().contiguous(), dt)
-            dx = ops.gemm(dyg, wT).view(B, H, W, Cin)
+            dx = ops.gemm(dyg, _w_t(ct, ("ct", kpad), (ct.weight,), lambda: engine.convt_weight2d(ct, kpad), dt)).view(B, H, W, kpad)
         return dx, dW, db, None
 
 
 def conv_transpose_ks(x, ct):
+    return ConvTransposeFn.apply(x, ct.weight, ct.bias, ct)
+
+
+def conv_transpose_padded(x, ct):
+    if ct.kernel_size != ct.stride or ct.kernel_size[0] != ct.kernel_size[1] or ct.padding != (0, 0) or ct.output_padding != (0, 0):
+        raise UcHipError("conv_transpose_padded: only ConvTranspose2d(kernel = stride, no padding) has a HIP path")
     return ConvTransposeFn.apply(x, ct.weight, ct.bias, ct)
 
 
@@ -1523,38 +1556,54 @@ def token_pool(x2d, B: int, T: int):
 # channels make the channel counts 514 / 258 / 130 / 66: zero-padded to the GEMM's granule, the zero columns built into the
 # prepared weights), the sum of the 1x1 projections as one GEMM over K-concatenated operands, and the Mlp of MLPFeature.
 # =================================================================================================================
-def check_group_size(C: int, G: int, what: str = "group_norm") -> None:
-    "what uc_group_norm_nhwc would reject, said before any tensor is touched"
-    if G <= 0 or C % G != 0 or (C // G) % 8 != 0:
+def check_group_size(C: int, G: int, what: str = "group_norm", group4: bool = False) -> None:
+    "what uc_group_norm_nhwc (group4: uc_group_norm_silu_nhwc, which also takes 4 channels per group) would reject, said before any tensor is touched"
+    if G <= 0 or C % G != 0 or ((C // G) % 8 != 0 and not (group4 and C // G == 4)):
         raise UcHipError(f"{what}: {C} channels in {G} groups: channels per group ({C / max(G, 1):g}) must be a multiple of 8 "
-                         "(uc_group_norm_nhwc)")
+                         + ("or 4 (uc_group_norm_silu_nhwc)" if group4 else "(uc_group_norm_nhwc)"))
 
 
 @_sink_aware
 class GroupNormFn(Function):
-    "y = [relu](GroupNorm(x)) on an NHWC map (uc_group_norm_nhwc / uc_group_norm_nhwc_bwd)."
+    """y = act(GroupNorm(x)) on an NHWC map, act in ("none", "relu", "silu") (uc_group_norm_nhwc / uc_group_norm_silu_nhwc and their
+    _bwd).  The ReLU's backward gates on the saved output; the SiLU's recomputes the pre-activation from x and beta."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gn, relu):
+    def forward(ctx, x, weight, bias, gn, act):
         x = _c(x)
         g, b = engine.ln_params(gn)
-        y, mean, rstd = ops.group_norm_nhwc(x, g, b, gn.num_groups, gn.eps, relu)
-        ctx.save_for_backward(x, g, mean, rstd, y if relu else torch.empty(0))
-        ctx.relu = relu
+        if act == "silu":
+            y, mean, rstd = ops.group_norm_silu_nhwc(x, g, b, gn.num_groups, gn.eps)
+        else:
+            y, mean, rstd = ops.group_norm_nhwc(x, g, b, gn.num_groups, gn.eps, act == "relu")
+        ctx.save_for_backward(x, g, mean, rstd, {"none": torch.empty(0), "relu": y, "silu": b}[act])
+        ctx.act = act
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, g, mean, rstd, y = ctx.saved_tensors
-        dx, dg, db = ops.group_norm_nhwc_bwd(_as_dt(_c(dy), x.dtype), x, mean, rstd, g, gate=y if ctx.relu else None)
+        x, g, mean, rstd, aux = ctx.saved_tensors
+        dy = _as_dt(_c(dy), x.dtype)
+        if ctx.act == "silu":
+            dx, dg, db = ops.group_norm_silu_nhwc_bwd(dy, x, mean, rstd, g, aux)
+        else:
+            dx, dg, db = ops.group_norm_nhwc_bwd(dy, x, mean, rstd, g, gate=aux if ctx.act == "relu" else None)
         return dx, dg, db, None, None
 
 
-def group_norm(x, gn, relu: bool):
-    check_group_size(x.shape[-1], gn.num_groups)
+def _group_norm(x, gn, act: str, what: str):
+    check_group_size(x.shape[-1], gn.num_groups, what, group4=act == "silu")
     if gn.weight is None:
-        raise UcHipError("group_norm: GroupNorm(affine=False) has no HIP path")
-    return GroupNormFn.apply(x, gn.weight, gn.bias, gn, relu)
+        raise UcHipError(f"{what}: GroupNorm(affine=False) has no HIP path")
+    return GroupNormFn.apply(x, gn.weight, gn.bias, gn, act)
+
+
+def group_norm(x, gn, relu: bool):
+    return _group_norm(x, gn, "relu" if relu else "none", "group_norm")
+
+
+def group_norm_silu(x, gn):
+    return _group_norm(x, gn, "silu", "group_norm_silu")
 
 
 @_sink_aware
@@ -1606,105 +1655,6 @@ def resize_bilinear(x, Ho: int, Wo: int, align_corners: bool):
     return ResizeBilinearFn.apply(x, Ho, Wo, align_corners)
 
 
-def _conv3x3_padded_weights(conv, dt, cin_pad: int, cout_pad: int):
-    "conv3x3 weights [cout_pad, 9 * cin_pad] (K ordered (ky, kx, c)) with zero rows / columns for the padded channels; bias fp32 [cout_pad]"
-    def build():
-        w = torch.zeros((cout_pad, 3, 3, cin_pad), dtype=torch.float32, device=conv.weight.device)
-        w[:conv.out_channels, :, :, :conv.in_channels] = conv.weight.detach().float().permute(0, 2, 3, 1)
-        b = torch.zeros(cout_pad, dtype=torch.float32, device=conv.weight.device)
-        if conv.bias is not None:
-            b[:conv.out_channels] = conv.bias.detach().float()
-        return w.reshape(cout_pad, -1).to(dt).contiguous(), b
-    return engine.prepared(conv, ("c3pad", dt, cin_pad, cout_pad), (conv.weight, conv.bias), build)
-
-
-def _conv3x3_padded_rot_weight(conv, dt, cin_pad: int, cout_pad: int):
-    "data-gradient weight [cin_pad, 9 * cout_pad], K ordered (ky', kx', o) = W[o, c, 2 - ky', 2 - kx'] (see _conv3x3_rot_weight)"
-    def build():
-        w = torch.zeros((cin_pad, 3, 3, cout_pad), dtype=torch.float32, device=conv.weight.device)
-        w[:conv.in_channels, :, :, :conv.out_channels] = conv.weight.detach().float().flip(2, 3).permute(1, 2, 3, 0)
-        return w.reshape(cin_pad, -1).to(dt).contiguous()
-    return engine.prepared(conv, ("c3padrot", dt, cin_pad, cout_pad), (conv.weight,), build)
-
-
-@_sink_aware
-class Conv3x3PaddedFn(Function):
-    """Zero-padded 3x3 convolution (stride 1) of an NHWC map whose channel count was padded with zero channels to `cin_pad`, to
-    `cout_pad` output channels (zero weight rows): the output block's Conv2d(64 + 2 -> 32) and Conv2d(32 -> dim_out, 3).  residual
-    [B, H, W, cout_pad] (optional) is added in the epilogue (the dense encoder's ResidualBlock: conv2 + shortcut)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, conv, cout_pad, out_dtype, residual=None):
-        x = _c(x)
-        B, H, W, cin_pad = x.shape
-        w, b = _conv3x3_padded_weights(conv, x.dtype, cin_pad, cout_pad)
-        ctx.save_for_backward(x)
-        ctx.meta = (conv, cout_pad, bias is not None)
-        ctx.res_dtype = None if residual is None else residual.dtype
-        r = None if residual is None else _c(residual).reshape(-1, cout_pad)
-        return ops.gemm(x, w, b, residual=r, conv=(B, H, W, cin_pad, 1), out_dtype=out_dtype).view(B, H, W, cout_pad)
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        conv, cout_pad, has_b = ctx.meta
-        B, H, W, cin_pad = x.shape
-        dt = x.dtype
-        dy = _c(dy)
-        dz = _as_dt(dy, dt)
-        if has_b and dy.dtype != dt:       # an fp32 cotangent (the head's last layer): the bias gradient sums it unrounded
-            dWg, db = _wgrad_conv(dz, x, 1, False)[0], _colsum(dy.view(-1, cout_pad))
-        else:
-            dWg, db = _wgrad_conv(dz, x, 1, False, has_b)
-        dW = dWg.view(cout_pad, 3, 3, cin_pad)[:conv.out_channels, :, :, :conv.in_channels].permute(0, 3, 1, 2)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = ops.gemm(dz, _conv3x3_padded_rot_weight(conv, dt, cin_pad, cout_pad), conv=(B, H, W, cout_pad, 1)).view(B, H, W, cin_pad)
-        dres = None
-        if ctx.res_dtype is not None and ctx.needs_input_grad[6]:
-            dres = dy if dy.dtype == ctx.res_dtype else _as_dt(dy, ctx.res_dtype)
-        return dx, dW, (db[:conv.out_channels] if has_b else None), None, None, None, dres
-
-
-@_sink_aware
-class OutConv1x1Fn(Function):
-    """The head's last 1x1 convolution (dim_out channels, zero-padded to `cpad`; fp32 output): PaddedConv1x1Fn whose bias gradient is the
-    column sum of the fp32 cotangent itself, not of its copy rounded to the operand dtype (a sum over every pixel of the image in which
-    the rounding errors of the summands do not average out against a cancelling total)."""
-
-    @staticmethod
-    def forward(ctx, x2d, weight, bias, conv, dt, cpad):
-        x2d = _c(x2d)
-        xb = x2d if x2d.dtype == dt else ops.convert(x2d, dt)
-        w, b = padded_conv1x1_weights(conv, dt, cpad)
-        ctx.save_for_backward(xb)
-        ctx.meta = (conv, dt, x2d.dtype, weight.shape, bias is not None, cpad)
-        return ops.gemm(xb, w, b, out_dtype=torch.float32)
-
-    @staticmethod
-    def backward(ctx, dy):
-        (xb,) = ctx.saved_tensors
-        conv, dt, x_dtype, wshape, has_b, cpad = ctx.meta
-        n = wshape[0]
-        dy = _c(dy)
-        dyb = _as_dt(dy, dt)
-        dW, _ = _wgrad(dyb, xb, dt)
-        db = _colsum(dy)[:n] if has_b else None
-        dx = None
-        if ctx.needs_input_grad[0]:
-            def padded32():
-                w = torch.zeros(cpad, conv.in_channels, device=conv.weight.device)
-                w[:n] = conv.weight.detach().reshape(n, -1).float()
-                return w
-            dx = ops.gemm(dyb, _w_t(conv, "c1pad", (conv.weight,), padded32, dt), out_dtype=x_dtype)
-        return dx, dW[:n].reshape(wshape), db, None, None, None
-
-
-def out_conv1x1(x, conv, dt, cpad):
-    B, H, W, Cin = x.shape
-    return OutConv1x1Fn.apply(x.reshape(-1, Cin), conv.weight, conv.bias, conv, dt, cpad).view(B, H, W, cpad)
-
-
 def check_conv3x3_replicate(conv) -> None:
     if conv.padding_mode != "replicate":
         raise UcHipError(f"conv3x3_replicate: padding_mode={conv.padding_mode!r} has no HIP path (supported: 'replicate')")
@@ -1723,66 +1673,9 @@ def conv3x3_replicate(x, conv, residual=None, relu_out: bool = False, out_dtype=
     channels (zero beyond the real ones).  padded: x is already the replicate-padded map (several convolutions of one map share
     one pad pass and one adjoint)."""
     check_conv3x3_replicate(conv)
-    cin_pad, cout_pad = x.shape[-1], head_pad(conv.out_channels, 8)
     xp = x if padded else ReplicatePadFn.apply(x)
-    if cin_pad == conv.in_channels and cout_pad == conv.out_channels and out_dtype in (None, x.dtype):
-        yp = Conv3x3Fn.apply(xp, conv.weight, conv.bias, None, None, conv, False, None, None)
-    else:
-        yp = Conv3x3PaddedFn.apply(xp, conv.weight, conv.bias, conv, cout_pad, out_dtype)
+    yp = Conv3x3Fn.apply(xp, conv.weight, conv.bias, None, None, conv, False, None, None, head_pad(conv.out_channels, 8), out_dtype)
     return CropAddFn.apply(yp, residual, relu_out)
-
-
-def _convt_padded_weights(ct, dt, kpad: int):
-    "engine.convt_weights with the input-channel (K) axis zero-padded to kpad columns"
-    k = ct.kernel_size[0]
-
-    def build():
-        w = torch.zeros((k * k * ct.out_channels, kpad), dtype=dt, device=ct.weight.device)
-        w[:, :ct.in_channels] = ct.weight.detach().permute(2, 3, 1, 0).reshape(k * k * ct.out_channels, ct.in_channels).to(dt)
-        b = None if ct.bias is None else ct.bias.detach().float().repeat(k * k).contiguous()
-        return w, b
-    return engine.prepared(ct, ("ctpad", dt, kpad), (ct.weight, ct.bias), build)
-
-
-@_sink_aware
-class ConvTransposePaddedFn(Function):
-    "ConvTransposeFn on a map whose channel axis was zero-padded to a multiple of the dense GEMM's K granule (514 -> 576, ...)."
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, ct):
-        x = _c(x)
-        B, H, W, kpad = x.shape
-        k = ct.kernel_size[0]
-        w, b = _convt_padded_weights(ct, x.dtype, kpad)
-        x2 = x.view(-1, kpad)
-        ctx.save_for_backward(x2)
-        ctx.meta = (ct, k, (B, H, W, kpad), bias is not None)
-        return ops.convt_scatter(ops.gemm(x2, w, b), B, H, W, k, ct.out_channels)
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x2,) = ctx.saved_tensors
-        ct, k, (B, H, W, kpad), has_b = ctx.meta
-        dt = x2.dtype
-        Cout, Cin = ct.out_channels, ct.in_channels
-        dyg = ops.convt_gather(_as_dt(_c(dy), dt), k)
-        dWg, dbg = _wgrad(dyg, x2, dt, has_b)
-        dW = dWg.view(k, k, Cout, kpad)[..., :Cin].permute(3, 2, 0, 1)
-        db = dbg.view(k * k, Cout).sum(0) if has_b else None
-        dx = None
-        if ctx.needs_input_grad[0]:
-            def padded32():
-                w = torch.zeros((k * k * Cout, kpad), dtype=torch.float32, device=ct.weight.device)
-                w[:, :Cin] = ct.weight.detach().permute(2, 3, 1, 0).reshape(k * k * Cout, Cin).float()
-                return w
-            dx = ops.gemm(dyg, _w_t(ct, ("ctpad", kpad), (ct.weight,), padded32, dt)).view(B, H, W, kpad)
-        return dx, dW, db, None
-
-
-def conv_transpose_padded(x, ct):
-    if ct.kernel_size != ct.stride or ct.kernel_size[0] != ct.kernel_size[1] or ct.padding != (0, 0) or ct.output_padding != (0, 0):
-        raise UcHipError("conv_transpose_padded: only ConvTranspose2d(kernel = stride, no padding) has a HIP path")
-    return ConvTransposePaddedFn.apply(x, ct.weight, ct.bias, ct)
 
 
 def _cat_k_weights(layers, dt):
@@ -1867,15 +1760,7 @@ class MlpFn(Function):
         dyb = _as_dt(_c(dy), dt)
         if drops is not None and drops.has_out:
             dyb = _drop_out(dyb, drops)
-        dW2, db2, _, w2t = _out_linear_bwd(dyb, a, fc2, None, has_b2, dt)
-        if act != "none" and dt == torch.bfloat16 and w2t.shape[1] % 64 == 0:
-            du = ops.gemm(dyb, w2t, dact=(u, act))          # act'(u) applied in the data-gradient GEMM's epilogue
-        else:
-            da = ops.gemm(dyb, w2t)
-            du = ops.act_bwd(da, u, act) if act != "none" else da
-        if drops is not None and drops.mid is not None:
-            du = ops.mask_scale(du, drops.mid, 0, drops.mid_scale)
-        dW1, db1 = _wgrad(du, h, dt, has_b1, sink=[(fc1.weight, 0, fc1.weight.shape[0])], bias_sink=[fc1.bias])
+        dW2, db2, _, du, dW1, db1 = _mlp_bwd(dyb, h, u, a, fc1, fc2, None, act, dt, has_b1, has_b2, drops)
         dx = ops.gemm(du, lin_weight_t(fc1, dt), out_dtype=x_dtype) if ctx.needs_input_grad[0] else None
         return (dx, dW1, db1, dW2, db2) + (None,) * 5
 
@@ -1942,11 +1827,11 @@ def act(u, name: str):
 
 
 def conv3x3_padded(x, conv, cout_pad: int, out_dtype=None, residual=None):
-    "Conv2d(k=3, padding=1) on an NHWC map with zero-padded channel counts (Conv3x3PaddedFn), residual added in the epilogue"
+    "Conv2d(k=3, padding=1) on an NHWC map with zero-padded channel counts (Conv3x3Fn), residual added in the epilogue"
     if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
             or conv.padding_mode != "zeros":
         raise UcHipError("conv3x3_padded: only a dense zero-padded 3x3 convolution of stride 1 has a HIP path")
-    return Conv3x3PaddedFn.apply(x, conv.weight, conv.bias, conv, cout_pad, out_dtype or x.dtype, residual)
+    return Conv3x3Fn.apply(x, conv.weight, conv.bias, residual, None, conv, False, None, None, cout_pad, out_dtype or x.dtype)
 
 
 def _ln_args(ln):
@@ -2093,44 +1978,6 @@ def haar_unpatch(rows, Cn: int):
     return HaarUnpatchFn.apply(rows, Cn)
 
 
-def check_group_size_silu(C: int, G: int, what: str = "group_norm_silu") -> None:
-    "what uc_group_norm_silu_nhwc would reject, said before any tensor is touched"
-    if G <= 0 or C % G != 0 or ((C // G) % 8 != 0 and C // G != 4):
-        raise UcHipError(f"{what}: {C} channels in {G} groups: channels per group ({C / max(G, 1):g}) must be a multiple of 8 or 4 "
-                         "(uc_group_norm_silu_nhwc)")
-
-
-@_sink_aware
-class GroupNormSiluFn(Function):
-    "y = silu(GroupNorm(x)) on an NHWC map; the backward recomputes the pre-activation from x"
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, gn):
-        x = _c(x)
-        g, b = engine.ln_params(gn)
-        y, mean, rstd = ops.group_norm_silu_nhwc(x, g, b, gn.num_groups, gn.eps)
-        ctx.save_for_backward(x, g, b, mean, rstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, g, b, mean, rstd = ctx.saved_tensors
-        dx, dg, db = ops.group_norm_silu_nhwc_bwd(_as_dt(_c(dy), x.dtype), x, mean, rstd, g, b)
-        return dx, dg, db, None
-
-
-def group_norm_silu(x, gn):
-    check_group_size_silu(x.shape[-1], gn.num_groups)
-    if gn.weight is None:
-        raise UcHipError("group_norm_silu: GroupNorm(affine=False) has no HIP path")
-    return GroupNormSiluFn.apply(x, gn.weight, gn.bias, gn)
-
-
-def _down2_weight(conv):
-    "fp32 [Cout, 9 Cin], K ordered (ky, kx, c)"
-    return conv.weight.detach().float().permute(0, 2, 3, 1).reshape(conv.out_channels, -1).contiguous()
-
-
 @_sink_aware
 class Down2ConvFn(Function):
     """The tokenizer's Downsample: F.pad(x, (0, 1, 0, 1)) + Conv2d(k = 3, stride = 2, padding = 0) on an NHWC map, as operand rows
@@ -2156,7 +2003,7 @@ class Down2ConvFn(Function):
         dW = dWg.view(conv.out_channels, 3, 3, Cin).permute(0, 3, 1, 2)
         dx = None
         if ctx.needs_input_grad[0]:
-            drows = ops.gemm(dy2, _w_t(conv, "down2", (conv.weight,), lambda: _down2_weight(conv), dt))
+            drows = ops.gemm(dy2, _w_t(conv, "down2", (conv.weight,), lambda: engine.conv3x3_weight2d(conv.weight), dt))
             dx = ops.down2_gather_bwd(drows, B, H, W)
         return dx, dW, db, None
 

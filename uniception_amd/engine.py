@@ -21,6 +21,7 @@ from typing import Optional, Sequence
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import ops
 from ._lib import UcHipError
@@ -499,11 +500,22 @@ def conv1x1_weights(conv: nn.Conv2d, dtype: torch.dtype):
                     lambda: (conv.weight.detach().reshape(conv.out_channels, -1).to(dtype).contiguous(), _f32c(conv.bias)))
 
 
-def conv3x3_weights(conv: nn.Conv2d, dtype: torch.dtype):
-    """[Cout, 9*Cin] with K ordered (ky,kx,c) to match the NHWC implicit-GEMM gather."""
-    return prepared(conv, ("c3", dtype), (conv.weight, conv.bias),
-                    lambda: (conv.weight.detach().permute(0, 2, 3, 1).reshape(conv.out_channels, -1).to(dtype).contiguous(),
-                             _f32c(conv.bias)))
+def conv3x3_weight2d(w4: torch.Tensor, cin_pad: Optional[int] = None, cout_pad: Optional[int] = None) -> torch.Tensor:
+    """fp32 [cout_pad, 9*cin_pad] of a [Cout, Cin, 3, 3] weight, K ordered (ky,kx,c) to match the NHWC implicit-GEMM gather; zero rows /
+    columns for the padded channels."""
+    Cout, Cin = w4.shape[:2]
+    w = F.pad(w4.detach().float().permute(0, 2, 3, 1), (0, (cin_pad or Cin) - Cin, 0, 0, 0, 0, 0, (cout_pad or Cout) - Cout))
+    return w.reshape(w.shape[0], -1).contiguous()
+
+
+def conv3x3_weights(conv: nn.Conv2d, dtype: torch.dtype, cin_pad: Optional[int] = None, cout_pad: Optional[int] = None):
+    """(conv3x3_weight2d in dtype, bias fp32 [cout_pad] | None); no pad = the convolution's own channel counts."""
+    cin_pad, cout_pad = cin_pad or conv.in_channels, cout_pad or conv.out_channels
+
+    def build():
+        b = None if conv.bias is None else F.pad(conv.bias.detach().float(), (0, cout_pad - conv.out_channels)).contiguous()
+        return conv3x3_weight2d(conv.weight, cin_pad, cout_pad).to(dtype).contiguous(), b
+    return prepared(conv, ("c3", dtype, cin_pad, cout_pad), (conv.weight, conv.bias), build)
 
 
 def conv3x3_bn_weights(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype: torch.dtype):
@@ -512,22 +524,27 @@ def conv3x3_bn_weights(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype: torch.dtype):
     (libs/croco/dpt_block.py:125-176).  Same layout as conv3x3_weights."""
     def build():
         s = (bn.weight.detach().float() if bn.weight is not None else torch.ones_like(bn.running_var)) / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-        w = (conv.weight.detach().float() * s[:, None, None, None]).permute(0, 2, 3, 1).reshape(conv.out_channels, -1).to(dtype).contiguous()
+        w = conv3x3_weight2d(conv.weight.detach().float() * s[:, None, None, None]).to(dtype).contiguous()
         b0 = conv.bias.detach().float() if conv.bias is not None else torch.zeros_like(s)
         beta = bn.bias.detach().float() if bn.bias is not None else torch.zeros_like(s)
         return w, (beta + (b0 - bn.running_mean.detach().float()) * s).contiguous()
     return prepared(conv, ("c3bn", dtype), (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), build)
 
 
-def convt_weights(ct: nn.ConvTranspose2d, dtype: torch.dtype):
-    """ConvTranspose2d(k=s): weight [Cin,Cout,k,k] -> GEMM weight [(u,v,o), Cin]; bias repeated per (u,v)."""
-    k = ct.kernel_size[0]
+def convt_weight2d(ct: nn.ConvTranspose2d, kpad: Optional[int] = None) -> torch.Tensor:
+    """ConvTranspose2d(k=s): weight [Cin,Cout,k,k] -> fp32 GEMM weight [(u,v,o), kpad], the input-channel (K) axis zero-padded to kpad."""
+    w = ct.weight.detach().float().permute(2, 3, 1, 0).reshape(-1, ct.in_channels)
+    return F.pad(w, (0, (kpad or ct.in_channels) - ct.in_channels)).contiguous()
+
+
+def convt_weights(ct: nn.ConvTranspose2d, dtype: torch.dtype, kpad: Optional[int] = None):
+    """(convt_weight2d in dtype, bias fp32 repeated per (u,v) | None); no pad = ct.in_channels."""
+    k, kpad = ct.kernel_size[0], kpad or ct.in_channels
 
     def build():
-        w = ct.weight.detach().permute(2, 3, 1, 0).reshape(k * k * ct.out_channels, ct.in_channels).to(dtype).contiguous()
         b = None if ct.bias is None else ct.bias.detach().float().repeat(k * k).contiguous()
-        return w, b
-    return prepared(ct, ("ct", dtype), (ct.weight, ct.bias), build)
+        return convt_weight2d(ct, kpad).to(dtype).contiguous(), b
+    return prepared(ct, ("ct", dtype, kpad), (ct.weight, ct.bias), build)
 
 
 def patch_weights(conv: nn.Conv2d, dtype: torch.dtype):

@@ -73,7 +73,7 @@ class ResnetBlock(nn.Module):
         if self.dropout.p > 0:
             raise UcHipError(f"ResnetBlock: dropout={self.dropout.p} has no HIP path (supported: 0.0)")
         for gn in (self.norm1, self.norm2):
-            autograd.check_group_size_silu(gn.num_channels, gn.num_groups, "ResnetBlock")
+            autograd.check_group_size(gn.num_channels, gn.num_groups, "ResnetBlock", group4=True)
 
     def forward_nhwc(self, x: torch.Tensor) -> torch.Tensor:
         h = autograd.conv3x3(autograd.group_norm_silu(x, self.norm1), self.conv1)
@@ -174,7 +174,7 @@ class Encoder(nn.Module):
 
     def check_supported(self) -> None:
         _check_tree(self)
-        autograd.check_group_size_silu(self.norm_out.num_channels, self.norm_out.num_groups, "Encoder.norm_out")
+        autograd.check_group_size(self.norm_out.num_channels, self.norm_out.num_groups, "Encoder.norm_out", group4=True)
         if self.conv_in.in_channels > LATENT_PAD or self.conv_out.out_channels > LATENT_PAD:
             raise UcHipError(f"Encoder: {self.conv_in.in_channels} patch coefficients / {self.conv_out.out_channels} latent channels exceed "
                              f"the padded width {LATENT_PAD}")
@@ -229,7 +229,7 @@ class Decoder(nn.Module):
 
     def check_supported(self) -> None:
         _check_tree(self)
-        autograd.check_group_size_silu(self.norm_out.num_channels, self.norm_out.num_groups, "Decoder.norm_out")
+        autograd.check_group_size(self.norm_out.num_channels, self.norm_out.num_groups, "Decoder.norm_out", group4=True)
         if self.conv_in.in_channels > LATENT_PAD or self.conv_out.out_channels % 8:
             raise UcHipError(f"Decoder: {self.conv_in.in_channels} latent channels exceed the padded width {LATENT_PAD}, or the "
                              f"{self.conv_out.out_channels} output coefficients are not a multiple of 8")
